@@ -22,12 +22,18 @@ on the library's stream); torch.distributed (gloo) only carries the 128-byte com
 time.  Headline at N > 1 = the same 2-scan job, weak scaling (N x the points on N x the floor area, every rank 1/N of each pair's
 queries) -- at N = 1 it is the BENCH workload.
 
-Output: the LAST line of stdout is one compact JSON object (< 4 KB: headline keys, `config`, `dtype`, the dominant kernel's `roofline`,
-`cpu_baseline`, `whole_run`, one summary per secondary leg under `legs`); the full result -- every kernel group, per-step arrays, the
-prose -- goes to bench_detail.json next to this file (and to gpurun_out/ when that directory exists).  The timed loop is the tool's:
-it ends with the iteration whose Run() reports convergence (`converged_at_iteration`; `steps` = the steps actually timed).
+A plain run (--gpus N --steps K --warmup W) does only what the headline needs: the scene, W untimed steps, the K timed steps, the
+result line.  The steps are the tool's loop run back to back: an iteration whose Run() reports convergence is the last of its job,
+and the next step is iteration 0 of the same job on a fresh handle (`converged_at_iteration`: the first such iteration;
+`job_restarts_in_timed_steps` in the detail), so `steps` = K always and no step after convergence is timed.  At the default
+--warmup 5 --steps 20 the job, which converges in iteration 25, never restarts.  --dump-outputs DIR writes what the last timed
+step computed (the clouds' poses, the per-pair counts and distance sums of that iteration) as float64 .npy files.
 
-Further legs (detail file; summaries in the line):
+Output: the LAST line of stdout is one compact JSON object (< 4 KB: headline keys, `config`, `dtype`, the dominant kernel's `roofline`,
+with --full also `cpu_baseline`, `whole_run` and one summary per secondary leg under `legs`); the full result -- every kernel group,
+per-step arrays, the prose -- goes to bench_detail.json next to this file (or to --detail).
+
+Further legs, --full only (detail file; summaries in the line):
   partial_overlap    (N = 1) the headline job on the partial-overlap room (30 - 60 % of the points find a partner): same
                      per-kernel table, so the no-partner branch of FindCorrespondencesFast is part of a measured steady state
   allpairs           BASELINE.json north_star's scaling target / configs[2] shape: 16 scans all-pairs (240 directed pairs, 90-unknown
@@ -36,6 +42,8 @@ Further legs (detail file; summaries in the line):
   image_registrator  (N = 1) configs[3] shape: 23 images of 6048 x 4032, THIN_PRISM_FISHEYE, ~10 M points, K = 5: residuals/s of the
                      accumulate pass, per-kernel roofline from HIP events, ms per RunOnCurrentScale iteration
   normal_estimation  (N = 1) SURVEY 8(d) (A'): normals/s for 20 M points, k = 32 and k = 8
+  regression, scanner_sampled   (N = 1) the headline job from round 4's start and on scanner-sampled scans
+  whole_run, candidates_per_query   (N = 1) add_cloud -> convergence on a fresh handle; the target points an exact search looks at
   cpu_baseline       the CPU restatement (oracle/, kind "port") on bounded samples of the same workloads, on this box's cores
 """
 import argparse
@@ -269,6 +277,44 @@ def run_icp(e3d, R, icp, d, thr, warmup, steps, warmed=False, first_warm_converg
     return dt, tot, warm, recs, per_rank, len(each), converged_at
 
 
+def run_icp_steps(e3d, R, new_handle, icp, it, d, thr, steps):
+    """The headline's timed region: exactly `steps` outer iterations, starting at iteration `it` of the job on `icp`.  The steps are
+    the tool's loop run back to back: when an iteration reports convergence, the next step is iteration 0 of the same job on a fresh
+    handle (new_handle(): add_point_cloud of both scans, untimed), so every timed step is one Run() the tool would make and none of
+    them is a step after convergence.  At the default --warmup 5 --steps 20 the job (converging in iteration 25) never restarts.
+    Returns run_icp's tuple summed over the segments between restarts, the handle of the last step and the number of restarts."""
+    dt, tot, warm, recs, n_rank, K, first_conv, restarts = 0.0, None, None, [], {}, 0, None, 0
+    while True:
+        seg = run_icp(e3d, R, icp, d, thr, it, steps - K, warmed=True)
+        dt += seg[0]
+        tot = seg[1] if tot is None else tot + seg[1]
+        warm = seg[2] if warm is None else warm
+        recs += seg[3]
+        for k, v in seg[4].items():
+            n_rank[k] = n_rank.get(k, 0.0) + v * seg[5]
+        K += seg[5]
+        if seg[6] is not None and first_conv is None:
+            first_conv = seg[6]
+        if K >= steps:
+            break
+        icp = None                                            # (the converged handle's memory goes before the next one is made)
+        icp, it, restarts = new_handle(), 0, restarts + 1
+    per_rank = {k: v / max(K, 1) for k, v in n_rank.items()}
+    return dt, tot, warm, recs, per_rank, K, first_conv, icp, restarts
+
+
+def dump_outputs(path, icp, n_clouds):
+    """--dump-outputs DIR: what a caller of the timed path holds after its last step -- every cloud's global_T_cloud (the poses
+    GetResultGlobalTCloud returns) and that iteration's per-pair correspondence counts and distance sums -- as float64 .npy files."""
+    os.makedirs(path, exist_ok=True)
+    poses = np.stack([icp.get_result_global_T_cloud(i) for i in range(n_clouds)]).astype(np.float64)
+    prs = icp.pair_records()
+    last = max(r[0] for r in prs) if prs else None
+    pairs = np.array([[r[1], r[2], r[3], r[4]] for r in prs if r[0] == last], np.float64).reshape(-1, 4)
+    np.save(os.path.join(path, "global_T_cloud.npy"), poses)                       # [clouds, 4, 4]
+    np.save(os.path.join(path, "last_step_pairs.npy"), pairs)                      # [pairs, 4]: source, target, count, distance sum
+
+
 def whole_run(e3d, scans, d, thr, device, max_iterations=100):
     """What the tool does with two scans already in memory (src/exe/icp_scan_aligner.cc:280-372 without the file I/O): AddPointCloud
     for every scan, then Run(d, it, 1, thr) from iteration 0 until it reports convergence or --max_iterations (100, BASELINE.json
@@ -408,34 +454,52 @@ def leg_terrace(e3d, synth, R, args, dev, partial=False, variant=None):
     scans = synth.make_scene(2, n_points, seed=1234, sigma=0.002, device=dev, room_scale=room_scale, partial=partial, perturb=perturb, scanner=(variant == "scanner"))
     torch.cuda.synchronize()
     whole = None
-    if world == 1 and not secondary and not args.no_whole_run:
+    if world == 1 and not secondary and args.full and not args.no_whole_run:
         whole = whole_run(e3d, scans, d, thr, R.local_rank)
-    icp = e3d.PointToPlaneICP(device=R.local_rank)
-    for s in scans:
-        icp.add_point_cloud(s["xyz"], s["normals"], s["T_init"], False)
-    if R.comm:
-        icp.set_comm(R.comm)
-    warm_conv = None
-    for it in range(args.warmup):                            # untimed warm-up steps (the timed region follows below)
+
+    def new_handle():
+        h = e3d.PointToPlaneICP(device=R.local_rank)
+        for s in scans:
+            h.add_point_cloud(s["xyz"], s["normals"], s["T_init"], False)
+        if R.comm:
+            h.set_comm(R.comm)
+        return h
+    icp = new_handle()
+    warm_conv, it = None, 0
+    for _ in range(args.warmup):                             # untimed warm-up steps (the timed region follows below)
         if icp.run(d, it, 1, thr, False):
-            warm_conv = it
-            break
+            warm_conv = it if warm_conv is None else warm_conv
+            if secondary:
+                break
+            icp, it = None, 0                                # headline: the warm-up goes on with the job from its start (run_icp_steps)
+            icp = new_handle()
+        else:
+            it += 1
     cand = None
-    if world == 1 and (variant == "scanner" or not secondary):
+    if world == 1 and (variant == "scanner" or (not secondary and args.full)):
         cand = candidates_per_query(scans, [icp.get_result_global_T_cloud(i) for i in range(2)], d, dev)
         torch.cuda.empty_cache()
     base = None
-    if R.rank == 0 and world == 1 and not args.no_cpu_baseline and not secondary:
+    if R.rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not secondary:
         # slab width chosen for ~4 M points per scan at this density (floor + two walls = 16 m^2 per metre of x); started from the
         # poses the GPU run has reached after its warm-up, so both sides are timed in the same regime
         width = min(10.0, 4.0e6 / (n_points / 242.6 * 16.0))
         base = cpu_baseline_icp(scans, d, thr, (4.0, 4.0 + width), n_points, poses=[icp.get_result_global_T_cloud(i) for i in range(2)],
-                                first_iteration=args.warmup)
-    del scans
+                                first_iteration=it)
+    if secondary:
+        del scans
     torch.cuda.empty_cache()
     if R.comm:
         R.comm.stats(reset=True)
-    dt, tot, warm, recs, per_rank, K, converged_at = run_icp(e3d, R, icp, d, thr, args.warmup, args.steps, warmed=True, first_warm_converged=warm_conv)
+    restarts = None
+    if secondary:
+        dt, tot, warm, recs, per_rank, K, converged_at = run_icp(e3d, R, icp, d, thr, args.warmup, args.steps, warmed=True, first_warm_converged=warm_conv)
+    else:
+        dt, tot, warm, recs, per_rank, K, converged_at, icp, restarts = run_icp_steps(e3d, R, new_handle, icp, it, d, thr, args.steps)
+        converged_at = warm_conv if warm_conv is not None else converged_at
+        if args.dump_outputs and R.rank == 0:
+            dump_outputs(args.dump_outputs, icp, 2)
+        del scans
     if K == 0:
         raise SystemExit("bench.py: the run converged inside the %d warm-up iterations (iteration %d): nothing to time" % (args.warmup, warm_conv))
     kernels, accounted, m = icp_kernel_table(tot, world, K, 2, n_points)      # (every rank transforms the whole clouds)
@@ -481,6 +545,8 @@ def leg_terrace(e3d, synth, R, args, dev, partial=False, variant=None):
                              "(their summed_ms_per_iter add up to breakdown_ms_per_iter.kernels_accounted; the rest of ms_per_step is host work and synchronisation)",
                      "kernels": kernels},
     }
+    if restarts is not None:
+        out["job_restarts_in_timed_steps"] = restarts
     if world > 1:
         out["per_rank_rank0"] = per_rank
     if R.comm:
@@ -867,6 +933,11 @@ def main():
     ap.add_argument("--perturb", type=float, default=2.5, help="scale of the headline scene's initial misalignment (synth.perturbation): 2.5 = 2.5 degrees and "
                     "(5, -2.5, 2.5) cm, the smallest start from which the run still needs the 25 outer iterations of --warmup 5 --steps 20 "
                     "(it converges in iteration 25; tools/icp_converge.py: 2.2 -> 23, 2.4 -> 24, 2.5 -> 25, 3.0 -> 29)")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline figure: the CPU baseline, the whole run, the candidates "
+                    "per query, the regression / scanner / partial-overlap / all-pairs legs, ImageRegistrator and normal estimation (each "
+                    "--no-* below drops one of them)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed (the "
+                    "clouds' global_T_cloud, that iteration's per-pair counts and distance sums) as float64 .npy files under DIR")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-whole-run", action="store_true", help="skip the add_cloud -> convergence run of the headline leg (N = 1)")
     ap.add_argument("--no-scale-model", action="store_true", help="skip the rank-0-of-8 run of the all-pairs leg (N = 1)")
@@ -889,6 +960,8 @@ def main():
     ap.add_argument("--reg-points", type=int, default=10_000_000)
     ap.add_argument("--normals-points", type=int, default=20_000_000)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         raise SystemExit(spawn(args))                           # never a silent 1-GPU run
@@ -933,15 +1006,15 @@ def main():
         R.close()
         return
     out = leg_terrace(e3d, synth, R, args, dev)
-    if world == 1 and not args.no_regression:
+    if world == 1 and args.full and not args.no_regression:
         out["regression"] = leg_terrace(e3d, synth, R, args, dev, variant="regression")
-    if world == 1 and not args.no_scanner:
+    if world == 1 and args.full and not args.no_scanner:
         out["scanner_sampled"] = leg_terrace(e3d, synth, R, args, dev, variant="scanner")
-    if world == 1 and not args.no_partial:
+    if world == 1 and args.full and not args.no_partial:
         out["partial_overlap"] = leg_terrace(e3d, synth, R, args, dev, partial=True)
-    if not args.no_allpairs:
+    if args.full and not args.no_allpairs:
         out["allpairs"] = leg_allpairs(e3d, synth, R, args, dev)
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_reg:
             out["image_registrator"] = leg_image_registrator(e3d, synth, args, dev)
         if not args.no_normals:

@@ -120,3 +120,43 @@ def test_a_run_that_converges_in_the_warm_up_times_nothing():
     icp = _FakeICP(3)
     dt, tot, warm, recs, per_rank, steps_run, converged_at = bench.run_icp(None, _FakeRanks(), icp, 0.01, 1e-10, 5, 20)
     assert steps_run == 0 and converged_at == 3 and icp.calls == [0, 1, 2, 3]
+
+
+@pytest.mark.parametrize("conv,steps,expect_calls,expect_restarts", [
+    (100, 20, list(range(5, 25)), 0),                                        # the default: the job never converges inside the steps
+    (24, 20, list(range(5, 25)), 0),                                         # converges in the last timed step: nothing after it
+    (18, 20, list(range(5, 19)) + list(range(0, 6)), 1),                     # the next step is iteration 0 of the same job, afresh
+    (5, 20, [5] + [0, 1, 2, 3, 4, 5] * 3 + [0], 4)])
+def test_headline_times_exactly_the_requested_steps(conv, steps, expect_calls, expect_restarts):
+    """--steps sets the number of timed steps: a job that converges before they are done starts again from iteration 0 on a
+    fresh handle (untimed set-up), so every timed step is one Run() of the tool's loop and none comes after a convergence."""
+    made = []
+
+    def new_handle():
+        made.append(_FakeICP(conv))
+        return made[-1]
+    first = new_handle()
+    dt, tot, warm, recs, per_rank, K, converged_at, last, restarts = bench.run_icp_steps(None, _FakeRanks(), new_handle, first, 5, 0.01, 1e-10, steps)
+    calls = [c for h in made for c in h.calls]
+    assert K == steps and len(recs) == steps and tot[0] == 1000 * steps and calls == expect_calls
+    assert restarts == expect_restarts and len(made) == 1 + restarts and last is made[-1]
+    assert converged_at == (conv if conv < 5 + steps else None)
+    assert all(c <= conv for c in calls)
+
+
+def test_dump_outputs_writes_the_last_step(tmp_path):
+    import numpy as np
+
+    class _Handle:
+        def get_result_global_T_cloud(self, i):
+            T = np.eye(4, dtype=np.float32)
+            T[0, 3] = i + 0.5
+            return T
+
+        def pair_records(self):
+            return [(7, 0, 1, 100, 1.5), (7, 1, 0, 90, 1.25), (8, 0, 1, 120, 2.0), (8, 1, 0, 110, 1.75)]
+    bench.dump_outputs(str(tmp_path / "out"), _Handle(), 2)
+    P = np.load(tmp_path / "out" / "global_T_cloud.npy")
+    Q = np.load(tmp_path / "out" / "last_step_pairs.npy")
+    assert P.dtype == np.float64 and P.shape == (2, 4, 4) and P[1, 0, 3] == 1.5
+    assert Q.dtype == np.float64 and Q.tolist() == [[0, 1, 120, 2.0], [1, 0, 110, 1.75]]

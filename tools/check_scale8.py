@@ -1,4 +1,4 @@
-"""Reads the bench lines of a 1 / 2 / 4 / 8-GPU run of bench.py (the LAST stdout line of each run: the compact JSON object) and prints
+"""Reads the bench lines of a 1 / 2 / 4 / 8-GPU run of bench.py --full (the LAST stdout line of each run: the compact JSON object) and prints
 what the first multi-GPU run has to be read against: weak-scaling efficiency of the headline (2 scans, N x the points on N GPUs),
 strong-scaling speed-up of the all-pairs job next to the single-GPU run's `scale_model` (rank 0 of a world of 8 measured on one
 GPU: an upper bound without collectives), and the time the all-reduces took.

@@ -23,7 +23,7 @@ for st in $STAGES; do
   case $st in
     trace)
       rm -rf /tmp/r5p_trace
-      timeout 600 rocprofv3 --kernel-trace --stats -d /tmp/r5p_trace -o b -- python $R/bench.py > $O/bench_traced.json 2> $O/bench_traced.err
+      timeout 600 rocprofv3 --kernel-trace --stats -d $TMPDIR/r5p_trace -o b -- python $R/bench.py --full > $O/bench_traced.json 2> $O/bench_traced.err
       echo "[trace] rc=$?"
       $SUM /tmp/r5p_trace/b_results.db $O/bench_kernel_stats.txt "" > /dev/null 2>&1
       head -25 $O/bench_kernel_stats.txt | cut -c1-60,150-230 ;;
