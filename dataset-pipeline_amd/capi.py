@@ -141,6 +141,10 @@ SIGNATURES = {
                                              C.c_void_p, C.c_void_p]),
     "e3d_reg_set_shard": (C.c_int, [C.c_void_p, C.c_int, C.c_int, ALLREDUCE_FN, ALLREDUCE_DEVICE_FN, C.c_void_p]),
     "e3d_reg_image_owner": (C.c_int, [C.c_void_p, C.c_int]),
+    "e3d_mesh_squared_distance": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float,
+                                            C.c_void_p, C.c_void_p]),
+    "e3d_create_splats": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float,
+                                      C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 
@@ -464,6 +468,49 @@ def local_outlier_removal(xyz, mean_k, distance_factor_threshold, negative=False
     if r < 0:
         _err("e3d_local_outlier_removal", r)
     return (inl.astype(bool), md) if return_distances else inl.astype(bool)
+
+
+def _mesh_arrays(vertices, triangles, keep):
+    v = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3) if not _is_torch(vertices) else vertices
+    t = np.ascontiguousarray(triangles, np.uint32).reshape(-1, 3)
+    keep.append(t)
+    return _ptr(v, np.float32, keep), int(v.shape[0]), C.c_void_p(t.ctypes.data), int(t.shape[0])
+
+
+def mesh_squared_distance(points, vertices, triangles, max_sq_distance=float("inf")):
+    """igl::AABB::squared_distance over a triangle mesh -> (squared distance[n] (+inf above max_sq_distance), closest triangle[n])."""
+    keep = []
+    n = int(points.shape[0])
+    vp, nv, tp, nt = _mesh_arrays(vertices, triangles, keep)
+    d = np.zeros(n, np.float32)
+    ids = np.zeros(n, np.int32)
+    r = lib().e3d_mesh_squared_distance(_ptr(points, np.float32, keep), n, vp, nv, tp, nt, float(max_sq_distance),
+                                        C.c_void_p(d.ctypes.data), C.c_void_p(ids.ctypes.data))
+    if r < 0:
+        _err("e3d_mesh_squared_distance", r)
+    return d, ids
+
+
+def create_splats(xyz, normals, vertices, triangles, distance_threshold=0.02, max_splat_size=float("inf"), timings=None):
+    """SplatCreator -> (vertices[4m,3], faces[2m,3], add_splat[n] bool, radius[n]).  timings: a dict that receives the index
+    build and splat pass times (ms)."""
+    keep = []
+    n = int(xyz.shape[0])
+    vp, nv, tp, nt = _mesh_arrays(vertices, triangles, keep)
+    out = np.empty((max(n, 1), 12), np.float32)           # room for a splat per point (pages are only touched where written)
+    flag = np.zeros(n, np.uint8)
+    rad = np.zeros(n, np.float32)
+    tm = np.zeros(2, np.float32)
+    m = lib().e3d_create_splats(_ptr(xyz, np.float32, keep), _ptr(normals, np.float32, keep), n, vp, nv, tp, nt, float(distance_threshold),
+                                float(max_splat_size), C.c_void_p(out.ctypes.data), n, C.c_void_p(flag.ctypes.data), C.c_void_p(rad.ctypes.data),
+                                C.c_void_p(tm.ctypes.data))
+    if m < 0:
+        _err("e3d_create_splats", m)
+    if timings is not None:
+        timings["index_ms"] = float(tm[0]); timings["splat_ms"] = float(tm[1])
+    s = np.arange(m, dtype=np.int32)[:, None] * 4
+    faces = np.concatenate([np.concatenate([s + 2, s + 1, s], 1), np.concatenate([s, s + 3, s + 2], 1)], 1).reshape(-1, 3)
+    return out[:m].reshape(-1, 3).copy(), faces, flag.astype(bool), rad
 
 
 # ---- (B) image registration kernels ------------------------------------------------------------------------------------

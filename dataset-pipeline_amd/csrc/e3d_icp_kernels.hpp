@@ -1,6 +1,8 @@
 // e3d_icp_kernels.hpp -- launch interface of the ICP kernels (see e3d_icp_kernels.hip).
 #pragma once
 
+#include <functional>
+
 #include "e3d_common.hpp"
 #include "e3d_kernels.hpp"
 
@@ -212,6 +214,12 @@ void sort_pairs_u32_u32(unsigned* keys_in, unsigned* keys_out, unsigned* vals_in
                         int end_bit, DevBuf<char>& temp, hipStream_t s, size_t n_reserve = 0);
 // in-place exclusive MAX scan of n unsigned values (rocPRIM, e3d_sort.hip); one-off per grid build
 void exclusive_max_scan_u32(unsigned* data, size_t n, DevBuf<char>& temp, hipStream_t s);
+// exclusive prefix sum of n 0/1 flags into 32-bit offsets (rocPRIM, e3d_sort.hip): the splat compaction
+void exclusive_sum_u8_u32(const unsigned char* in, unsigned* out, size_t n, DevBuf<char>& temp, hipStream_t s);
+// the exact kNN (e3d_normals.hip) of a finite cloud (host or device xyz) with each query's k-th squared distance (input order)
+// left on the device; `use(kth, query_order, stream)` runs while the kNN workspace is held: query_order lists the queries in
+// the pass's grid-cell order (w = input index as bits)
+void knn_kth_sqdist(const float* xyz, size_t n, int k, const std::function<void(const float*, const float4*, hipStream_t)>& use);
 void launch_compact_corr(const int* match_pos, const unsigned* order, size_t n, const unsigned* block_offsets, const float4* Gsrc,
                          const float4* LNsrc, const Affine& Tsrc, const float4* Gtgt, const float4* LNtgt,
                          const Affine& Ttgt, float4* A, float4* B, float4* C, size_t out_base, hipStream_t s);

@@ -1471,12 +1471,25 @@ static bool is_device_pointer(const void* ptr) {
   return attr.type == hipMemoryTypeDevice && attr.device == dev;
 }
 
+// each query's k-th squared distance: FLANN's f32 (query - neighbour) distance of the last list entry (+inf if the list is short)
+__global__ __launch_bounds__(256) void k_knn_kth(const float* __restrict__ xyz, const int* __restrict__ knn, size_t n, int k,
+                                                 float* __restrict__ kth) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int j = knn[i * (size_t)k + (size_t)(k - 1)];
+  kth[i] = j < 0 ? INFINITY : sqdist_l2(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2]);
+}
+
 // The exact kNN pass over a host cloud.  Results stay on the device: normals + curvature (if want_normals), the neighbour
 // index lists (if d_knn) and the mean neighbour distance (if d_mean), all in input order.
 // direct_n / direct_c: device buffers that take the normals / curvatures as they are computed (no staging in W.d_on / W.d_oc);
 // a cloud that already lies in device memory is read in place.
+// d_kth (needs want_knn): device buffer of n floats that receives each query's k-th squared distance, in input order.
+// query_order: receives the queries in the order the pass searched them (level-0 grid-cell order; w = input index as bits),
+// valid in W until its next pass.
 static void knn_pass(KnnWorkspace& W, const float* xyz, size_t n, int k, const float* viewpoint, bool want_normals, bool want_knn,
-                     bool want_mean, float* direct_n = nullptr, float* direct_c = nullptr) {
+                     bool want_mean, float* direct_n = nullptr, float* direct_c = nullptr, float* d_kth = nullptr,
+                     const float4** query_order = nullptr) {
     hipStream_t s = W.stream;
     DevBuf<float>&bbox_partial = W.bbox_partial, &bbox_out = W.bbox_out;
     DevBuf<int>* d_knn_out = want_knn ? &W.d_knn : nullptr;
@@ -1774,8 +1787,31 @@ static void knn_pass(KnnWorkspace& W, const float* xyz, size_t n, int k, const f
       cell *= level_step;
     }
     if (n_todo != 0) throw Error(E3D_ERR_INVALID, "e3d_normals_knn: internal error, unresolved queries remain");
+    if (d_kth) {
+      if (!knn_indices) throw Error(E3D_ERR_INVALID, "knn_pass: the k-th distance needs the neighbour lists");
+      hipLaunchKernelGGL(k_knn_kth, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, raw.p, d_knn.p, n, k, d_kth);
+      E3D_HIP(hipGetLastError());
+    }
+    if (query_order) *query_order = Q4.p;
 }
 
+}  // namespace e3d
+
+// e3d_splats.hip: the exact kNN of a finite cloud with each query's k-th squared distance left on the device; `use` runs on the
+// workspace's stream while the workspace is held
+void e3d::knn_kth_sqdist(const float* xyz, size_t n, int k, const std::function<void(const float*, const float4*, hipStream_t)>& use) {
+  if (k < 1 || k > kKnnMaxK) throw Error(E3D_ERR_INVALID, fmt("knn_kth_sqdist: k = %d outside [1, %d]", k, kKnnMaxK));
+  if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "knn_kth_sqdist: more than 2^31-1 points");
+  WorkspaceLease lease;
+  KnnWorkspace& W = *lease.ws;
+  W.d_mean.reserve(n);                 // (the mean-distance buffer holds the k-th distances: the pass computes no mean)
+  const float vp[3] = {0.f, 0.f, 0.f};
+  const float4* order = nullptr;
+  knn_pass(W, xyz, n, k, vp, false, true, false, nullptr, nullptr, W.d_mean.p, &order);
+  use(W.d_mean.p, order, W.stream);
+}
+
+namespace e3d {
 static void require_device() {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)

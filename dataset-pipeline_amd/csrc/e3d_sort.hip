@@ -52,4 +52,12 @@ void exclusive_max_scan_u32(unsigned* data, size_t n, DevBuf<char>& temp, hipStr
   E3D_HIP(rocprim::exclusive_scan(temp.p, bytes, data, data, 0u, n, rocprim::maximum<unsigned>(), s));
 }
 
+void exclusive_sum_u8_u32(const unsigned char* in, unsigned* out, size_t n, DevBuf<char>& temp, hipStream_t s) {
+  if (n == 0) return;
+  size_t bytes = 0;
+  E3D_HIP(rocprim::exclusive_scan(nullptr, bytes, in, out, 0u, n, rocprim::plus<unsigned>(), s));
+  temp.reserve(bytes);
+  E3D_HIP(rocprim::exclusive_scan(temp.p, bytes, in, out, 0u, n, rocprim::plus<unsigned>(), s));
+}
+
 }  // namespace e3d

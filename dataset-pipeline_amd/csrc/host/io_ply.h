@@ -6,6 +6,7 @@
 // "element camera" block PCL's PLYWriter appends.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <cstring>
 #include <fstream>
@@ -468,6 +469,27 @@ inline int savePLYFileBinaryXYZPcl(const std::string& path, const std::vector<fl
   f.write(reinterpret_cast<const char*>(vp), sizeof vp);
   const float zeros2[2] = {0, 0};
   f.write(reinterpret_cast<const char*>(zeros2), sizeof zeros2);
+  return f ? 0 : -1;
+}
+
+// pcl::io::savePLYFileBinary of a pcl::PolygonMesh of pcl::PointXYZ vertices (splat_creator.cc:224-229): x y z f32 vertices and
+// `list uchar int vertex_indices` triangles, binary little endian; an empty mesh is a valid file with 0 vertices and 0 faces
+inline int savePLYMeshBinary(const std::string& path, const float* xyz, size_t n_vertices, const int32_t* faces, size_t n_faces) {
+  std::ofstream f(path, std::ios::binary);
+  if (!f) { std::cerr << "[savePLYFile] cannot open " << path << std::endl; return -1; }
+  f << "ply\nformat binary_little_endian 1.0\nelement vertex " << n_vertices << "\nproperty float x\nproperty float y\nproperty float z\n"
+    << "element face " << n_faces << "\nproperty list uchar int vertex_indices\nend_header\n";
+  f.write(reinterpret_cast<const char*>(xyz), (std::streamsize)(n_vertices * 3 * sizeof(float)));
+  std::vector<unsigned char> rec(13 * std::min(n_faces, (size_t)1 << 16));
+  for (size_t b = 0; b < n_faces; b += (size_t)1 << 16) {
+    const size_t e = std::min(n_faces, b + ((size_t)1 << 16));
+    for (size_t i = b; i < e; ++i) {
+      unsigned char* r = &rec[13 * (i - b)];
+      r[0] = 3;
+      memcpy(r + 1, faces + 3 * i, 12);
+    }
+    f.write(reinterpret_cast<const char*>(rec.data()), (std::streamsize)(13 * (e - b)));
+  }
   return f ? 0 : -1;
 }
 

@@ -261,6 +261,27 @@ int e3d_normals_radius(const float* xyz, size_t n, float radius, const float vie
 int e3d_local_outlier_removal(const float* xyz, size_t n, int mean_k, double distance_factor_threshold, int negative,
                               uint8_t* inlier, float* mean_distances);
 
+/* ---- SplatCreator (src/exe/splat_creator.cc:75-235) ------------------------------------------------------------
+ * igl::AABB<MatrixXf,3>::squared_distance (thirdparty/igl/AABB.cpp:344-430) over a triangle mesh: per point the minimum over
+ * all triangles of point_simplex_squared_distance (f32, Ericson ch. 5) if it is <= max_sq_distance, else +inf (non-finite
+ * points: +inf).  closest_triangle (optional, n): the triangle of the minimum, the lowest id among equal minima, -1 with +inf.
+ * vertices n_vertices x 3, triangles n_triangles x 3 vertex indices; host or device pointers; a GPU index over the triangles
+ *  is built per call. */
+int e3d_mesh_squared_distance(const float* points, size_t n, const float* vertices, size_t n_vertices,
+                              const uint32_t* triangles, size_t n_triangles, float max_sq_distance,
+                              float* sq_distance, int32_t* closest_triangle);
+/* SplatCreator (src/exe/splat_creator.cc:75-235): returns the number of splats m (< 0: error).  A point with a NaN normal
+ * component is skipped; the splat radius is min(sqrtf(5th smallest squared distance of a k = 5 search that includes the
+ * point), max_splat_size); a splat is added if the centre or one of its corners is farther than distance_threshold from the
+ * mesh.  Points with a non-finite coordinate are neither searched nor splatted; fewer than 5 finite points is an error.
+ * splat_vertices: the first min(m, capacity) splats, 12 floats each (corners TR, BR, BL, TL) in ascending point order; the
+ * faces of splat s are (4s+2, 4s+1, 4s) and (4s, 4s+3, 4s+2).  splat_vertices == NULL with capacity 0 only counts.
+ * add_splat / splat_radius (optional, n each): per point 0/1 and the radius (NaN for skipped points).  timings_ms (optional,
+ * 2 floats): index build and splat pass in ms (HIP events).  Host or device pointers. */
+int64_t e3d_create_splats(const float* xyz, const float* normals, size_t n, const float* vertices, size_t n_vertices,
+                          const uint32_t* triangles, size_t n_triangles, float distance_threshold, float max_splat_size,
+                          float* splat_vertices, size_t capacity, uint8_t* add_splat, float* splat_radius, float* timings_ms);
+
 /* ---- (B) ImageRegistrator: dense photometric residual / Jacobian kernels -------------------------------------
  * Device-resident mirror of the parts of opt::Problem the hot loops read (src/opt/problem.h:300-388) and the inner
  * operator surfaces of the optimizer:
