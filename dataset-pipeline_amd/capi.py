@@ -145,6 +145,8 @@ SIGNATURES = {
                                             C.c_void_p, C.c_void_p]),
     "e3d_create_splats": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_float,
                                       C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_render_cube_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_cube_map_timings": (C.c_int, [C.c_void_p]),
 }
 
 
@@ -194,7 +196,7 @@ def _ptr(a, dtype, keep):
         return None
     if _is_torch(a):
         import torch
-        want = {np.float32: torch.float32, np.int32: torch.int32, np.float64: torch.float64}[dtype]
+        want = {np.float32: torch.float32, np.int32: torch.int32, np.float64: torch.float64, np.uint8: torch.uint8}[dtype]
         t = a.contiguous()
         if t.dtype != want:
             t = t.to(want)
@@ -511,6 +513,30 @@ def create_splats(xyz, normals, vertices, triangles, distance_threshold=0.02, ma
     s = np.arange(m, dtype=np.int32)[:, None] * 4
     faces = np.concatenate([np.concatenate([s + 2, s + 1, s], 1), np.concatenate([s, s + 3, s + 2], 1)], 1).reshape(-1, 3)
     return out[:m].reshape(-1, 3).copy(), faces, flag.astype(bool), rad
+
+
+CUBE_MAP_FACES = ("front", "left", "back", "right", "down", "up")
+
+
+def render_cube_map(xyz, rgb, size, fill=True, timings=None):
+    """CubeMapRenderer -> (color[6, size, size, 3] uint8 (R, G, B), depth[6, size, size] float32 (+inf: none), sweeps[6]).
+    Faces in the order of CUBE_MAP_FACES.  fill=False: the raw z-buffer.  timings: a dict that receives the phase times (ms)."""
+    keep = []
+    n = int(xyz.shape[0])
+    size = int(size)
+    color = np.zeros((6, max(size, 0), max(size, 0), 3), np.uint8)
+    depth = np.zeros((6, max(size, 0), max(size, 0)), np.float32)
+    sweeps = np.zeros(6, np.int32)
+    r = lib().e3d_render_cube_map(_ptr(xyz, np.float32, keep) if n else None, _ptr(rgb, np.uint8, keep) if n else None, n, size,
+                                  1 if fill else 0, C.c_void_p(color.ctypes.data), C.c_void_p(depth.ctypes.data), C.c_void_p(sweeps.ctypes.data))
+    if r < 0:
+        _err("e3d_render_cube_map", r)
+    if timings is not None:
+        tm = np.zeros(8, np.float32)
+        lib().e3d_cube_map_timings(C.c_void_p(tm.ctypes.data))
+        timings.update(points_ms=float(tm[0]), resolve_ms=float(tm[1]), fill_ms=float(tm[2]), dilation_ms=float(tm[3]),
+                       batches=int(tm[4]), sweeps_launched=int(tm[5]))
+    return color, depth, sweeps
 
 
 # ---- (B) image registration kernels ------------------------------------------------------------------------------------

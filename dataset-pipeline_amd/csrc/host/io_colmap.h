@@ -69,6 +69,94 @@ inline bool ReadColmapImages(const std::string& path, std::map<int, ColmapImage>
   return true;
 }
 
+// ---- images.txt with its feature observations, for SfMScaleEstimator ---------------------------------------------------------
+// ReadColmapImages(read_observations = true) :102-153 with scale_factor = 1 and WriteColmapImages :155-190.  The pose words are
+// parsed twice, as the reference's two readers do: as float (the model that is scaled and written back) and as double rounded
+// to float (src/exe/sfm_scale_estimator.cc:164-187, the cube map faces).  An observation is a complete (x, y, id) triple: the
+// reference's eof-driven loop appends one more element of unspecified content after trailing blanks or on an empty line, which
+// is not restated.
+struct ColmapFeatureObservation { float x = 0, y = 0; int point3d_id = -1; };
+struct ColmapImageWithObservations : ColmapImage {
+  float q_from_double[4] = {1, 0, 0, 0};
+  float t_from_double[3] = {0, 0, 0};
+  std::vector<ColmapFeatureObservation> observations;
+};
+
+// images in file order (no scale side effect)
+inline bool ReadColmapImagesWithObservations(const std::string& path, std::vector<ColmapImageWithObservations>* images) {
+  std::ifstream f(path);
+  if (!f) return false;
+  std::string line;
+  while (std::getline(f, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    ColmapImageWithObservations im;
+    {
+      std::istringstream s(line);
+      s >> im.image_id >> im.q[0] >> im.q[1] >> im.q[2] >> im.q[3] >> im.t[0] >> im.t[1] >> im.t[2] >> im.camera_id >> im.file_path;
+    }
+    {
+      std::istringstream s(line);
+      int id;
+      double v[7] = {1, 0, 0, 0, 0, 0, 0};
+      s >> id;
+      for (int i = 0; i < 7; ++i) s >> v[i];
+      for (int i = 0; i < 4; ++i) im.q_from_double[i] = (float)v[i];
+      for (int i = 0; i < 3; ++i) im.t_from_double[i] = (float)v[4 + i];
+    }
+    if (std::getline(f, line)) {
+      std::istringstream s(line);
+      ColmapFeatureObservation o;
+      while (s >> o.x >> o.y >> o.point3d_id) im.observations.push_back(o);
+    }
+    images->push_back(im);
+  }
+  return true;
+}
+
+// ascending image id, a repeated id keeps its first entry (the reference's std::map); floats at the stream's six digits
+inline bool WriteColmapImages(const std::string& path, const std::vector<ColmapImageWithObservations>& images) {
+  std::map<int, const ColmapImageWithObservations*> by_id;
+  for (const ColmapImageWithObservations& im : images) by_id.insert(std::make_pair(im.image_id, &im));
+  std::ofstream f(path);
+  if (!f) return false;
+  f << "# Image list with two lines of data per image:" << std::endl;
+  f << "#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME" << std::endl;
+  f << "#   POINTS2D[] as (X, Y, POINT3D_ID)" << std::endl;
+  f << "# Number of images: " << by_id.size() << std::endl;
+  for (const auto& it : by_id) {
+    const ColmapImageWithObservations& im = *it.second;
+    f << im.image_id << " " << im.q[0] << " " << im.q[1] << " " << im.q[2] << " " << im.q[3] << " " << im.t[0] << " " << im.t[1] << " "
+      << im.t[2] << " " << im.camera_id << " " << im.file_path << std::endl;
+    for (const ColmapFeatureObservation& o : im.observations) f << " " << o.x << " " << o.y << " " << o.point3d_id;
+    f << std::endl;
+  }
+  f.close();
+  return (bool)f;
+}
+
+// points3D.txt with the positions multiplied by `factor` and the remaining words of each line unchanged
+// (src/exe/sfm_scale_estimator.cc:336-384)
+inline bool ScaleColmapPoints3D(const std::string& in_path, const std::string& out_path, float factor) {
+  std::ifstream in(in_path);
+  if (!in) { std::cout << "Cannot read file " << in_path << std::endl; return false; }
+  std::ofstream out(out_path);
+  if (!out) { std::cout << "Cannot write file " << out_path << std::endl; return false; }
+  std::string line;
+  while (std::getline(in, line)) {
+    if (line.empty() || line[0] == '#') continue;
+    std::istringstream s(line);
+    int id = 0;
+    float p[3] = {0, 0, 0};
+    s >> id >> p[0] >> p[1] >> p[2];
+    out << id << " " << (factor * p[0]) << " " << (factor * p[1]) << " " << (factor * p[2]);
+    std::string word;
+    while (s >> word) out << " " << word;
+    out << std::endl;
+  }
+  out.close();
+  return (bool)out;
+}
+
 // ---- rigs.json: [ { "ref_camera_id": int, "cameras": [ { "camera_id": int, "image_prefix": string }, ... ] }, ... ] --------
 namespace json_detail {
 struct Cursor {

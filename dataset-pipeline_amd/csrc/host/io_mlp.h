@@ -5,6 +5,8 @@
 // (tinyxml2 is a reference third-party source and is not copied).
 #pragma once
 
+#include <sys/stat.h>
+
 #include <cmath>
 #include <fstream>
 #include <iostream>
@@ -128,6 +130,35 @@ inline std::string parent_path(const std::string& p) {
 inline std::string join_path(const std::string& dir, const std::string& file) {
   if (dir.empty()) return file;
   return (dir.back() == '/') ? dir + file : dir + "/" + file;
+}
+
+inline void create_directories(const std::string& p) {
+  std::string cur;
+  std::istringstream s(p);
+  std::string part;
+  if (!p.empty() && p[0] == '/') cur = "/";
+  while (std::getline(s, part, '/')) {
+    if (part.empty()) continue;
+    cur += part + "/";
+    mkdir(cur.c_str(), 0777);
+  }
+}
+// util::RelativePath (src/base/util.cc:36-66)
+inline std::string relative_path(const std::string& from, const std::string& to) {
+  auto split = [](const std::string& p) {
+    std::vector<std::string> v;
+    if (!p.empty() && p[0] == '/') v.push_back("/");
+    std::istringstream s(p); std::string part;
+    while (std::getline(s, part, '/')) if (!part.empty()) v.push_back(part);
+    return v;
+  };
+  const std::vector<std::string> a = split(from), b = split(to);
+  size_t i = 0;
+  while (i < a.size() && i < b.size() && a[i] == b[i]) ++i;
+  std::string r;
+  for (size_t k = i; k < a.size(); ++k) r += (r.empty() ? "" : "/") + std::string("..");
+  for (size_t k = i; k < b.size(); ++k) r += (r.empty() ? "" : "/") + b[k];
+  return r;
 }
 
 }  // namespace e3d_host

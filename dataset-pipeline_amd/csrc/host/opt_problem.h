@@ -195,34 +195,7 @@ inline std::string replace_extension(const std::string& p, const std::string& ex
   return stem + "." + ext;
 }
 inline bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0; }
-inline void create_directories(const std::string& p) {
-  std::string cur;
-  std::istringstream s(p);
-  std::string part;
-  if (!p.empty() && p[0] == '/') cur = "/";
-  while (std::getline(s, part, '/')) {
-    if (part.empty()) continue;
-    cur += part + "/";
-    mkdir(cur.c_str(), 0777);
-  }
-}
-// util::RelativePath (src/base/util.cc:36-66)
-inline std::string relative_path(const std::string& from, const std::string& to) {
-  auto split = [](const std::string& p) {
-    std::vector<std::string> v;
-    if (!p.empty() && p[0] == '/') v.push_back("/");
-    std::istringstream s(p); std::string part;
-    while (std::getline(s, part, '/')) if (!part.empty()) v.push_back(part);
-    return v;
-  };
-  const std::vector<std::string> a = split(from), b = split(to);
-  size_t i = 0;
-  while (i < a.size() && i < b.size() && a[i] == b[i]) ++i;
-  std::string r;
-  for (size_t k = i; k < a.size(); ++k) r += (r.empty() ? "" : "/") + std::string("..");
-  for (size_t k = i; k < b.size(); ++k) r += (r.empty() ? "" : "/") + b[k];
-  return r;
-}
+// create_directories and relative_path: io_mlp.h
 
 // ---- problem state --------------------------------------------------------------------------------------------------------------
 struct HostIntrinsics {

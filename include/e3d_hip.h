@@ -282,6 +282,24 @@ int64_t e3d_create_splats(const float* xyz, const float* normals, size_t n, cons
                           const uint32_t* triangles, size_t n_triangles, float distance_threshold, float max_splat_size,
                           float* splat_vertices, size_t capacity, uint8_t* add_splat, float* splat_radius, float* timings_ms);
 
+/* ---- CubeMapRenderer (src/exe/cube_map_renderer.cc:161-373) ----------------------------------------------------
+ * Six pinhole faces (front, left, back, right, down, up; fx = fy = cx = cy = size / 2) of a coloured scan given in the
+ * scanner's frame.  Point pass (:238-258): per pixel the lowest depth, among equal depths the lowest point index; a point
+ * with a non-finite coordinate lands in no face.  fill != 0 adds the fill-in of :260-319 (interior pixels: depth from the
+ * median of the first 3 / 5 / 7 valid neighbours, colour from the mean of all of them; border pixels get depth +inf) and
+ * the colour dilation of :321-373 (3 x 3 means of the valid pixels, repeated until every pixel has a colour).  fill == 0
+ * returns the raw z-buffer.  Results equal a serial execution bit for bit.  Where the reference is undefined: border pixels
+ * of a face that needs no dilation are black, and a face without any valid pixel stays black.
+ * xyz n x 3 floats, rgb n x 3 bytes (R, G, B); host or device pointers.  color_out 6 * size * size * 3 bytes (R, G, B),
+ * depth_out 6 * size * size floats (+inf = no depth), sweeps_out (optional) six ints: dilation sweeps per face that gave at
+ * least one pixel its colour (= the reference's loop iterations).  size >= 3, n < 2^31. */
+int e3d_render_cube_map(const float* xyz, const uint8_t* rgb, size_t n, int size, int fill, uint8_t* color_out,
+                        float* depth_out, int32_t* sweeps_out);
+/* Times of this thread's last e3d_render_cube_map (HIP events, ms): [0] point pass, [1] resolve, [2] fill-in pass 1,
+ * [3] dilation including its read-backs, [4] batches of sweeps looked at, [5] sweeps launched, [6..7] reserved. */
+#define E3D_CUBE_MAP_TIMINGS 8
+int e3d_cube_map_timings(float* out);
+
 /* ---- (B) ImageRegistrator: dense photometric residual / Jacobian kernels -------------------------------------
  * Device-resident mirror of the parts of opt::Problem the hot loops read (src/opt/problem.h:300-388) and the inner
  * operator surfaces of the optimizer:
