@@ -36,6 +36,14 @@ static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 const char* last_error_cstr() { return g_last_error.c_str(); }
 
+// environment switches of this file: a number; on unless the value starts with '0'; off unless it starts with '1'
+static double env_double(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
+static bool env_default_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
+static bool env_default_off(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+
 static int g_device = 0;
 // E3D_NN_MODE / e3d_set_nn_mode: 0 auto, 1 per-query, 2 hash-table buckets, 3 dense rows, 4 dense rows + MFMA filter,
 // 5 dense rows with the half-cell directory of the bounded search built whatever the density and used for every list (tests)
@@ -185,7 +193,7 @@ struct e3d_icp {
   int max_inner = 150;
   // the progress line's "avg. distance" from the reference's own sum: f32, sequential, in original source order (one device ->
   // host copy of n floats and a host loop per pair; off: f64 sum on the device, which does not stagnate for large clouds)
-  bool sequential_dsum = [] { const char* e = getenv("E3D_ICP_SEQUENTIAL_DISTANCE_SUM"); return e && e[0] == '1'; }();
+  bool sequential_dsum = env_default_off("E3D_ICP_SEQUENTIAL_DISTANCE_SUM");
   DevBuf<float> d2_by_orig;
   std::vector<float> h_d2_by_orig;
   int nn_mode = 0;                              // 0 auto, 1 per-query kernel, 2 hash-table bucket kernel, 3 dense-directory row kernel, 4 row kernel with MFMA filter
@@ -217,7 +225,7 @@ struct e3d_icp {
   size_t corr_used = 0;
   // e3d_icp_set_resident_rows / E3D_ICP_RESIDENT=0: compacted planes rewritten every outer iteration for every pair (the round-3
   // data flow; A/B timing, tests)
-  bool resident_rows = [] { const char* e = getenv("E3D_ICP_RESIDENT"); return !(e && e[0] == '0'); }();
+  bool resident_rows = env_default_on("E3D_ICP_RESIDENT");
   bool resident_now = false;                    // this outer iteration keeps resident rows for the pairs of the certificate path
   int lm_prev_end_step = -1;                    // LM step at which the previous outer iteration's LM ended with ten rejections (-1: none yet)
   std::unique_ptr<SolvePool> solve_pool;        // host threads of the LM step's damped solves (systems of >= 30 unknowns)
@@ -436,7 +444,7 @@ static void build_grid(e3d_icp* h, Cloud& c, float d) {
   // occupancy bits of the 27-cell blocks (E3D_NN_PRUNE=0: none): cells / 8 bytes, the unpadded bits of the build in the sort's key
   // buffer when it is large enough
   c.has_occ = false;
-  static const bool want_occ = [] { const char* e = getenv("E3D_NN_PRUNE"); return !(e && e[0] == '0'); }();
+  static const bool want_occ = env_default_on("E3D_NN_PRUNE");
   if (c.has_dense && want_occ && n > 0) {
     const unsigned stride_w = (c.qrange.D[0] + 31u) / 32u;
     const size_t words = (size_t)c.qrange.D[2] * c.qrange.D[1] * stride_w;
@@ -514,10 +522,6 @@ static inline float radius_sq(float d) {
   return (float)(r * r);
 }
 
-static double env_double(const char* name, double dflt) {
-  const char* e = getenv(name);
-  return e ? atof(e) : dflt;
-}
 static float round_up_f(double v) {
   float f = (float)v;
   if ((double)f < v) f = std::nextafter(f, FLT_MAX);
@@ -584,7 +588,7 @@ static double pose_rounding_bound(const Cloud& c, const float* T) {
 }
 
 // E3D_NN_PERQUERY=0: the certificates use the clouds' global motion bounds (rounds 2 - 4) instead of the bound per query
-static bool per_query_motion() { static const bool on = [] { const char* e = getenv("E3D_NN_PERQUERY"); return !(e && e[0] == '0'); }(); return on; }
+static bool per_query_motion() { static const bool on = env_default_on("E3D_NN_PERQUERY"); return on; }
 // largest entry of |L^T L - I|: the singular values of the pose's linear part lie within sqrt(1 -+ 3 dev).  Poses are re-composed in
 // f32 every outer iteration (Tn = R * T) and never re-orthonormalised, so dev grows by ~1e-7 per iteration: the bound per query is
 // scaled by what dev allows (accumulate_pair_motion) instead of being switched off at a fixed tolerance (at 4e-6 a
@@ -720,6 +724,25 @@ static void sort_query_keys(e3d_icp* h, const Cloud& tgt, const float4* srcG, co
   }
 }
 
+// The certificate search's switches, read once for the three drivers (find_pair, find_pairs_batched, find_pairs_multi)
+struct NnSwitches {
+  bool use_cert = env_default_on("E3D_NN_CERT");       // 0: every query is searched in every outer iteration
+  bool want_stats = env_default_off("E3D_NN_STATS");
+  // fractions of the search radius: the bounded search's margin, the near list's reach, what a query without a partner is searched
+  // beyond the radius and the clouds' motion below which it is (prepare_pair)
+  double margin_frac = env_double("E3D_NN_MARGIN", 0.08), near_frac = env_double("E3D_NN_NEAR", 0.4);
+  double np_frac = env_double("E3D_NN_NP_EXTRA", 0.5), np_gate = env_double("E3D_NN_NP_GATE", 0.2);
+  size_t prune_min_list = (size_t)env_double("E3D_NN_PRUNE_MIN", 262144.0);   // shorter far lists are not pruned (sort_query_keys_pruned)
+  // find_pairs_multi alone (what they do: there)
+  bool fuse_update = env_default_on("E3D_NN_FUSE_UPDATE");
+  double fuse_gate = env_double("E3D_NN_FUSE_GATE", 0.003);
+  bool far_batch = env_default_on("E3D_NN_FAR_BATCH");
+  bool seed_allowed = env_default_on("E3D_NN_SEED");
+  double seed_frac = env_double("E3D_NN_SEED_FRAC", 0.3), seed_near = env_double("E3D_NN_SEED_NEAR", 0.4);
+  bool seed_fresh = env_double("E3D_NN_SEED_FRESH", 0.0) != 0.0;
+};
+static const NnSwitches& nn_switches() { static const NnSwitches sw; return sw; }
+
 // Is k_nn_certify worth a pass over this pair's queries?  While two scans are centimetres apart every certificate breaks with every
 // pose update (0.7 ms per outer iteration at 2 x 50 M points for nothing).  After a pass that settled less than 2 % of the queries
 // the pair is searched whole -- the state of the last search still tells which queries had no partner (from_state) -- until half
@@ -727,7 +750,7 @@ static void sort_query_keys(e3d_icp* h, const Cloud& tgt, const float4* srcG, co
 // at that pass.  A wrong guess costs searches, never a
 // result.  E3D_NN_CERT_SKIP=0: always test.
 static bool certify_now(const PairState& ps, const Cloud& src, const Cloud& tgt) {
-  static const bool allow = [] { const char* e = getenv("E3D_NN_CERT_SKIP"); return !(e && e[0] == '0'); }();
+  static const bool allow = env_default_on("E3D_NN_CERT_SKIP");
   return !allow || ps.settled_frac >= 0.02 || ps.matched_frac >= 0.5 || (src.last_motion + tgt.last_motion) < 0.5 * ps.certify_motion;
 }
 static void certify_ran(PairState& ps, const Cloud& src, const Cloud& tgt, size_t n, size_t unsettled) {
@@ -742,8 +765,7 @@ static void certify_ran(PairState& ps, const Cloud& src, const Cloud& tgt, size_
 // goes back to the plain key kernel (ps.prune; a fresh state starts over).  E3D_NN_PRUNE=0: never.
 static size_t sort_query_keys_pruned(e3d_icp* h, PairState& ps, const Cloud& tgt, const float4* srcG, const unsigned* list, size_t n, const InvMap& im,
                                      float r2, const CertParams& cert, float* match_d2, bool from_state) {
-  static const size_t min_list = (size_t)env_double("E3D_NN_PRUNE_MIN", 262144.0);
-  if (!tgt.has_occ || !ps.prune || n < min_list) { sort_query_keys(h, tgt, srcG, list, n, im); return n; }
+  if (!tgt.has_occ || !ps.prune || n < nn_switches().prune_min_list) { sort_query_keys(h, tgt, srcG, list, n, im); return n; }
   hipStream_t s = h->stream;
   h->keys_a.reserve(n); h->keys_b.reserve(n); h->vals_a.reserve(n); h->vals_b.reserve(n);
   h->prune_count.reserve(1); h->h_prune_count.reserve(1);
@@ -767,7 +789,7 @@ static size_t sort_query_keys_pruned(e3d_icp* h, PairState& ps, const Cloud& tgt
 // Multi-GPU: every rank holds all clouds and handles the slice [j0, j1) of the source cloud (cell order).
 // E3D_NN_PROFILE=1: wall-clock split of the search of one outer iteration (synchronises between the phases; diagnostics only)
 static double g_nn_prof[8];
-static bool nn_profile() { static const bool on = [] { const char* e = getenv("E3D_NN_PROFILE"); return e && e[0] == '1'; }(); return on; }
+static bool nn_profile() { static const bool on = env_default_off("E3D_NN_PROFILE"); return on; }
 struct NnPhase {
   hipStream_t s; int slot; std::chrono::steady_clock::time_point t0;
   NnPhase(hipStream_t st, int sl) : s(st), slot(sl) { if (nn_profile()) { (void)hipStreamSynchronize(s); t0 = std::chrono::steady_clock::now(); } }
@@ -791,6 +813,123 @@ static bool far_list_is_short(size_t n_far, size_t n) {
 static size_t resident_rows_cap(size_t n) { return div_up(n, 64) * 64; }
 static size_t resident_bytes(size_t n) { return resident_rows_cap(n) * 48 + n * 4 + div_up(n, 64) * 4; }
 
+// ---- what the three drivers of the certificate search share -----------------------------------------------------------------------
+// One directed pair of the certificate search: who (filled by the caller), what its kernels are asked to do at this outer iteration
+// (prepare_pair), and the lengths of its two todo lists once k_nn_certify has run
+struct BatchItem {
+  PairJob* job; Cloud* src; Cloud* tgt; size_t j0, n; PairState* ps;
+  InvMap im; CertParams cert; BoundParams bp; double cum_pair;
+  MotionBound cum_up;                  // the pair's accumulated motion, rounded up (k_nn_certify)
+  float near2; bool none_near;
+  bool certified = false, from_state = false; size_t n_near = 0, n_far = 0;
+};
+
+static void prepare_pair(BatchItem& it, float d) {
+  const NnSwitches& sw = nn_switches();
+  const Cloud& src = *it.src; const Cloud& tgt = *it.tgt;
+  const PairState& ps = *it.ps;
+  it.im = make_invmap(tgt);
+  it.cum_pair = src.cum_motion + tgt.cum_motion;
+  MotionBound m_lo;
+  pair_motion_bounds(ps, src, tgt, m_lo, it.cum_up);
+  it.cert = make_cert_params(tgt, m_lo);
+  it.n_far = it.n; it.n_near = 0;
+  it.certified = !ps.fresh && sw.use_cert && certify_now(ps, src, tgt);
+  it.from_state = !ps.fresh && sw.use_cert && !it.certified;       // searched whole; the state says who had no partner
+  it.near2 = (float)((sw.near_frac * (double)d) * (sw.near_frac * (double)d));
+  // Queries without a partner whose "nothing within the radius" bound no longer holds: k_nn_bounded searches them np_extra
+  // beyond the radius (cheap where the target is absent, and the bound then survives the following pose updates) -- but only
+  // once the poses move little: while the scans are still centimetres apart such a query has the other surface just outside
+  // the radius, one thread would scan 64 full cells, and the bound would not survive the next update anyway.
+  it.none_near = sw.np_frac > 0 && (src.last_motion + tgt.last_motion) < sw.np_gate * (double)d;
+  // the bounded search (old partner close by: only the cells its distance + margin reaches, one thread per query, no sort).  Filled
+  // for every pair, certified or not: host arithmetic on values that exist either way, read only where a bounded search is launched
+  double smin = cloud_smin(tgt);
+  if (!(smin > 1e-12)) smin = 1e-12;
+  double m_local = 0;
+  for (int k = 0; k < 3; ++k) m_local = std::max(m_local, std::max(std::fabs((double)tgt.lmin[k]), std::fabs((double)tgt.lmax[k])));
+  it.bp.margin = (float)(sw.margin_frac * (double)d);
+  it.bp.rho_scale = round_up_f((1.0 + 1e-5) / smin);
+  it.bp.rho_pad = round_up_f(2.0 * tgt.build_slack + 8.0 * FLT_EPSILON * m_local);
+  it.bp.lo = it.cert.lo;
+  it.bp.cell_scale = it.cert.cell_scale; it.bp.cell_sub = it.cert.cell_sub;
+  it.bp.np_extra = it.none_near ? (float)(sw.np_frac * (double)d) : 0.f;   // gate closed: partnerless queries on the far list keep the plain radius
+}
+
+// The bounded search of a certified pair's near list, and of its far list when that is short (few queries without a near partner:
+// the same kernel, whole radius for those without any, instead of sort + row kernel, whose cost is per visited cell row, not per
+// query).  tm_bounded is read lazily: timing it costs no synchronisation.
+static void search_bounded_lists(e3d_icp* h, BatchItem& it, const unsigned* todo_near, const unsigned* todo_far, float* match_d2, float d, e3d_icp_iter_record& rec) {
+  hipStream_t s = h->stream;
+  const Cloud& tgt = *it.tgt;
+  PairState& ps = *it.ps;
+  const float4* srcG = it.src->G4.p + it.j0;
+  const unsigned long long* half = tgt.has_half ? tgt.half_prefix.p : nullptr;
+  h->tm_bounded.start(s);
+  launch_nn_bounded(srcG, todo_near, it.n_near, tgt.G4.p, tgt.dense_start.p, half, h->nn_mode == 5, tgt.grid, it.im, tgt.qrange, radius_sq(d), it.bp,
+                    ps.match.p, ps.match2.p, match_d2, ps.lbe.p, s);
+  if (far_list_is_short(it.n_far, it.n)) {
+    launch_nn_bounded(srcG, todo_far, it.n_far, tgt.G4.p, tgt.dense_start.p, half, h->nn_mode == 5, tgt.grid, it.im, tgt.qrange, radius_sq(d), it.bp,
+                      ps.match.p, ps.match2.p, match_d2, ps.lbe.p, s);
+    it.n_near += it.n_far; it.n_far = 0;
+  }
+  h->tm_bounded.stop(s);
+  if (it.n_near > 0) { rec.nn_bounded_launches++; rec.nn_bounded_queries += (long long)it.n_near; rec.nn_kernel_launches++; }
+}
+
+// A pair's far list searched on its own: keys (+ prune) and sort, then k_nn_rows over the queries with a candidate in their 27 cells.
+// nn_timer: find_pair's stop-watch of its search kernels, started here behind the sort and stopped by find_pair (around no launch,
+// too); the batch drivers pass none and the row kernel goes into tm_search.
+static void search_far_list(e3d_icp* h, BatchItem& it, const unsigned* list, float* match_d2, float d, EventTimer* nn_timer, e3d_icp_iter_record& rec) {
+  hipStream_t s = h->stream;
+  PairState& ps = *it.ps;
+  const float4* srcG = it.src->G4.p + it.j0;
+  size_t n_rows = 0;
+  if (it.n_far > 0) {
+    NnPhase ph(s, 1);
+    n_rows = sort_query_keys_pruned(h, ps, *it.tgt, srcG, list, it.n_far, it.im, radius_sq(d), it.cert, match_d2, it.from_state);
+    rec.nn_sort_calls++; rec.nn_kernel_launches++;
+  }
+  if (nn_timer) nn_timer->start(s);
+  if (n_rows == 0) return;
+  if (!nn_timer) h->tm_search.start(s);
+  launch_rows(3, *it.tgt, srcG, h->vals_b.p, n_rows, it.im, radius_sq(d), it.cert, ps.match.p, match_d2, ps.lbe.p, ps.match2.p, s);
+  if (!nn_timer) h->tm_search.stop(s);
+  rec.nn_search_launches++; rec.nn_search_queries += (long long)n_rows; rec.nn_kernel_launches++;
+}
+
+static void print_pair_stats(const BatchItem& it) {
+  if (!nn_switches().want_stats) return;
+  fprintf(stderr, "[nn %d->%d] queries %zu bounded %zu rows %zu cum %.3g (last %.3g) err %.3g\n", it.job->src, it.job->tgt, it.n, it.n_near, it.n_far,
+          it.cum_pair, it.src->last_motion + it.tgt->last_motion, it.src->err_max + it.tgt->err_max);
+}
+
+// Resident rows: are the pair's planes those plane_match describes, in the frames this outer iteration wants?  A cloud that never
+// moves inside this AlignMeshes call (impl cloud 0, the fixed cloud) keeps its half in the global frame: no outer transform inside
+// the LM passes for it.  If such a cloud did move since the rows were written (another role in an earlier call), or a half changes
+// frames, every row is rewritten once: plane_match is reset to "never written" (enqueued on s).
+struct RowFrames { bool sg, tg; bool reset; };      // source / target half in the global frame; the rows were reset
+static RowFrames ensure_resident_rows(PairState& ps, const Cloud& src, const Cloud& tgt, size_t n, hipStream_t s) {
+  const size_t cap = resident_rows_cap(n);
+  const bool sg = src.fixed || src.cloud_index == 0, tg = tgt.fixed || tgt.cloud_index == 0;
+  bool valid = ps.rows_valid && ps.pA.cap >= cap && ps.src_global == sg && ps.tgt_global == tg;
+  if (valid && sg && std::memcmp(ps.src_T, src.T, sizeof ps.src_T) != 0) valid = false;
+  if (valid && tg && std::memcmp(ps.tgt_T, tgt.T, sizeof ps.tgt_T) != 0) valid = false;
+  if (!valid) {
+    ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap); ps.plane_match.reserve(n); ps.glist.reserve(div_up(n, 64));
+    E3D_HIP(hipMemsetAsync(ps.plane_match.p, 0xFE, sizeof(int) * n, s));
+    if (cap > n) {                                                                 // the rows past the last query stay zero rows
+      E3D_HIP(hipMemsetAsync(ps.pA.p + n, 0, sizeof(float4) * (cap - n), s));
+      E3D_HIP(hipMemsetAsync(ps.pB.p + n, 0, sizeof(float4) * (cap - n), s));
+      E3D_HIP(hipMemsetAsync(ps.pC.p + n, 0, sizeof(float4) * (cap - n), s));
+    }
+    ps.src_global = sg; ps.tgt_global = tg;
+    std::memcpy(ps.src_T, src.T, sizeof ps.src_T); std::memcpy(ps.tgt_T, tgt.T, sizeof ps.tgt_T);
+    ps.rows_valid = true;
+  }
+  return {sg, tg, !valid};
+}
+
 static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job, size_t j0, size_t j1,
                       e3d_icp_iter_record& rec) {
   hipStream_t s = h->stream;
@@ -811,8 +950,6 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
   const bool dense = pair_is_dense(h, tgt);
   const bool rows = pair_uses_rows(h, tgt);
   PairState* rstate = nullptr;
-  static const bool use_cert = [] { const char* e = getenv("E3D_NN_CERT"); return !(e && e[0] == '0'); }();
-  static const bool want_stats = [] { const char* e = getenv("E3D_NN_STATS"); return e && e[0] == '1'; }();
   const unsigned* order = nullptr;
   int* match_pos = nullptr;
   // the timer brackets the search kernels themselves (what rocprofv3 reports for them); keys + sort are part of t_nn_ms
@@ -820,80 +957,30 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
     PairState& ps = pair_state_for(h, job.src, job.tgt, src, tgt, j0, n);
     if (h->resident_now) rstate = &ps;
     match_pos = ps.match.p;
-    const InvMap im = make_invmap(tgt);
-    const double cum_pair = src.cum_motion + tgt.cum_motion;
-    MotionBound m_lo, m_up;
-    pair_motion_bounds(ps, src, tgt, m_lo, m_up);
-    const CertParams cert = make_cert_params(tgt, m_lo);
-    size_t n_far = n, n_near = 0;
-    const unsigned* list = nullptr;
-    const bool test_certificates = !ps.fresh && use_cert && certify_now(ps, src, tgt);
-    const bool from_state = !ps.fresh && use_cert && !test_certificates;       // searched whole; the state says who had no partner
-    if (test_certificates) {
+    BatchItem it{};
+    it.job = &job; it.src = &src; it.tgt = &tgt; it.j0 = j0; it.n = n; it.ps = &ps;
+    prepare_pair(it, d);
+    if (it.certified) {
       NnPhase ph(s, 0);
-      static const double margin_frac = env_double("E3D_NN_MARGIN", 0.08), near_frac = env_double("E3D_NN_NEAR", 0.4);   // of the radius
-      const MotionBound& cum_up = m_up;
-      const float near2 = (float)((near_frac * (double)d) * (near_frac * (double)d));
       h->h_todo.reserve(2);
       h->todo_near.reserve(n); h->todo_far.reserve(n);
       E3D_HIP(hipMemsetAsync(ps.todo_count.p, 0, 2 * sizeof(unsigned), s));
       if (!h->nn_timer_c) h->nn_timer_c.reset(new EventTimer());
       h->nn_timer_c->start(s);
-      // Queries without a partner whose "nothing within the radius" bound no longer holds: k_nn_bounded searches them np_extra
-      // beyond the radius (cheap where the target is absent, and the bound then survives the following pose updates) -- but only
-      // once the poses move little: while the scans are still centimetres apart such a query has the other surface just outside
-      // the radius, one thread would scan 64 full cells, and the bound would not survive the next update anyway.
-      static const double np_frac = env_double("E3D_NN_NP_EXTRA", 0.5), np_gate = env_double("E3D_NN_NP_GATE", 0.2);   // of the radius
-      const bool none_near = np_frac > 0 && (src.last_motion + tgt.last_motion) < np_gate * (double)d;
-      launch_nn_certify(srcG, n, tgt.G4.p, cum_up, radius_sq(d), near2, none_near, ps.match.p, ps.match2.p, ps.lbe.p, h->match_d2.p, h->todo_near.p,
+      launch_nn_certify(srcG, n, tgt.G4.p, it.cum_up, radius_sq(d), it.near2, it.none_near, ps.match.p, ps.match2.p, ps.lbe.p, h->match_d2.p, h->todo_near.p,
                         h->todo_far.p, ps.todo_count.p, s);
       h->nn_timer_c->stop(s);
       copy_out(h->h_todo.p, ps.todo_count.p, 2 * sizeof(unsigned), s);
       sync(h);
       { const double t = h->nn_timer_c->ms(); rec.t_nn_certify_ms += t; rec.t_nn_query_ms += t; }
       rec.nn_certify_launches++; rec.nn_certify_queries += (long long)n; rec.nn_kernel_launches++;
-      n_near = h->h_todo.p[0]; n_far = h->h_todo.p[1];
-      certify_ran(ps, src, tgt, n, n_near + n_far);
-      h->tm_bounded.start(s);                             // (read lazily: timing the bounded search costs no synchronisation)
-      list = h->todo_far.p;
-      // old partner close by: only the cells its distance (+ margin) reaches, one thread per query, no sort
-      double smin = cloud_smin(tgt);
-      if (!(smin > 1e-12)) smin = 1e-12;
-      double m_local = 0;
-      for (int k = 0; k < 3; ++k) m_local = std::max(m_local, std::max(std::fabs((double)tgt.lmin[k]), std::fabs((double)tgt.lmax[k])));
-      BoundParams bp;
-      bp.margin = (float)(margin_frac * (double)d);
-      bp.rho_scale = round_up_f((1.0 + 1e-5) / smin);
-      bp.rho_pad = round_up_f(2.0 * tgt.build_slack + 8.0 * FLT_EPSILON * m_local);
-      bp.lo = cert.lo;
-      bp.cell_scale = cert.cell_scale; bp.cell_sub = cert.cell_sub;
-      bp.np_extra = none_near ? (float)(np_frac * (double)d) : 0.f;   // gate closed: partnerless queries on the far list keep the plain radius
-      launch_nn_bounded(srcG, h->todo_near.p, n_near, tgt.G4.p, tgt.dense_start.p, tgt.has_half ? tgt.half_prefix.p : nullptr, h->nn_mode == 5, tgt.grid, im, tgt.qrange, radius_sq(d), bp, ps.match.p,
-                        ps.match2.p, h->match_d2.p, ps.lbe.p, s);
-      if (far_list_is_short(n_far, n)) {
-        // few queries without a near partner: the same kernel (whole radius for those without any) instead of sort + row kernel,
-        // whose cost is per visited cell row, not per query
-        launch_nn_bounded(srcG, h->todo_far.p, n_far, tgt.G4.p, tgt.dense_start.p, tgt.has_half ? tgt.half_prefix.p : nullptr, h->nn_mode == 5, tgt.grid, im, tgt.qrange, radius_sq(d), bp, ps.match.p,
-                          ps.match2.p, h->match_d2.p, ps.lbe.p, s);
-        n_near += n_far; n_far = 0;
-      }
-      h->tm_bounded.stop(s);
-      if (n_near > 0) { rec.nn_bounded_launches++; rec.nn_bounded_queries += (long long)n_near; rec.nn_kernel_launches++; }
+      it.n_near = h->h_todo.p[0]; it.n_far = h->h_todo.p[1];
+      certify_ran(ps, src, tgt, n, it.n_near + it.n_far);
+      search_bounded_lists(h, it, h->todo_near.p, h->todo_far.p, h->match_d2.p, d, rec);
     }
-    size_t n_rows = 0;                                     // far-list queries with a candidate in their 27 cells: sorted and searched
-    if (n_far > 0) {
-      NnPhase ph(s, 1);
-      n_rows = sort_query_keys_pruned(h, ps, tgt, srcG, list, n_far, im, radius_sq(d), cert, h->match_d2.p, from_state);
-      rec.nn_sort_calls++; rec.nn_kernel_launches++;
-    }
-    h->nn_timer->start(s);
-    if (n_rows > 0)
-      launch_rows(3, tgt, srcG, h->vals_b.p, n_rows, im, radius_sq(d), cert, ps.match.p, h->match_d2.p, ps.lbe.p, ps.match2.p, s);
+    search_far_list(h, it, it.certified ? h->todo_far.p : nullptr, h->match_d2.p, d, h->nn_timer.get(), rec);
     ps.fresh = false;
-    if (n_rows > 0) { rec.nn_search_launches++; rec.nn_search_queries += (long long)n_rows; rec.nn_kernel_launches++; }
-    if (want_stats)
-      fprintf(stderr, "[nn %d->%d] queries %zu bounded %zu rows %zu cum %.3g (last %.3g) err %.3g\n", job.src, job.tgt, n,
-              n_near, n_far, cum_pair, src.last_motion + tgt.last_motion, src.err_max + tgt.err_max);
+    print_pair_stats(it);
   } else if (dense) {
     h->match_pos.reserve(n);
     match_pos = h->match_pos.p;
@@ -925,26 +1012,8 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
   if (rstate) {
     // resident rows: bring the pair's planes up to date with the match list (rows whose partner changed), count, list the groups
     PairState& ps = *rstate;
-    const size_t cap = resident_rows_cap(n);
-    // a cloud that never moves inside this AlignMeshes call (impl cloud 0, the fixed cloud) keeps its half in the global frame:
-    // no outer transform inside the LM passes for it.  If such a cloud did move since the rows were written (another role in an
-    // earlier call), or a half changes frames, every row is rewritten once.
-    const bool sg = src.fixed || src.cloud_index == 0, tg = tgt.fixed || tgt.cloud_index == 0;
-    bool valid = ps.rows_valid && ps.pA.cap >= cap && ps.src_global == sg && ps.tgt_global == tg;
-    if (valid && sg && std::memcmp(ps.src_T, src.T, sizeof ps.src_T) != 0) valid = false;
-    if (valid && tg && std::memcmp(ps.tgt_T, tgt.T, sizeof ps.tgt_T) != 0) valid = false;
-    if (!valid) {
-      ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap); ps.plane_match.reserve(n); ps.glist.reserve(div_up(n, 64));
-      E3D_HIP(hipMemsetAsync(ps.plane_match.p, 0xFE, sizeof(int) * n, s));          // "never written": every row is
-      if (cap > n) {                                                                 // the rows past the last query stay zero rows
-        E3D_HIP(hipMemsetAsync(ps.pA.p + n, 0, sizeof(float4) * (cap - n), s));
-        E3D_HIP(hipMemsetAsync(ps.pB.p + n, 0, sizeof(float4) * (cap - n), s));
-        E3D_HIP(hipMemsetAsync(ps.pC.p + n, 0, sizeof(float4) * (cap - n), s));
-      }
-      ps.src_global = sg; ps.tgt_global = tg;
-      std::memcpy(ps.src_T, src.T, sizeof ps.src_T); std::memcpy(ps.tgt_T, tgt.T, sizeof ps.tgt_T);
-      ps.rows_valid = true;
-    }
+    const RowFrames rf = ensure_resident_rows(ps, src, tgt, n, s);
+    const bool sg = rf.sg, tg = rf.tg;
     h->block_groups.reserve(nb); h->chunk_groups.reserve(2 * (div_up(nb, 256) + 1));
     h->tm_compact.start(s);
     launch_corr_update(ps.match.p, ps.plane_match.p, h->match_d2.p, n, (sg ? src.G4.p : src.L4.p) + j0, srcLN, sg, to_affine(src.T),
@@ -1012,140 +1081,16 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
 // depend on each other, so a batch runs in phases: (A) k_nn_certify of every pair, ONE read-back of all list lengths; (B) the
 // searches and the row update of every pair, ONE read-back of all totals.  Per-pair scratch (distances, todo lists) comes from
 // the handle's slots; what a pair's kernels share with the next pair's (sort buffers, block counts) is ordered by the stream.
-// Same kernels, same launches, same results as find_pair's certificate branch with resident rows.
-struct BatchItem {
-  PairJob* job; Cloud* src; Cloud* tgt; size_t j0, n; PairState* ps;
-  InvMap im; CertParams cert; BoundParams bp; double cum_pair;
-  bool certified = false, from_state = false; size_t n_near = 0, n_far = 0;
-};
+// Same kernels, same launches, same results as find_pair's certificate branch with resident rows: what each pair's kernels are asked
+// to do comes from the helpers the three drivers share (prepare_pair, search_bounded_lists, search_far_list, ensure_resident_rows).
 static constexpr size_t kPairBatch = 32;
 // queries of a batch: its scratch (squared distances, two todo lists) is 12 B per query, 3 GB at most -- whatever the clouds' size
 static constexpr size_t kBatchQueries = (size_t)256 << 20;
 
-static void find_pairs_batched(e3d_icp* h, std::vector<BatchItem>& items, float d, e3d_icp_iter_record& rec) {
+// the totals of a batch's row updates (d_totals_all: count, active groups, rewritten rows per pair; d_d2_all), ONE read-back
+static void read_back_batch(e3d_icp* h, std::vector<BatchItem>& items, e3d_icp_iter_record& rec) {
   hipStream_t s = h->stream;
   const size_t B = items.size();
-  static const bool use_cert = [] { const char* e = getenv("E3D_NN_CERT"); return !(e && e[0] == '0'); }();
-  static const bool want_stats = [] { const char* e = getenv("E3D_NN_STATS"); return e && e[0] == '1'; }();
-  static const double margin_frac = env_double("E3D_NN_MARGIN", 0.08), near_frac = env_double("E3D_NN_NEAR", 0.4);   // of the radius
-  static const double np_frac = env_double("E3D_NN_NP_EXTRA", 0.5), np_gate = env_double("E3D_NN_NP_GATE", 0.2);   // of the radius
-  while (h->slots.size() < B) h->slots.emplace_back(new e3d_icp::PairSlot());
-  h->h_todo_all.reserve(2 * kPairBatch); h->d_totals_all.reserve(3 * kPairBatch); h->d_d2_all.reserve(kPairBatch);
-  h->h_totals_all.reserve(3 * kPairBatch); h->h_d2_all.reserve(kPairBatch);
-  size_t n_max = 0;
-  for (BatchItem& it : items) n_max = std::max(n_max, it.n);
-  const size_t nb_max = div_up(n_max, kBlock);
-  h->block_counts.reserve(nb_max); h->block_d2.reserve(nb_max); h->block_groups.reserve(nb_max);
-  h->chunk_sum.reserve(div_up(nb_max, 256) + 1); h->chunk_d2.reserve(div_up(nb_max, 256) + 1); h->chunk_groups.reserve(2 * (div_up(nb_max, 256) + 1));
-  // ---- phase A: certificates ----------------------------------------------------------------------------------------------
-  for (size_t i = 0; i < B; ++i) {
-    BatchItem& it = items[i];
-    e3d_icp::PairSlot& sl = *h->slots[i];
-    Cloud& src = *it.src; Cloud& tgt = *it.tgt;
-    PairState& ps = *it.ps;
-    sl.match_d2.reserve(it.n);
-    it.im = make_invmap(tgt);
-    it.cum_pair = src.cum_motion + tgt.cum_motion;
-    MotionBound m_lo, cum_up;
-    pair_motion_bounds(ps, src, tgt, m_lo, cum_up);
-    it.cert = make_cert_params(tgt, m_lo);
-    it.n_far = it.n; it.n_near = 0;
-    it.certified = !ps.fresh && use_cert && certify_now(ps, src, tgt);
-    it.from_state = !ps.fresh && use_cert && !it.certified;
-    if (!it.certified) continue;
-    const float4* srcG = src.G4.p + it.j0;
-    const float near2 = (float)((near_frac * (double)d) * (near_frac * (double)d));
-    sl.todo_near.reserve(it.n); sl.todo_far.reserve(it.n);
-    E3D_HIP(hipMemsetAsync(ps.todo_count.p, 0, 2 * sizeof(unsigned), s));
-    // (queries without a partner and the np_extra gate: see find_pair)
-    const bool none_near = np_frac > 0 && (src.last_motion + tgt.last_motion) < np_gate * (double)d;
-    h->tm_certify.start(s);
-    launch_nn_certify(srcG, it.n, tgt.G4.p, cum_up, radius_sq(d), near2, none_near, ps.match.p, ps.match2.p, ps.lbe.p, sl.match_d2.p, sl.todo_near.p,
-                      sl.todo_far.p, ps.todo_count.p, s);
-    h->tm_certify.stop(s);
-    copy_out(h->h_todo_all.p + 2 * i, ps.todo_count.p, 2 * sizeof(unsigned), s);
-    rec.nn_certify_launches++; rec.nn_certify_queries += (long long)it.n; rec.nn_kernel_launches++;
-    double smin = cloud_smin(tgt);
-    if (!(smin > 1e-12)) smin = 1e-12;
-    double m_local = 0;
-    for (int k = 0; k < 3; ++k) m_local = std::max(m_local, std::max(std::fabs((double)tgt.lmin[k]), std::fabs((double)tgt.lmax[k])));
-    it.bp.margin = (float)(margin_frac * (double)d);
-    it.bp.rho_scale = round_up_f((1.0 + 1e-5) / smin);
-    it.bp.rho_pad = round_up_f(2.0 * tgt.build_slack + 8.0 * FLT_EPSILON * m_local);
-    it.bp.lo = it.cert.lo;
-    it.bp.cell_scale = it.cert.cell_scale; it.bp.cell_sub = it.cert.cell_sub;
-    it.bp.np_extra = none_near ? (float)(np_frac * (double)d) : 0.f;
-  }
-  sync(h);
-  // ---- phase B: searches, row update, totals ----------------------------------------------------------------------------------
-  for (size_t i = 0; i < B; ++i) {
-    BatchItem& it = items[i];
-    e3d_icp::PairSlot& sl = *h->slots[i];
-    Cloud& src = *it.src; Cloud& tgt = *it.tgt;
-    PairState& ps = *it.ps;
-    const size_t n = it.n;
-    const float4* srcG = src.G4.p + it.j0;
-    const float4* srcLN = src.LN.p + it.j0;
-    const unsigned* list = nullptr;
-    if (it.certified) {
-      it.n_near = h->h_todo_all.p[2 * i]; it.n_far = h->h_todo_all.p[2 * i + 1];
-      certify_ran(ps, src, tgt, it.n, it.n_near + it.n_far);
-      list = sl.todo_far.p;
-      const unsigned long long* half = tgt.has_half ? tgt.half_prefix.p : nullptr;
-      h->tm_bounded.start(s);
-      launch_nn_bounded(srcG, sl.todo_near.p, it.n_near, tgt.G4.p, tgt.dense_start.p, half, h->nn_mode == 5, tgt.grid, it.im, tgt.qrange, radius_sq(d), it.bp,
-                        ps.match.p, ps.match2.p, sl.match_d2.p, ps.lbe.p, s);
-      if (far_list_is_short(it.n_far, n)) {
-        launch_nn_bounded(srcG, sl.todo_far.p, it.n_far, tgt.G4.p, tgt.dense_start.p, half, h->nn_mode == 5, tgt.grid, it.im, tgt.qrange, radius_sq(d), it.bp,
-                          ps.match.p, ps.match2.p, sl.match_d2.p, ps.lbe.p, s);
-        it.n_near += it.n_far; it.n_far = 0;
-      }
-      h->tm_bounded.stop(s);
-      if (it.n_near > 0) { rec.nn_bounded_launches++; rec.nn_bounded_queries += (long long)it.n_near; rec.nn_kernel_launches++; }
-    }
-    if (it.n_far > 0) {
-      rec.nn_sort_calls++; rec.nn_kernel_launches++;
-      const size_t n_rows = sort_query_keys_pruned(h, ps, tgt, srcG, list, it.n_far, it.im, radius_sq(d), it.cert, sl.match_d2.p, it.from_state);
-      if (n_rows > 0) {
-        h->tm_search.start(s);
-        launch_rows(3, tgt, srcG, h->vals_b.p, n_rows, it.im, radius_sq(d), it.cert, ps.match.p, sl.match_d2.p, ps.lbe.p, ps.match2.p, s);
-        h->tm_search.stop(s);
-        rec.nn_search_launches++; rec.nn_search_queries += (long long)n_rows; rec.nn_kernel_launches++;
-      }
-    }
-    ps.fresh = false;
-    if (want_stats)
-      fprintf(stderr, "[nn %d->%d] queries %zu bounded %zu rows %zu cum %.3g (last %.3g) err %.3g\n", it.job->src, it.job->tgt, n, it.n_near, it.n_far,
-              it.cum_pair, src.last_motion + tgt.last_motion, src.err_max + tgt.err_max);
-    // resident rows (see find_pair)
-    const size_t cap = resident_rows_cap(n);
-    const bool sg = src.fixed || src.cloud_index == 0, tg = tgt.fixed || tgt.cloud_index == 0;
-    bool valid = ps.rows_valid && ps.pA.cap >= cap && ps.src_global == sg && ps.tgt_global == tg;
-    if (valid && sg && std::memcmp(ps.src_T, src.T, sizeof ps.src_T) != 0) valid = false;
-    if (valid && tg && std::memcmp(ps.tgt_T, tgt.T, sizeof ps.tgt_T) != 0) valid = false;
-    if (!valid) {
-      ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap); ps.plane_match.reserve(n); ps.glist.reserve(div_up(n, 64));
-      E3D_HIP(hipMemsetAsync(ps.plane_match.p, 0xFE, sizeof(int) * n, s));
-      if (cap > n) {
-        E3D_HIP(hipMemsetAsync(ps.pA.p + n, 0, sizeof(float4) * (cap - n), s));
-        E3D_HIP(hipMemsetAsync(ps.pB.p + n, 0, sizeof(float4) * (cap - n), s));
-        E3D_HIP(hipMemsetAsync(ps.pC.p + n, 0, sizeof(float4) * (cap - n), s));
-      }
-      ps.src_global = sg; ps.tgt_global = tg;
-      std::memcpy(ps.src_T, src.T, sizeof ps.src_T); std::memcpy(ps.tgt_T, tgt.T, sizeof ps.tgt_T);
-      ps.rows_valid = true;
-    }
-    h->tm_compact.start(s);
-    launch_corr_update(ps.match.p, ps.plane_match.p, sl.match_d2.p, n, (sg ? src.G4.p : src.L4.p) + it.j0, srcLN, sg, to_affine(src.T),
-                       tg ? tgt.G4.p : tgt.L4.p, tgt.LN.p, tg, to_affine(tgt.T), ps.pA.p, ps.pB.p, ps.pC.p, h->block_counts.p,
-                       h->block_d2.p, h->block_groups.p, s);
-    h->tm_compact.stop(s);
-    h->tm_scan.start(s);
-    launch_corr_totals(n, h->block_counts.p, h->block_d2.p, h->block_groups.p, h->chunk_sum.p, h->chunk_d2.p, h->chunk_groups.p,
-                       h->d_totals_all.p + 3 * i, h->d_d2_all.p + i, ps.glist.p, s);
-    h->tm_scan.stop(s);
-    rec.nn_update_launches++; rec.nn_kernel_launches += 4;
-  }
   copy_out(h->h_totals_all.p, h->d_totals_all.p, sizeof(unsigned long long) * 3 * B, s);
   copy_out(h->h_d2_all.p, h->d_d2_all.p, sizeof(double) * B, s);
   sync(h);
@@ -1163,20 +1108,78 @@ static void find_pairs_batched(e3d_icp* h, std::vector<BatchItem>& items, float 
   }
 }
 
+static void find_pairs_batched(e3d_icp* h, std::vector<BatchItem>& items, float d, e3d_icp_iter_record& rec) {
+  hipStream_t s = h->stream;
+  const size_t B = items.size();
+  while (h->slots.size() < B) h->slots.emplace_back(new e3d_icp::PairSlot());
+  h->h_todo_all.reserve(2 * kPairBatch); h->d_totals_all.reserve(3 * kPairBatch); h->d_d2_all.reserve(kPairBatch);
+  h->h_totals_all.reserve(3 * kPairBatch); h->h_d2_all.reserve(kPairBatch);
+  size_t n_max = 0;
+  for (BatchItem& it : items) n_max = std::max(n_max, it.n);
+  const size_t nb_max = div_up(n_max, kBlock);
+  h->block_counts.reserve(nb_max); h->block_d2.reserve(nb_max); h->block_groups.reserve(nb_max);
+  h->chunk_sum.reserve(div_up(nb_max, 256) + 1); h->chunk_d2.reserve(div_up(nb_max, 256) + 1); h->chunk_groups.reserve(2 * (div_up(nb_max, 256) + 1));
+  // ---- phase A: certificates ----------------------------------------------------------------------------------------------
+  for (size_t i = 0; i < B; ++i) {
+    BatchItem& it = items[i];
+    e3d_icp::PairSlot& sl = *h->slots[i];
+    PairState& ps = *it.ps;
+    sl.match_d2.reserve(it.n);
+    prepare_pair(it, d);
+    if (!it.certified) continue;
+    sl.todo_near.reserve(it.n); sl.todo_far.reserve(it.n);
+    E3D_HIP(hipMemsetAsync(ps.todo_count.p, 0, 2 * sizeof(unsigned), s));
+    h->tm_certify.start(s);
+    launch_nn_certify(it.src->G4.p + it.j0, it.n, it.tgt->G4.p, it.cum_up, radius_sq(d), it.near2, it.none_near, ps.match.p, ps.match2.p, ps.lbe.p, sl.match_d2.p,
+                      sl.todo_near.p, sl.todo_far.p, ps.todo_count.p, s);
+    h->tm_certify.stop(s);
+    copy_out(h->h_todo_all.p + 2 * i, ps.todo_count.p, 2 * sizeof(unsigned), s);
+    rec.nn_certify_launches++; rec.nn_certify_queries += (long long)it.n; rec.nn_kernel_launches++;
+  }
+  sync(h);
+  // ---- phase B: searches, row update, totals ----------------------------------------------------------------------------------
+  for (size_t i = 0; i < B; ++i) {
+    BatchItem& it = items[i];
+    e3d_icp::PairSlot& sl = *h->slots[i];
+    Cloud& src = *it.src; Cloud& tgt = *it.tgt;
+    PairState& ps = *it.ps;
+    const size_t n = it.n;
+    if (it.certified) {
+      it.n_near = h->h_todo_all.p[2 * i]; it.n_far = h->h_todo_all.p[2 * i + 1];
+      certify_ran(ps, src, tgt, n, it.n_near + it.n_far);
+      search_bounded_lists(h, it, sl.todo_near.p, sl.todo_far.p, sl.match_d2.p, d, rec);
+    }
+    search_far_list(h, it, it.certified ? sl.todo_far.p : nullptr, sl.match_d2.p, d, nullptr, rec);
+    ps.fresh = false;
+    print_pair_stats(it);
+    const RowFrames rf = ensure_resident_rows(ps, src, tgt, n, s);
+    h->tm_compact.start(s);
+    launch_corr_update(ps.match.p, ps.plane_match.p, sl.match_d2.p, n, (rf.sg ? src.G4.p : src.L4.p) + it.j0, src.LN.p + it.j0, rf.sg, to_affine(src.T),
+                       rf.tg ? tgt.G4.p : tgt.L4.p, tgt.LN.p, rf.tg, to_affine(tgt.T), ps.pA.p, ps.pB.p, ps.pC.p, h->block_counts.p,
+                       h->block_d2.p, h->block_groups.p, s);
+    h->tm_compact.stop(s);
+    h->tm_scan.start(s);
+    launch_corr_totals(n, h->block_counts.p, h->block_d2.p, h->block_groups.p, h->chunk_sum.p, h->chunk_d2.p, h->chunk_groups.p,
+                       h->d_totals_all.p + 3 * i, h->d_d2_all.p + i, ps.glist.p, s);
+    h->tm_scan.stop(s);
+    rec.nn_update_launches++; rec.nn_kernel_launches += 4;
+  }
+  read_back_batch(h, items, rec);
+}
+
 // The same batch with ONE launch per kernel (round 5): the batch's pairs go into a device table (NnBatchDev) and k_nn_certify_multi,
 // k_nn_bounded_half_multi, k_corr_update_multi and the three kernels of the totals walk it -- 7 launches and two host round trips per
 // batch where find_pairs_batched issues ~8 launches per PAIR.  Same kernels bodies on the same data: counts, distances, rows and group
 // lists are those of find_pair bit for bit (tests/test_gpu_switches.py, E3D_ICP_BATCH=1 / 0).  A pair's far list that is too long for
-// the bounded search (the first outer iterations) is still sorted and searched by k_nn_rows pair by pair.  Needs the half-cell
-// directory of every target of the batch (dense scans have it); returns false otherwise and the caller takes find_pairs_batched.
+// the bounded search (the first outer iterations) is still sorted and searched by k_nn_rows pair by pair (search_far_list) when the
+// batch's far lists cannot share one launch.  What the table says about a pair comes from prepare_pair and ensure_resident_rows.  Needs
+// the half-cell directory of every target of the batch (dense scans have it); returns false otherwise and the caller takes
+// find_pairs_batched.
 static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d, e3d_icp_iter_record& rec) {
   hipStream_t s = h->stream;
   const size_t B = items.size();
   for (const BatchItem& it : items) if (!it.tgt->has_half || h->nn_mode == 5) return false;
-  static const bool use_cert = [] { const char* e = getenv("E3D_NN_CERT"); return !(e && e[0] == '0'); }();
-  static const bool want_stats = [] { const char* e = getenv("E3D_NN_STATS"); return e && e[0] == '1'; }();
-  static const double margin_frac = env_double("E3D_NN_MARGIN", 0.08), near_frac = env_double("E3D_NN_NEAR", 0.4);   // of the radius
-  static const double np_frac = env_double("E3D_NN_NP_EXTRA", 0.5), np_gate = env_double("E3D_NN_NP_GATE", 0.2);   // of the radius
+  const NnSwitches& sw = nn_switches();
   while (h->slots.size() < B) h->slots.emplace_back(new e3d_icp::PairSlot());
   h->h_todo_all.reserve(2 * kPairBatch); h->d_todo_all.reserve(2 * kPairBatch);
   h->d_totals_all.reserve(3 * kPairBatch); h->d_d2_all.reserve(kPairBatch); h->h_totals_all.reserve(3 * kPairBatch); h->h_d2_all.reserve(kPairBatch);
@@ -1195,50 +1198,16 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
     PairState& ps = *it.ps;
     const size_t n = it.n;
     sl.match_d2.reserve(n); sl.todo_near.reserve(n); sl.todo_far.reserve(n);
-    it.im = make_invmap(tgt);
-    it.cum_pair = src.cum_motion + tgt.cum_motion;
-    MotionBound m_lo, m_up;
-    pair_motion_bounds(ps, src, tgt, m_lo, m_up);
-    it.cert = make_cert_params(tgt, m_lo);
-    it.n_far = n; it.n_near = 0;
-    it.certified = !ps.fresh && use_cert && certify_now(ps, src, tgt);
-    it.from_state = !ps.fresh && use_cert && !it.certified;
-    const bool none_near = np_frac > 0 && (src.last_motion + tgt.last_motion) < np_gate * (double)d;
-    double smin = cloud_smin(tgt);
-    if (!(smin > 1e-12)) smin = 1e-12;
-    double m_local = 0;
-    for (int k = 0; k < 3; ++k) m_local = std::max(m_local, std::max(std::fabs((double)tgt.lmin[k]), std::fabs((double)tgt.lmax[k])));
-    it.bp.margin = (float)(margin_frac * (double)d);
-    it.bp.rho_scale = round_up_f((1.0 + 1e-5) / smin);
-    it.bp.rho_pad = round_up_f(2.0 * tgt.build_slack + 8.0 * FLT_EPSILON * m_local);
-    it.bp.lo = it.cert.lo;
-    it.bp.cell_scale = it.cert.cell_scale; it.bp.cell_sub = it.cert.cell_sub;
-    it.bp.np_extra = none_near ? (float)(np_frac * (double)d) : 0.f;
-    // resident rows (see find_pair)
-    const size_t cap = resident_rows_cap(n);
-    const bool sg = src.fixed || src.cloud_index == 0, tg = tgt.fixed || tgt.cloud_index == 0;
-    bool valid = ps.rows_valid && ps.pA.cap >= cap && ps.src_global == sg && ps.tgt_global == tg;
-    if (valid && sg && std::memcmp(ps.src_T, src.T, sizeof ps.src_T) != 0) valid = false;
-    if (valid && tg && std::memcmp(ps.tgt_T, tgt.T, sizeof ps.tgt_T) != 0) valid = false;
-    if (!valid) {
-      ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap); ps.plane_match.reserve(n); ps.glist.reserve(div_up(n, 64));
-      E3D_HIP(hipMemsetAsync(ps.plane_match.p, 0xFE, sizeof(int) * n, s));
-      if (cap > n) {
-        E3D_HIP(hipMemsetAsync(ps.pA.p + n, 0, sizeof(float4) * (cap - n), s));
-        E3D_HIP(hipMemsetAsync(ps.pB.p + n, 0, sizeof(float4) * (cap - n), s));
-        E3D_HIP(hipMemsetAsync(ps.pC.p + n, 0, sizeof(float4) * (cap - n), s));
-      }
-      ps.src_global = sg; ps.tgt_global = tg;
-      std::memcpy(ps.src_T, src.T, sizeof ps.src_T); std::memcpy(ps.tgt_T, tgt.T, sizeof ps.tgt_T);
-      ps.rows_valid = true;
-    }
+    prepare_pair(it, d);
+    const RowFrames rf = ensure_resident_rows(ps, src, tgt, n, s);
+    const bool sg = rf.sg, tg = rf.tg;
     NnPairDev& P = T.pair[i];
     P.Gsrc = src.G4.p + it.j0; P.Gtgt = tgt.G4.p; P.S = tgt.dense_start.p; P.H8 = tgt.half_prefix.p;
     P.match = ps.match.p; P.match2 = ps.match2.p; P.lbe = ps.lbe.p; P.match_d2 = sl.match_d2.p;
     P.todo_near = sl.todo_near.p; P.todo_far = sl.todo_far.p; P.counts = h->d_todo_all.p + 2 * i;
-    P.n = (unsigned)n; P.none_near = none_near ? 1 : 0;
-    P.cum_up = m_up;
-    P.near2 = (float)((near_frac * (double)d) * (near_frac * (double)d));
+    P.n = (unsigned)n; P.none_near = it.none_near ? 1 : 0;
+    P.cum_up = it.cum_up;
+    P.near2 = it.near2;
     P.g = tgt.grid; P.im = it.im; P.qr = tgt.qrange; P.bp = it.bp;
     P.Psrc = (sg ? src.G4.p : src.L4.p) + it.j0; P.LNsrc = src.LN.p + it.j0; P.Ptgt = tg ? tgt.G4.p : tgt.L4.p; P.LNtgt = tgt.LN.p;
     P.src_global = sg ? 1 : 0; P.tgt_global = tg ? 1 : 0; P.Tsrc = to_affine(src.T); P.Ttgt = to_affine(tgt.T);
@@ -1256,14 +1225,12 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
   // (default 0.3 %) of the queries unsettled: a block is settled whole with probability exp(-256 x that share) (46 % at the gate,
   // 80 % at 0.09 %, the settled all-pairs job); below that the flag's extra round trip in front of every block of the update and
   // the extra sums in the certificate kernel cost more than the skipped blocks save (measured: profiles/round6_certify_update_fusion.txt).
-  static const bool fuse_update = [] { const char* e = getenv("E3D_NN_FUSE_UPDATE"); return !(e && e[0] == '0'); }();
-  static const double fuse_gate = env_double("E3D_NN_FUSE_GATE", 0.003);
   {
-    if (fuse_update && cert_blocks) { h->block_done.reserve(upd_blocks); E3D_HIP(hipMemsetAsync(h->block_done.p, 0, upd_blocks, s)); }
+    if (sw.fuse_update && cert_blocks) { h->block_done.reserve(upd_blocks); E3D_HIP(hipMemsetAsync(h->block_done.p, 0, upd_blocks, s)); }
     unsigned b0 = 0;
     for (size_t i = 0; i < B; ++i) {
       NnPairDev& P = T.pair[i];
-      const bool on = fuse_update && cert_blocks && items[i].certified && (1.0 - items[i].ps->settled_frac) < fuse_gate;
+      const bool on = sw.fuse_update && cert_blocks && items[i].certified && (1.0 - items[i].ps->settled_frac) < sw.fuse_gate;
       P.upd_counts = on ? h->block_counts.p + b0 : nullptr; P.upd_d2 = on ? h->block_d2.p + b0 : nullptr;
       P.upd_groups = on ? h->block_groups.p + b0 : nullptr; P.upd_done = on ? h->block_done.p + b0 : nullptr;
       b0 = T.upd_end[i];
@@ -1295,7 +1262,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
       job_queries += (long long)n_list;
     };
     add_job(sl.todo_near.p, it.n_near);
-    if (far_list_is_short(it.n_far, it.n)) {                  // (few queries without a near partner: see find_pair)
+    if (far_list_is_short(it.n_far, it.n)) {                  // (few queries without a near partner: search_bounded_lists)
       add_job(sl.todo_far.p, it.n_far);
       it.n_near += it.n_far; it.n_far = 0;
     }
@@ -1311,23 +1278,19 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
   // the far lists that are too long for the bounded search (first outer iterations): ONE key kernel, ONE sort, ONE k_nn_rows launch
   // for the batch (round 6; E3D_NN_FAR_BATCH=0: pair by pair as in round 5).  The pair's index rides above the cell key, so the
   // batch's keys need key_bits + log2(pairs) bits: 8-byte (key, query) pairs while that fits 32 bits.
-  static const bool far_batch = [] { const char* e = getenv("E3D_NN_FAR_BATCH"); return !(e && e[0] == '0'); }();
-  static const size_t prune_min_list = (size_t)env_double("E3D_NN_PRUNE_MIN", 262144.0);
   // SEEDS (k_query_seed_multi): once a fair share of a pair's queries found a partner in the last search (the scans are about to
   // meet, or have met), the key kernel probes the query's own half cell and the old partner; a query with a target point nearer than
   // E3D_NN_SEED_NEAR x radius takes it as its partner to start from and goes through the bounded search instead of sort + k_nn_rows.
   // E3D_NN_SEED=0: off; E3D_NN_SEED_FRAC: the matched share of the last search from which a pair's far list is seeded.
-  static const bool seed_allowed = [] { const char* e = getenv("E3D_NN_SEED"); return !(e && e[0] == '0'); }();
-  static const double seed_frac = env_double("E3D_NN_SEED_FRAC", 0.3), seed_near = env_double("E3D_NN_SEED_NEAR", 0.4);
-  static const bool seed_fresh = env_double("E3D_NN_SEED_FRESH", 0.0) != 0.0;      // (a pair's first search: nothing is known about it)
-  auto seeds_for = [&](const BatchItem& it) { return seed_allowed && it.n_far > 0 && (it.ps->fresh ? seed_fresh : it.ps->matched_frac >= seed_frac); };
+  // (E3D_NN_SEED_FRESH: a pair's first search, when nothing is known about it)
+  auto seeds_for = [&](const BatchItem& it) { return sw.seed_allowed && it.n_far > 0 && (it.ps->fresh ? sw.seed_fresh : it.ps->matched_frac >= sw.seed_frac); };
   size_t far_pairs = 0, far_total = 0;
   int kb_max = 1;
   for (size_t i = 0; i < B; ++i) if (items[i].n_far > 0) { ++far_pairs; far_total += items[i].n_far; kb_max = std::max(kb_max, items[i].tgt->key_bits); }
   int pair_bits = 0;
   while (((size_t)1 << pair_bits) < B) ++pair_bits;
   // (a batch whose keys would need 12-byte pairs only because of the pair bits keeps the 8-byte pairs of the pair-by-pair path)
-  const bool far_multi = far_batch && far_pairs > 0 && (kb_max + pair_bits <= 32 || kb_max > 31) && kb_max + pair_bits <= 63;
+  const bool far_multi = sw.far_batch && far_pairs > 0 && (kb_max + pair_bits <= 32 || kb_max > 31) && kb_max + pair_bits <= 63;
   if (!far_multi) launch_bounded_jobs();
   if (far_multi) {
     const bool k32 = kb_max + pair_bits <= 32;
@@ -1341,7 +1304,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
       NnPairDev& P = T.pair[i];
       P.far_n = 0; P.far_list = nullptr; P.far_flags = 0; P.occ = nullptr; P.occ_stride = 0; P.rows_off = 0; P.rows_n = 0; P.seed_list = nullptr; P.seed2 = 0.f;
       if (it.n_far > 0) {
-        const bool prune = it.tgt->has_occ && it.ps->prune && it.n_far >= prune_min_list;       // (sort_query_keys_pruned's rule)
+        const bool prune = it.tgt->has_occ && it.ps->prune && it.n_far >= sw.prune_min_list;       // (sort_query_keys_pruned's rule)
         const bool seed = seeds_for(it);
         P.far_n = (unsigned)it.n_far;
         P.far_list = it.certified ? h->slots[i]->todo_far.p : nullptr;
@@ -1349,7 +1312,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
         P.occ = it.tgt->has_occ ? it.tgt->occ27.p : nullptr; P.occ_stride = it.tgt->occ_stride;
         // (the seeded list behind the pair's near list: the two together are at most the pair's queries)
         P.seed_list = h->slots[i]->todo_near.p + (it.certified ? (size_t)h->h_todo_all.p[2 * i] : 0);
-        P.seed2 = (float)((seed_near * (double)d) * (seed_near * (double)d));
+        P.seed2 = (float)((sw.seed_near * (double)d) * (sw.seed_near * (double)d));
         key_blocks += (unsigned)div_up(it.n_far, key_block);
       }
       T.far_end[i] = key_blocks;
@@ -1404,23 +1367,10 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
   }
   for (size_t i = 0; i < B; ++i) {
     BatchItem& it = items[i];
-    PairState& ps = *it.ps;
-    if (it.n_far > 0 && !far_multi) {
-      e3d_icp::PairSlot& sl = *h->slots[i];
-      const float4* srcG = it.src->G4.p + it.j0;
-      const size_t n_rows = sort_query_keys_pruned(h, ps, *it.tgt, srcG, it.certified ? sl.todo_far.p : nullptr, it.n_far, it.im, radius_sq(d), it.cert, sl.match_d2.p, it.from_state);
-      rec.nn_kernel_launches++; rec.nn_sort_calls++;
-      if (n_rows > 0) {
-        h->tm_search.start(s);
-        launch_rows(3, *it.tgt, srcG, h->vals_b.p, n_rows, it.im, radius_sq(d), it.cert, ps.match.p, sl.match_d2.p, ps.lbe.p, ps.match2.p, s);
-        h->tm_search.stop(s);
-        rec.nn_search_launches++; rec.nn_search_queries += (long long)n_rows; rec.nn_kernel_launches++;
-      }
-    }
-    ps.fresh = false;
-    if (want_stats)
-      fprintf(stderr, "[nn %d->%d] queries %zu bounded %zu rows %zu cum %.3g (last %.3g) err %.3g\n", it.job->src, it.job->tgt, it.n, it.n_near, it.n_far,
-              it.cum_pair, it.src->last_motion + it.tgt->last_motion, it.src->err_max + it.tgt->err_max);
+    e3d_icp::PairSlot& sl = *h->slots[i];
+    if (!far_multi) search_far_list(h, it, it.certified ? sl.todo_far.p : nullptr, sl.match_d2.p, d, nullptr, rec);
+    it.ps->fresh = false;
+    print_pair_stats(it);
   }
   h->tm_compact.start(s);
   launch_corr_update_multi(h->d_batch.p, upd_blocks, h->block_counts.p, h->block_d2.p, h->block_groups.p, s);
@@ -1430,21 +1380,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
                            h->chunk_rewritten.p, h->d_totals_all.p, h->d_d2_all.p, s);
   h->tm_scan.stop(s);
   rec.nn_update_launches++; rec.nn_kernel_launches += 4; rec.nn_batches++;
-  copy_out(h->h_totals_all.p, h->d_totals_all.p, sizeof(unsigned long long) * 3 * B, s);
-  copy_out(h->h_d2_all.p, h->d_d2_all.p, sizeof(double) * B, s);
-  sync(h);
-  for (size_t i = 0; i < B; ++i) {
-    BatchItem& it = items[i];
-    it.job->count = (long long)h->h_totals_all.p[3 * i];
-    it.job->dsum = h->h_d2_all.p[i];
-    it.ps->matched_frac = it.n ? (double)it.job->count / (double)it.n : 1.0;
-    it.job->resident = it.ps;
-    it.job->vrows = 64 * (long long)h->h_totals_all.p[3 * i + 1];
-    rec.corr_rows_rewritten += (long long)h->h_totals_all.p[3 * i + 2];
-    rec.corr_rows_walked += it.job->vrows;
-    rec.queries += (long long)it.n;
-    rec.correspondences += it.job->count;
-  }
+  read_back_batch(h, items, rec);
   return true;
 }
 
@@ -1954,12 +1890,14 @@ static bool align_meshes(e3d_icp* h, float max_d, float thr, bool print, int ite
   {
     // Pairs of the certificate search with resident rows run in batches of up to kPairBatch (two host round trips per batch);
     // every other pair (sparse targets, forced kernel modes, compacted rows, the sequential distance sum) one by one.
-    static const bool batching = [] { const char* e = getenv("E3D_ICP_BATCH"); return !(e && e[0] == '0'); }();
     std::vector<BatchItem> batch;
     size_t batch_queries = 0;                               // (kBatchQueries bounds a batch's scratch)
     // E3D_ICP_BATCH: 2 (default) one launch per kernel and batch (find_pairs_multi), 1 one launch per kernel and pair with the host
     // round trips batched (find_pairs_batched), 0 pair by pair (find_pair)
-    static const int batch_mode = [] { const char* e = getenv("E3D_ICP_BATCH"); return e ? atoi(e) : 2; }();
+    // (a value that starts with '0' switches batching off, whatever follows)
+    static const char* const batch_env = getenv("E3D_ICP_BATCH");
+    static const bool batching = !(batch_env && batch_env[0] == '0');
+    static const int batch_mode = batch_env ? atoi(batch_env) : 2;
     auto flush = [&]() {
       if (batch.empty()) return;
       if (!(batch_mode >= 2 && find_pairs_multi(h, batch, max_d, rec))) find_pairs_batched(h, batch, max_d, rec);
@@ -2078,11 +2016,8 @@ static bool align_meshes(e3d_icp* h, float max_d, float thr, bool print, int ite
     const double glob = ((si == M) ? 0.0 : src.last_motion) + ((ti == M) ? 0.0 : tgt.last_motion);
     if (!accumulate_pair_motion(*kv.second, src, tgt, &T_before[12 * (size_t)si], src.T, &T_before[12 * (size_t)ti], tgt.T, glob)) ++h->nn_global_bound_updates;
   }
-  {
-    static const bool want_stats = [] { const char* e = getenv("E3D_NN_STATS"); return e && e[0] == '1'; }();
-    if (want_stats && h->nn_global_bound_updates)
-      fprintf(stderr, "[nn] %lld pose updates of a pair went into the clouds' global motion bound (a pose that is not near-rigid)\n", h->nn_global_bound_updates);
-  }
+  if (nn_switches().want_stats && h->nn_global_bound_updates)
+    fprintf(stderr, "[nn] %lld pose updates of a pair went into the clouds' global motion bound (a pose that is not near-rigid)\n", h->nn_global_bound_updates);
   rec.t_transform_ms = t_tr.ms();
   rec.t_nn_ms = t_nn.ms();
   rec.t_nn_sort_ms = h->tm_sort.take(); rec.t_nn_scan_ms = h->tm_scan.take(); rec.t_nn_compact_ms = h->tm_compact.take();
