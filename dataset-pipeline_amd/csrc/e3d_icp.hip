@@ -541,6 +541,8 @@ static PairState& pair_state_for(e3d_icp* h, int src_id, int tgt_id, const Cloud
   PairState& ps = *up;
   if (ps.n != n || ps.jbase != (long long)j0 || ps.src_gen != src.generation || ps.tgt_gen != tgt.generation) {
     ps.match.reserve(n); ps.match2.reserve(n); ps.lbe.reserve(n); ps.todo_count.reserve(2);
+    // no partner yet (-1): E3D_NN_SEED_FRESH has k_query_seed_multi read match[] before any search has written it
+    if (n) { E3D_HIP(hipMemsetAsync(ps.match.p, 0xFF, sizeof(int) * n, h->stream)); E3D_HIP(hipMemsetAsync(ps.match2.p, 0xFF, sizeof(int) * n, h->stream)); }
     ps.n = n; ps.jbase = (long long)j0; ps.src_gen = src.generation; ps.tgt_gen = tgt.generation;
     ps.fresh = true; ps.prune = true; ps.settled_frac = 1.0; ps.certify_motion = 0.0; ps.matched_frac = 1.0;
     ps.rows_valid = false;
@@ -600,7 +602,8 @@ static double pose_ortho_dev(const float* T) {
       double d = 0;
       for (int r = 0; r < 3; ++r) d += (double)T[4 * r + i] * (double)T[4 * r + j];
       const double e = std::fabs(d - (i == j ? 1.0 : 0.0));
-      if (!(e <= dev)) dev = e;
+      if (std::isnan(e)) return e;
+      dev = std::max(dev, e);
     }
   return dev;
 }
@@ -822,6 +825,7 @@ struct BatchItem {
   MotionBound cum_up;                  // the pair's accumulated motion, rounded up (k_nn_certify)
   float near2; bool none_near;
   bool certified = false, from_state = false; size_t n_near = 0, n_far = 0;
+  bool rows_reset = false;             // ensure_resident_rows reset the pair's rows in this outer iteration (find_pairs_multi)
 };
 
 static void prepare_pair(BatchItem& it, float d) {
@@ -1201,6 +1205,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
     prepare_pair(it, d);
     const RowFrames rf = ensure_resident_rows(ps, src, tgt, n, s);
     const bool sg = rf.sg, tg = rf.tg;
+    it.rows_reset = rf.reset;
     NnPairDev& P = T.pair[i];
     P.Gsrc = src.G4.p + it.j0; P.Gtgt = tgt.G4.p; P.S = tgt.dense_start.p; P.H8 = tgt.half_prefix.p;
     P.match = ps.match.p; P.match2 = ps.match2.p; P.lbe = ps.lbe.p; P.match_d2 = sl.match_d2.p;
@@ -1225,12 +1230,14 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
   // (default 0.3 %) of the queries unsettled: a block is settled whole with probability exp(-256 x that share) (46 % at the gate,
   // 80 % at 0.09 %, the settled all-pairs job); below that the flag's extra round trip in front of every block of the update and
   // the extra sums in the certificate kernel cost more than the skipped blocks save (measured: profiles/round6_certify_update_fusion.txt).
+  // Never in the iteration that reset the pair's rows (another frame or pose of a global half, rows released and allocated again while
+  // the search state lived on): a skipped block keeps its rows as they are, and after a reset no row has been written yet.
   {
     if (sw.fuse_update && cert_blocks) { h->block_done.reserve(upd_blocks); E3D_HIP(hipMemsetAsync(h->block_done.p, 0, upd_blocks, s)); }
     unsigned b0 = 0;
     for (size_t i = 0; i < B; ++i) {
       NnPairDev& P = T.pair[i];
-      const bool on = sw.fuse_update && cert_blocks && items[i].certified && (1.0 - items[i].ps->settled_frac) < sw.fuse_gate;
+      const bool on = sw.fuse_update && cert_blocks && items[i].certified && !items[i].rows_reset && (1.0 - items[i].ps->settled_frac) < sw.fuse_gate;
       P.upd_counts = on ? h->block_counts.p + b0 : nullptr; P.upd_d2 = on ? h->block_d2.p + b0 : nullptr;
       P.upd_groups = on ? h->block_groups.p + b0 : nullptr; P.upd_done = on ? h->block_done.p + b0 : nullptr;
       b0 = T.upd_end[i];
@@ -1293,7 +1300,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
   const bool far_multi = sw.far_batch && far_pairs > 0 && (kb_max + pair_bits <= 32 || kb_max > 31) && kb_max + pair_bits <= 63;
   if (!far_multi) launch_bounded_jobs();
   if (far_multi) {
-    const bool k32 = kb_max + pair_bits <= 32;
+    const bool k32 = kb_max <= 31 && kb_max + pair_bits <= 32;      // (search_far_list's rule: the <unsigned> key kernels shift by kb_max)
     bool seed_any = false;
     for (size_t i = 0; i < B; ++i)
       if (seeds_for(items[i])) seed_any = true;
