@@ -122,6 +122,11 @@ SIGNATURES = {
     "e3d_reg_count_scan_observations": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "e3d_reg_get_scan_observation_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
     "e3d_reg_set_scan_observation_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_reg_scan_colors_begin": (C.c_int, [C.c_void_p]),
+    "e3d_reg_scan_colors_add_image": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]),
+    "e3d_reg_scan_colors_get_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_reg_scan_colors_set_sums": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_reg_scan_colors_finish": (C.c_int, [C.c_void_p, C.c_void_p]),
     "e3d_reg_ground_truth_depth": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "e3d_reg_scan_rendering": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "e3d_reg_set_cache_observations": (C.c_int, [C.c_void_p, C.c_int]),
@@ -725,6 +730,35 @@ class RegProblem:
         counts = np.ascontiguousarray(counts, np.int32)
         assert counts.shape[0] == self._n_scan
         self._chk(lib().e3d_reg_set_scan_observation_counts(self._h, C.c_void_p(counts.ctypes.data)), "e3d_reg_set_scan_observation_counts")
+
+    # ---- debug point clouds (Problem::DebugWriteColoredPointCloud) ----------------------------------------------------
+    def scan_colors_begin(self):
+        """Zero the colour sums and observation counts of the scan points (set_scan_points)."""
+        self._chk(lib().e3d_reg_scan_colors_begin(self._h), "e3d_reg_scan_colors_begin")
+
+    def scan_colors_add_image(self, image_id, rgb):
+        """rgb: (height, width, 3) uint8, R G B -- the image file as decoded, at its own size."""
+        rgb = np.ascontiguousarray(rgb, np.uint8)
+        assert rgb.ndim == 3 and rgb.shape[2] == 3
+        self._chk(lib().e3d_reg_scan_colors_add_image(self._h, int(image_id), C.c_void_p(rgb.ctypes.data), rgb.shape[1], rgb.shape[0]),
+                  "e3d_reg_scan_colors_add_image")
+
+    def scan_colors_sums(self):
+        """-> (sums (n, 3) float32 r g b, counts (n,) int32)."""
+        sums = np.zeros((self._n_scan, 3), np.float32); counts = np.zeros(self._n_scan, np.int32)
+        self._chk(lib().e3d_reg_scan_colors_get_sums(self._h, C.c_void_p(sums.ctypes.data), C.c_void_p(counts.ctypes.data)), "e3d_reg_scan_colors_get_sums")
+        return sums, counts
+
+    def scan_colors_set_sums(self, sums, counts):
+        sums = np.ascontiguousarray(sums, np.float32); counts = np.ascontiguousarray(counts, np.int32)
+        assert sums.shape == (self._n_scan, 3) and counts.shape == (self._n_scan,)
+        self._chk(lib().e3d_reg_scan_colors_set_sums(self._h, C.c_void_p(sums.ctypes.data), C.c_void_p(counts.ctypes.data)), "e3d_reg_scan_colors_set_sums")
+
+    def scan_colors_finish(self):
+        """-> (n, 3) uint8: (uint8)(sum / count + 0.5f) per channel, 0 0 0 where count == 0."""
+        rgb = np.zeros((self._n_scan, 3), np.uint8)
+        self._chk(lib().e3d_reg_scan_colors_finish(self._h, C.c_void_p(rgb.ctypes.data)), "e3d_reg_scan_colors_finish")
+        return rgb
 
     def ground_truth_depth(self, image_id, width, height, mask=None, excluded_flag=2, min_count=2):
         """-> (gt_depth, occlusion_depth), both (height, width) float32."""

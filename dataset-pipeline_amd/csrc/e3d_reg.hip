@@ -779,7 +779,36 @@ __device__ __forceinline__ float2 image_to_normalized(const CamLevel& c, const f
 
 struct RadiusParams { int image_scale, min_image_scale; float occlusion_threshold, max_valid_intensity; double min_scaling_factor; };
 
-// one image: observations without scale test (visibility_estimator.cc:297-364), then the radius that projects to half a pixel
+// _AppendObservationsForImageNoScale for one point (visibility_estimator.cc:297-364): in front of the camera, rounded pixel inside
+// the level `cam`, not behind the occlusion depth, not under an image or camera mask pixel, not over-saturated -- all at the level
+// rp.image_scale.  True: (ox, oy) is the observation's position at its smaller interpolation scale and returned_scale its scale.
+template <int M>
+__device__ __forceinline__ bool observe_no_scale(const float4 p, const Pose& P, const CamLevel& cam, const unsigned char* __restrict__ img,
+                                                 const unsigned char* __restrict__ mask, const unsigned char* __restrict__ cam_mask,
+                                                 const float* __restrict__ occlusion, const RadiusParams& rp, float& ox, float& oy,
+                                                 float& returned_scale) {
+  float X, Y, Z;
+  rt(P, p.x, p.y, p.z, X, Y, Z);
+  if (!(Z > 0.f)) return false;
+  float ixf, iyf;
+  cam_normalized_to_image<M>(cam, X / Z, Y / Z, ixf, iyf);
+  const int ix = f2i(ixf + 0.5f), iy = f2i(iyf + 0.5f);
+  if (!(ixf + 0.5f >= 0 && iyf + 0.5f >= 0 && ix >= 0 && iy >= 0 && ix < cam.width && iy < cam.height)) return false;
+  if (!(occlusion[(size_t)iy * cam.width + ix] + rp.occlusion_threshold >= Z)) return false;
+  if (mask && mask[(size_t)iy * cam.width + ix] != 0) return false;
+  if (cam_mask && cam_mask[(size_t)iy * cam.width + ix] != 0) return false;                    // visibility_estimator.cc:335-345
+  if (img[(size_t)iy * cam.width + ix] > rp.max_valid_intensity) return false;
+  returned_scale = rp.image_scale - 1e-6f;
+  ox = ixf; oy = iyf;
+  if (returned_scale < 0.f) {
+    returned_scale = 0.f;
+    ox = 0.5f * (ox + 0.5f) - 0.5f;
+    oy = 0.5f * (oy + 0.5f) - 0.5f;
+  }
+  return true;
+}
+
+// one image: observations without scale test, then the radius that projects to half a pixel
 // at the best image scale; each point is touched by one thread per image and the images are processed one after the other, so
 // the running min / max need no atomics
 template <int M>
@@ -792,24 +821,8 @@ __global__ __launch_bounds__(kBlock) void k_point_radius(const float4* __restric
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float4 p = pts[i];
-  float X, Y, Z;
-  rt(P, p.x, p.y, p.z, X, Y, Z);
-  if (!(Z > 0.f)) return;
-  float ixf, iyf;
-  cam_normalized_to_image<M>(cam, X / Z, Y / Z, ixf, iyf);
-  const int ix = f2i(ixf + 0.5f), iy = f2i(iyf + 0.5f);
-  if (!(ixf + 0.5f >= 0 && iyf + 0.5f >= 0 && ix >= 0 && iy >= 0 && ix < cam.width && iy < cam.height)) return;
-  if (!(occlusion[(size_t)iy * cam.width + ix] + rp.occlusion_threshold >= Z)) return;
-  if (mask && mask[(size_t)iy * cam.width + ix] != 0) return;
-  if (cam_mask && cam_mask[(size_t)iy * cam.width + ix] != 0) return;                          // visibility_estimator.cc:335-345
-  if (img[(size_t)iy * cam.width + ix] > rp.max_valid_intensity) return;
-  float returned_scale = rp.image_scale - 1e-6f;
-  float ox = ixf, oy = iyf;
-  if (returned_scale < 0.f) {
-    returned_scale = 0.f;
-    ox = 0.5f * (ox + 0.5f) - 0.5f;
-    oy = 0.5f * (oy + 0.5f) - 0.5f;
-  }
+  float ox, oy, returned_scale;
+  if (!observe_no_scale<M>(p, P, cam, img, mask, cam_mask, occlusion, rp, ox, oy, returned_scale)) return;
   const int smaller_scale = (int)returned_scale + 1;
   const float up = exp2f((float)(smaller_scale - rp.min_image_scale));     // exact power of two
   const float mx = up * (ox + 0.5f) - 0.5f, my = up * (oy + 0.5f) - 0.5f;
@@ -834,6 +847,57 @@ __global__ __launch_bounds__(kBlock) void k_point_radius(const float4* __restric
   if (point_radius < min_radius[i]) min_radius[i] = point_radius;
   const float mr = (float)((double)point_radius / rp.min_scaling_factor);
   if (mr > max_radius[i]) max_radius[i] = mr;
+}
+
+// ==== debug point clouds (Problem::DebugWriteColoredPointCloud, problem.cc:642-704) ==============================================
+// One image: every scan point that is an observation without scale test takes a bilinear sample of the colour image
+// (InterpolateBilinearVec3, interpolate_bilinear.h:117-146) at its position at the camera's highest resolution
+// (PointObservation::image_x_at_scale(min_image_scale), point_observation.h:84-93) and adds it to its accumulator {r, g, b sums as
+// f32, count as int bits} -- one 16-byte record, one load and one store.  A point is touched by one thread per image and the images
+// run one after the other on the handle's stream, so there are no atomics (as in k_point_radius).  rgb: cols x rows pixels of 3
+// bytes, R G B, the file's own size -- the sample is rejected by ITS bounds, whatever the camera's size is.
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_scan_colors(const float4* __restrict__ pts, size_t n, Pose P, CamLevel cam,
+                                                        const unsigned char* __restrict__ img, const unsigned char* __restrict__ mask,
+                                                        const unsigned char* __restrict__ cam_mask, const float* __restrict__ occlusion,
+                                                        RadiusParams rp, const unsigned char* __restrict__ rgb, int cols, int rows,
+                                                        float4* __restrict__ acc) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float ox, oy, returned_scale;
+  if (!observe_no_scale<M>(pts[i], P, cam, img, mask, cam_mask, occlusion, rp, ox, oy, returned_scale)) return;
+  const int smaller_scale = (int)returned_scale + 1;
+  const float up = exp2f((float)(smaller_scale - rp.min_image_scale));     // exact power of two
+  const float x = up * (ox + 0.5f) - 0.5f, y = up * (oy + 0.5f) - 0.5f;
+  const int ix = f2i(x), iy = f2i(y);
+  // (!(x >= 0) is x < 0 for the finite positions an observation has and keeps a NaN out: 0 <= ix <= cols - 2, 0 <= iy <= rows - 2 below)
+  if (!(x >= 0.f) || !(y >= 0.f) || ix >= cols - 1 || iy >= rows - 1) return;
+  const float fx = x - (float)ix, fx_inv = 1.f - fx, fy = y - (float)iy, fy_inv = 1.f - fy;
+  const unsigned char* top = rgb + ((size_t)iy * cols + ix) * 3;
+  const unsigned char* bottom = top + (size_t)cols * 3;
+  float c[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k)
+    c[k] = fx_inv * fy_inv * (float)top[k] + fx * fy_inv * (float)top[3 + k] + fx_inv * fy * (float)bottom[k] + fx * fy * (float)bottom[3 + k];
+  float4 a = acc[i];
+  a.x += c[0]; a.y += c[1]; a.z += c[2];
+  a.w = __int_as_float(__float_as_int(a.w) + 1);
+  acc[i] = a;
+}
+
+// point->r = color_sums.x() / observation_counts + 0.5f (problem.cc:690-696): f32 divide, truncation to u8; never observed = 0 0 0
+__global__ __launch_bounds__(kBlock) void k_scan_colors_finish(const float4* __restrict__ acc, size_t n, unsigned char* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float4 a = acc[i];
+  const int count = __float_as_int(a.w);
+  unsigned char r = 0, g = 0, b = 0;
+  if (count > 0) {
+    r = (unsigned char)(a.x / (float)count + 0.5f);
+    g = (unsigned char)(a.y / (float)count + 0.5f);
+    b = (unsigned char)(a.z / (float)count + 0.5f);
+  }
+  out[3 * i] = r; out[3 * i + 1] = g; out[3 * i + 2] = b;
 }
 
 // ==== a20 / a21: observation candidates =============================================================================================
@@ -2333,6 +2397,11 @@ struct e3d_reg {
   DevBuf<unsigned char> eval_mask;
   DevBuf<unsigned> gt_depth;
   size_t n_scan = 0;
+  bool scan_points_set = false;
+  // debug point clouds (e3d_reg_scan_colors_*): per scan point {r, g, b sums (f32), count (int bits)}, the colour image being sampled
+  DevBuf<float4> scan_color_acc;
+  DevBuf<unsigned char> scan_color_image, scan_color_rgb;
+  bool scan_colors_begun = false;
   // scratch
   DevBuf<int> valid;
   DevBuf<float> tx, ty, ts;
@@ -4216,7 +4285,7 @@ int e3d_reg_set_scan_points(e3d_reg_t* h, const float* xyz, size_t n) {
   R_TRYH
   if (!h || (n && !xyz)) throw Error(E3D_ERR_INVALID, "null argument");
   if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "more than 2^31-1 scan points");
-  h->n_scan = n;
+  h->n_scan = n; h->scan_points_set = true; h->scan_colors_begun = false;
   h->scan_pts.reserve(n); h->scan_counts.reserve(n);
   if (n) {
     DevBuf<float> raw;
@@ -4301,6 +4370,98 @@ int e3d_reg_scan_rendering(e3d_reg_t* h, int image_id, const uint8_t* mask, int 
   scan_visibility(h, image_id, mask, excluded_flag, 2, min_count, point_radius);
   copy_out(winner, h->gt_depth.p, sizeof(unsigned) * px, h->stream);
   rsync(h);
+  return 0;
+  R_CATCH()
+}
+
+// ---- debug point clouds (Problem::DebugWriteColoredPointCloud, src/opt/problem.cc:642-704) ---------------------------------------
+int e3d_reg_scan_colors_begin(e3d_reg_t* h) {
+  R_TRYH
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
+  h->scan_color_acc.reserve(h->n_scan);
+  if (h->n_scan) E3D_HIP(hipMemsetAsync(h->scan_color_acc.p, 0, sizeof(float4) * h->n_scan, h->stream));     // 0.f sums, count 0
+  rsync(h);
+  h->scan_colors_begun = true;
+  return 0;
+  R_CATCH()
+}
+int e3d_reg_scan_colors_add_image(e3d_reg_t* h, int image_id, const uint8_t* rgb, int width, int height) {
+  R_TRYH
+  if (!h || !rgb) throw Error(E3D_ERR_INVALID, "null argument");
+  if (width < 2 || height < 2) throw Error(E3D_ERR_INVALID, "a colour image needs at least 2 x 2 pixels for a bilinear sample");
+  if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
+  if (!h->scan_colors_begun) throw Error(E3D_ERR_INVALID, "call e3d_reg_scan_colors_begin first");
+  ImageDev& im = get_image(h, image_id);
+  if (!h->owns(image_id)) throw Error(E3D_ERR_INVALID, fmt("image %d belongs to rank %d", image_id, e3d_reg_image_owner(h, image_id)));
+  if (h->n_scan == 0) return 0;
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  const int scale = best_available_scale(h, in);
+  if (e3d_reg_render_depth(h, image_id, scale, nullptr) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+  const int lvl = std::max(0, scale - in.min_image_scale);
+  const CamLevel& cam = in.levels[lvl];
+  const size_t bytes = (size_t)width * height * 3;
+  h->scan_color_image.reserve(bytes);
+  copy_in(h->scan_color_image.p, rgb, bytes, h->stream);
+  RadiusParams rp{};
+  rp.image_scale = scale; rp.min_image_scale = in.min_image_scale;
+  rp.occlusion_threshold = h->prm.occlusion_depth_threshold; rp.max_valid_intensity = h->prm.maximum_valid_intensity;
+  {
+    KT kt(h, "debug.scan_colors", (double)h->n_scan);
+    E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_scan_colors<M>, dim3(nblk(h->n_scan)), dim3(kBlock), 0, h->stream, h->scan_pts.p, h->n_scan,
+                                               im.pose, cam, im.pix[lvl].p, im.has_mask[lvl] ? im.mask[lvl].p : nullptr,
+                                               (in.cam_mask && lvl < (int)in.cam_mask->size()) ? (*in.cam_mask)[lvl].p : nullptr, im.depth.p, rp,
+                                               h->scan_color_image.p, width, height, h->scan_color_acc.p));
+  }
+  rsync(h);                          // (the caller's pixels may go away after the call)
+  E3D_HIP(hipGetLastError());
+  return 0;
+  R_CATCH()
+}
+int e3d_reg_scan_colors_get_sums(e3d_reg_t* h, float* sums, int32_t* counts) {
+  R_TRYH
+  if (!h || (h->n_scan && (!sums || !counts))) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!h->scan_colors_begun) throw Error(E3D_ERR_INVALID, "call e3d_reg_scan_colors_begin first");
+  std::vector<float4> acc(h->n_scan);
+  if (h->n_scan) copy_out(acc.data(), h->scan_color_acc.p, sizeof(float4) * h->n_scan, h->stream);
+  rsync(h);
+  for (size_t i = 0; i < h->n_scan; ++i) {
+    sums[3 * i] = acc[i].x; sums[3 * i + 1] = acc[i].y; sums[3 * i + 2] = acc[i].z;
+    memcpy(&counts[i], &acc[i].w, sizeof(int32_t));
+  }
+  return 0;
+  R_CATCH()
+}
+int e3d_reg_scan_colors_set_sums(e3d_reg_t* h, const float* sums, const int32_t* counts) {
+  R_TRYH
+  if (!h || (h->n_scan && (!sums || !counts))) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
+  std::vector<float4> acc(h->n_scan);
+  for (size_t i = 0; i < h->n_scan; ++i) {
+    acc[i].x = sums[3 * i]; acc[i].y = sums[3 * i + 1]; acc[i].z = sums[3 * i + 2];
+    memcpy(&acc[i].w, &counts[i], sizeof(int32_t));
+  }
+  h->scan_color_acc.reserve(h->n_scan);
+  if (h->n_scan) copy_in(h->scan_color_acc.p, acc.data(), sizeof(float4) * h->n_scan, h->stream);
+  rsync(h);
+  h->scan_colors_begun = true;
+  return 0;
+  R_CATCH()
+}
+int e3d_reg_scan_colors_finish(e3d_reg_t* h, uint8_t* rgb) {
+  R_TRYH
+  if (!h || (h->n_scan && !rgb)) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!h->scan_colors_begun) throw Error(E3D_ERR_INVALID, "call e3d_reg_scan_colors_begin first");
+  if (h->n_scan) {
+    h->scan_color_rgb.reserve(3 * h->n_scan);
+    {
+      KT kt(h, "debug.scan_colors_finish", (double)h->n_scan);
+      hipLaunchKernelGGL(k_scan_colors_finish, dim3(nblk(h->n_scan)), dim3(kBlock), 0, h->stream, h->scan_color_acc.p, h->n_scan, h->scan_color_rgb.p);
+    }
+    copy_out(rgb, h->scan_color_rgb.p, 3 * h->n_scan, h->stream);
+  }
+  rsync(h);
+  E3D_HIP(hipGetLastError());
   return 0;
   R_CATCH()
 }

@@ -6,7 +6,7 @@
 // Occlusion meshes (--occlusion_mesh_path / --occlusion_splats_path) are rasterised on the GPU by the library instead of OpenGL.
 // Observations are cached like in the reference: from the second image scale on (or from the first with
 // --cache_observations 1) the visible point lists are fixed and kept in --observations_cache_path.
-// Not built yet (the tool says so instead of silently doing something else): --write_debug_point_clouds.
+// --write_debug_point_clouds 1 writes the scans coloured by the images (initial_point_cloud.ply, scale_<factor>_final_point_cloud.ply).
 #include <exception>
 #include <cmath>
 #include <cstdlib>
@@ -40,6 +40,8 @@ static int run_tool(int argc, char** argv) {
   parse_argument(argc, argv, "--camera_ids_to_ignore", camera_ids_to_ignore_string);
   bool cache_observations = false;
   parse_argument(argc, argv, "--cache_observations", cache_observations);
+  bool write_debug_point_clouds = false;
+  parse_argument(argc, argv, "--write_debug_point_clouds", write_debug_point_clouds);
   int gpus = 1;     // not a flag of the reference: GPUs of this node to shard the images over (image id mod N)
   parse_argument(argc, argv, "--gpus", gpus);
   if (gpus > 1 && !set_gpu_count(gpus)) return EXIT_FAILURE;
@@ -113,6 +115,19 @@ static int run_tool(int argc, char** argv) {
   if (ReadColmapRigs(state_path + "/rigs.json", &rig_vector) && !problem.AssignRigs(rig_vector)) return EXIT_FAILURE;
   if (!problem.SetScanGeometryAndInitialize(colored_scans, occlusion_points, multi_res_point_cloud_directory_path)) return EXIT_FAILURE;
 
+  // Debug: the scans coloured by the images at the initial state, unless the file exists (image_registrator.cc:200-215)
+  if (write_debug_point_clouds) {
+    const std::string point_cloud_filename = "initial_point_cloud.ply";
+    const std::string point_cloud_path = join_path(output_folder_path, point_cloud_filename);
+    if (file_exists(point_cloud_path)) {
+      std::cout << "Not writing initial point cloud since " << point_cloud_filename << " already exists." << std::endl;
+    } else {
+      std::cout << "Writing initial point cloud ..." << std::endl;
+      if (!problem.DebugWriteColoredPointCloud(occlusion_points, point_cloud_path)) return EXIT_FAILURE;
+      std::cout << "Wrote " << point_cloud_filename << std::endl;
+    }
+  }
+
   constexpr float kMaxChangeConvergenceThreshold = 0;
   constexpr int kIterationsWithoutNewOptimumThreshold = 15;
   const int max_image_scale_minus_one = problem.max_image_scale() - 1;
@@ -166,6 +181,15 @@ static int run_tool(int argc, char** argv) {
     metadata_stream << std::endl;
     metadata_stream << "optimum_cost " << optimum_cost << std::endl;
     metadata_stream.close();
+
+    // Debug: the scans coloured by the images at this scale's result (image_registrator.cc:286-295)
+    if (write_debug_point_clouds) {
+      std::ostringstream point_cloud_filename;
+      point_cloud_filename << "scale_" << current_scaling_factor << "_final_point_cloud.ply";
+      std::cout << "Writing point cloud ..." << std::endl;
+      if (!problem.DebugWriteColoredPointCloud(occlusion_points, join_path(output_folder_path, point_cloud_filename.str()))) return EXIT_FAILURE;
+      std::cout << "Wrote " << point_cloud_filename.str() << std::endl;
+    }
 
     if (std::fabs(current_scaling_factor - target_scaling_factor) < 1e-8 || current_scaling_factor > target_scaling_factor) {
       std::cout << "Target scaling factor reached, stopping." << std::endl;

@@ -11,6 +11,7 @@
 //                                           src/opt/multi_scale_point_cloud.cc:182-369 (radius ranges and merging on the GPU)
 //   fixed descriptors                       src/opt/problem.cc:549-572
 //   io::ExportProblemToColmap / ExportRigs  src/io/colmap_model.cc:286-516
+//   Problem::DebugWriteColoredPointCloud    src/opt/problem.cc:642-704 (visibility and colour sampling on the GPU)
 #pragma once
 
 #include <sys/stat.h>
@@ -954,6 +955,40 @@ class Problem {
     for (HostRig& rig : rigs)
       for (size_t c = 0; c < rig.image_T_rig.size(); ++c)
         if (api().e3d_reg_get_rig(reg, rig.rig_id, (int)c, rig.image_T_rig[c].q, rig.image_T_rig[c].t) < 0) return lib_fail("e3d_reg_get_rig");
+    return true;
+  }
+
+  // Problem::DebugWriteColoredPointCloud (src/opt/problem.cc:642-704): the points xyz (n x 3, global frame) coloured by all images at
+  // the device problem's current state -- per image, in ascending id, the observations without scale test sample the colour image
+  // file bilinearly (e3d_reg_scan_colors_*); the mean colour per point goes to a binary PLY of pcl::PointXYZRGB layout.
+  // With --gpus N every rank accumulates its own images; the partial sums (f32) and counts are added here in rank order and finished on
+  // rank 0.  f32 addition is not associative, so a channel may differ by one level from the single-GPU file, whose sums grow image by
+  // image.
+  bool DebugWriteColoredPointCloud(const std::vector<float>& xyz, const std::string& ply_path) {
+    const size_t n = xyz.size() / 3;
+    if (!all_regs([&](e3d_reg_t* r) { return api().e3d_reg_set_scan_points(r, xyz.data(), n); }, "e3d_reg_set_scan_points")) return false;
+    if (!all_regs([&](e3d_reg_t* r) { return api().e3d_reg_scan_colors_begin(r); }, "e3d_reg_scan_colors_begin")) return false;
+    for (const auto& kv : images) {
+      std::string err;
+      const ColorImage color = imread_color(kv.second.file_path, &err);
+      if (color.empty()) return fail("Cannot read image: " + kv.second.file_path);
+      if (api().e3d_reg_scan_colors_add_image(owner(kv.first), kv.first, color.rgb.data(), color.width, color.height) < 0)
+        return lib_fail("e3d_reg_scan_colors_add_image");
+    }
+    if (regs.size() > 1) {
+      std::vector<float> total(3 * n), part(3 * n);
+      std::vector<int32_t> total_counts(n), part_counts(n);
+      if (api().e3d_reg_scan_colors_get_sums(regs[0], total.data(), total_counts.data()) < 0) return lib_fail("e3d_reg_scan_colors_get_sums");
+      for (size_t k = 1; k < regs.size(); ++k) {
+        if (api().e3d_reg_scan_colors_get_sums(regs[k], part.data(), part_counts.data()) < 0) return lib_fail("e3d_reg_scan_colors_get_sums");
+        for (size_t i = 0; i < 3 * n; ++i) total[i] += part[i];
+        for (size_t i = 0; i < n; ++i) total_counts[i] += part_counts[i];
+      }
+      if (api().e3d_reg_scan_colors_set_sums(reg, total.data(), total_counts.data()) < 0) return lib_fail("e3d_reg_scan_colors_set_sums");
+    }
+    std::vector<uint8_t> rgb(3 * n);
+    if (api().e3d_reg_scan_colors_finish(reg, rgb.data()) < 0) return lib_fail("e3d_reg_scan_colors_finish");
+    if (savePLYFileBinaryXYZRGB(ply_path, xyz, rgb) < 0) return fail("Cannot write " + ply_path);
     return true;
   }
 

@@ -490,6 +490,30 @@ int e3d_reg_ground_truth_depth(e3d_reg_t* reg, int image_id, const uint8_t* mask
  * per pixel is the LAST point covering it: winner[y * width + x] = point index + 1 (order of e3d_reg_set_scan_points), 0 = untouched. */
 int e3d_reg_scan_rendering(e3d_reg_t* reg, int image_id, const uint8_t* mask, int excluded_flag, int min_count, int point_radius,
                            uint32_t* winner);
+/* Problem::DebugWriteColoredPointCloud (src/opt/problem.cc:642-704), the output of ImageRegistrator --write_debug_point_clouds
+ * (src/exe/image_registrator.cc:202-215, :287-295): the scan points of e3d_reg_set_scan_points coloured by the images at their
+ * current poses.
+ *   e3d_reg_scan_colors_begin: zero colour sums and observation counts (problem.cc:644-649).
+ *   e3d_reg_scan_colors_add_image: one image of this rank (problem.cc:655-682).  Observations without scale test
+ *     (VisibilityEstimator::AppendObservationsForImageNoScale, visibility_estimator.cc:117-138, :297-364): occlusion depth map, camera
+ *     level, masks and grey values at best_available_image_scale(max(min_occlusion_check_image_scale (0), current_image_scale)); z > 0,
+ *     rounded pixel inside the level, occlusion + occlusion_depth_threshold >= z, image mask == 0, camera mask == 0, grey value <=
+ *     maximum_valid_intensity.  Each observation samples `rgb` (width x height pixels of 3 bytes R, G, B: cv::imread(IMREAD_COLOR) of
+ *     the image file at the file's own size) bilinearly (InterpolateBilinearVec3, interpolate_bilinear.h:117-146) at
+ *     image_x/y_at_scale(min_image_scale) (point_observation.h:84-93); a sample with x < 0, y < 0, (int)x >= width - 1 or
+ *     (int)y >= height - 1 is dropped, any other adds its f32 colour to the point's sums and 1 to its count.
+ *   e3d_reg_scan_colors_get/set_sums: the accumulators (sums: 3 floats r g b per scan point, counts: one int, input order).  With
+ *     image sharding every rank accumulates its own images; the caller adds the vectors (f32 sums, in rank order) and installs the
+ *     totals on one rank with set_sums before finish.  f32 addition is not associative: a channel may then differ by one level from
+ *     the single-GPU result, whose sums grow image by image.
+ *   e3d_reg_scan_colors_finish: rgb[3 i + c] = (uint8)(sum / count + 0.5f), 0 0 0 for a point no image coloured (problem.cc:687-697).
+ * Errors (negative return, e3d_last_error): null handle or pixels, unknown image, an image of another rank, width or height < 2, no
+ * scan points set, add_image / get_sums / finish without begin (set_sums counts as begin).  No scan points (n = 0) is not an error. */
+int e3d_reg_scan_colors_begin(e3d_reg_t* reg);
+int e3d_reg_scan_colors_add_image(e3d_reg_t* reg, int image_id, const uint8_t* rgb, int width, int height);
+int e3d_reg_scan_colors_get_sums(e3d_reg_t* reg, float* sums, int32_t* counts);
+int e3d_reg_scan_colors_set_sums(e3d_reg_t* reg, const float* sums, const int32_t* counts);
+int e3d_reg_scan_colors_finish(e3d_reg_t* reg, uint8_t* rgb);
 /* Observations cache (src/opt/observations_cache.{h,cc}; Optimizer::set_cache_observations, optimizer.h).  When enabled, the
  * observation update re-projects a fixed per-image list of point indices with the current state and applies only the
  * scale-fit and border tests (VisibilityEstimator::AppendObservationsForIndexedPointsVisibleInImage,
