@@ -465,7 +465,8 @@ def normals_radius(xyz, radius, viewpoint=(0.0, 0.0, 0.0), return_counts=False):
 
 
 def local_outlier_removal(xyz, mean_k, distance_factor_threshold, negative=False, return_distances=False):
-    """pcl::LocalStatisticalOutlierRemoval: bool mask of the points the filter keeps [, first-pass mean neighbour distances]."""
+    """pcl::LocalStatisticalOutlierRemoval: bool mask of the points the filter keeps [, first-pass mean neighbour distances].
+    1 <= mean_k <= 1023; the neighbour lists take n x (mean_k + 1) x 4 bytes of device memory."""
     keep = []
     n = int(xyz.shape[0])
     inl = np.zeros(n, np.uint8)

@@ -1279,6 +1279,138 @@ __global__ __launch_bounds__(64 * kWideWaves) void k_knn_wide_wave(const float4*
   out_c[q_oi] = curv;
 }
 
+// The large-k search (kKnnMaxK < k <= kKnnLargeMaxK; LocalStatisticalOutlierRemoval with hundreds of neighbours): a k-entry list
+// per LANE does not fit the LDS, so here a WAVE shares one query and one list, and a block is that one wave (the waves of a
+// larger block would need barriers inside loops whose trip counts differ per query; with one wave per block the block barrier is
+// the wave's own and the LDS budget per block is the list's alone).
+//   * key = (f32 bits of the squared distance) << 32 | original index: a non-negative f32 orders like its bits, so ONE unsigned
+//     64-bit compare is the (distance, index) order of every other variant, and no two candidates of a query have the same key;
+//   * the lanes evaluate 64 candidates of the 27-cell block per step (kLargeBatch steps' loads in flight); candidates below the
+//     current k-th key are appended to the LDS buffer behind the kept entries, by ballot and lane rank;
+//   * a full buffer (cap = 2 * the power of two at or above k entries) is sorted by a bitonic network in LDS, its best k are kept
+//     and the k-th becomes the threshold -- once it is set only ~k ln(candidates / k) more entries pass;
+//   * a last sort leaves the list ascending: indices written as they lie, the f32 roots go to the free upper half of the buffer
+//     (all lanes) and lane 0 adds them in f64 in list order -- the sums of k_knn_normals' out_mean code.
+// Resolved / unresolved exactly as k_knn_normals with reach 1; the unresolved go to next_todo and the next, coarser level.
+constexpr int kKnnLargeMaxK = 1024;
+constexpr int kLargeBatch = 4;
+constexpr size_t kLargeLdsMax = 2 * (size_t)kKnnLargeMaxK * sizeof(unsigned long long);        // 16 KB at k = 1024
+static_assert((kKnnLargeMaxK & (kKnnLargeMaxK - 1)) == 0, "the sorting network needs a power of two");
+static_assert(kLargeLdsMax * 8 <= 160u * 1024u, "eight one-wave blocks of the largest k must fit a CU's 160 KB of LDS");
+
+// ascending bitonic sort of buf[0, S) by the 64 lanes of a one-wave block (S a power of two >= 64)
+__device__ __forceinline__ void knn_large_sort(unsigned long long* buf, unsigned S, unsigned lane) {
+  for (unsigned size = 2; size <= S; size <<= 1)
+    for (unsigned stride = size >> 1; stride >= 1; stride >>= 1) {
+      for (unsigned t = lane; t < (S >> 1); t += 64) {
+        const unsigned i = ((t & ~(stride - 1u)) << 1) | (t & (stride - 1u));     // t-th index with bit `stride` clear
+        const unsigned j = i | stride;
+        const unsigned long long a = buf[i], b = buf[j];
+        const bool up = (i & size) == 0u;
+        if ((a > b) == up) { buf[i] = b; buf[j] = a; }
+      }
+      __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(64) void k_knn_large(const float4* __restrict__ P4, const unsigned* __restrict__ todo, size_t n_todo,
+                                                  const HashEntry* __restrict__ table, KnnGrid G, int k, unsigned cap,
+                                                  const float4* __restrict__ Q4, int* __restrict__ out_knn, float* __restrict__ out_mean,
+                                                  unsigned* __restrict__ next_todo, unsigned* __restrict__ next_count) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long lbuf[];      // cap keys; cap >= 2 k, a power of two >= 512
+  const unsigned lane = threadIdx.x;
+  const size_t gi = (size_t)blockIdx.y * gridDim.x + blockIdx.x;
+  if (gi >= n_todo) return;                                                      // (the whole block)
+  const unsigned qid = todo ? todo[gi] : (unsigned)gi;
+  const float4 q = Q4[qid];
+  const int cx = cell_coord(q.x, G.g.origin[0], G.g.inv_cell);
+  const int cy = cell_coord(q.y, G.g.origin[1], G.g.inv_cell);
+  const int cz = cell_coord(q.z, G.g.origin[2], G.g.inv_cell);
+  const unsigned long long lt_mask = (1ull << lane) - 1ull;
+  unsigned cnt = 0u;                                                             // entries in the buffer (wave-uniform, like thr)
+  unsigned long long thr = ~0ull;                                                // the k-th key once k are known
+  bool sorted = false;
+  // sort what the buffer holds, keep the best k
+  auto reduce = [&]() {
+    unsigned S = 64u;
+    while (S < cnt) S <<= 1;                                                     // (cnt <= cap, a power of two: S <= cap)
+    for (unsigned i = cnt + lane; i < S; i += 64u) lbuf[i] = ~0ull;
+    __syncthreads();
+    knn_large_sort(lbuf, S, lane);
+    if (cnt >= (unsigned)k) { cnt = (unsigned)k; thr = lbuf[k - 1]; }
+    sorted = true;
+  };
+  auto consider = [&](bool valid, const float4 c) {
+    const unsigned long long key = ((unsigned long long)__float_as_uint(sqdist_l2(q.x, q.y, q.z, c.x, c.y, c.z)) << 32) |
+                                   (unsigned long long)__float_as_uint(c.w);
+    bool take = valid && key < thr;
+    unsigned long long m = __ballot(take);
+    if (m == 0ull) return;
+    unsigned tot = (unsigned)__popcll(m);
+    if (cnt + tot > cap) {                                                       // (then cnt > cap - 64 >= k: the sort leaves k <= cap - 64)
+      reduce();
+      take = valid && key < thr;
+      m = __ballot(take);
+      tot = (unsigned)__popcll(m);
+    }
+    if (take) lbuf[cnt + (unsigned)__popcll(m & lt_mask)] = key;
+    cnt += tot;
+    if (tot) sorted = false;
+  };
+  for (int oz = -1; oz <= 1; ++oz)
+    for (int oy = -1; oy <= 1; ++oy)
+      knn_row(G, table, cx - 1, cx + 1, cy + oy, cz + oz, [&](unsigned m0, unsigned e) {
+        for (unsigned m = m0; m < e; m += 64u * kLargeBatch) {
+          float4 c[kLargeBatch];
+#pragma unroll
+          for (int j = 0; j < kLargeBatch; ++j) { const unsigned p = m + 64u * (unsigned)j + lane; c[j] = P4[p < e ? p : e - 1u]; }
+#pragma unroll
+          for (int j = 0; j < kLargeBatch; ++j)
+            if (m + 64u * (unsigned)j < e) consider(m + 64u * (unsigned)j + lane < e, c[j]);
+        }
+      });
+  if (!sorted) reduce();
+  cnt = min(cnt, (unsigned)k);
+  // resolved?  (as k_knn_normals with reach 1)
+  bool resolved = true;
+  {
+    float safe = 3.402823466e+38f;
+    const int c3[3] = {cx, cy, cz};
+    const float qq[3] = {q.x, q.y, q.z};
+    bool covers_all = true;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const float lo = G.g.origin[a] + (float)(c3[a] - 1) * G.cell;
+      const float hi = G.g.origin[a] + (float)(c3[a] + 2) * G.cell;
+      if (lo > G.dmin[a]) { safe = fminf(safe, qq[a] - lo); covers_all = false; }
+      if (hi <= G.dmax[a]) { safe = fminf(safe, hi - qq[a]); covers_all = false; }
+    }
+    if (!covers_all) {
+      safe -= G.slack;
+      const float kth = cnt ? __uint_as_float((unsigned)(lbuf[cnt - 1u] >> 32)) : 3.402823466e+38f;
+      resolved = (cnt >= (unsigned)k) && safe > 0.f && kth < safe * safe * 0.99999f;
+    }
+  }
+  if (!resolved) {
+    if (lane == 0u) { const unsigned slot = atomicAdd(next_count, 1u); next_todo[slot] = qid; }
+    return;
+  }
+  const unsigned q_oi = __float_as_uint(q.w);
+  float* const roots = reinterpret_cast<float*>(lbuf + (cap >> 1));              // k floats behind the (at most cap / 2) kept keys
+  for (unsigned i = lane; i < (unsigned)k; i += 64u) {
+    const unsigned long long e = i < cnt ? lbuf[i] : 0ull;
+    if (out_knn) out_knn[(size_t)q_oi * (size_t)k + i] = i < cnt ? (int)(unsigned)e : -1;
+    roots[i] = sqrtf(__uint_as_float((unsigned)(e >> 32)));
+  }
+  if (!out_mean) return;
+  __syncthreads();
+  if (lane != 0u) return;
+  // LocalStatisticalOutlierRemoval, first pass: f64 sum of the f32 roots in neighbour order (entry 0 is the query point)
+  double dist_sum = 0.0;
+  for (unsigned i = 1u; i < cnt; ++i) dist_sum += (double)roots[i];
+  out_mean[q_oi] = (float)(dist_sum / (double)(k - 1));
+}
+
 // Radius-search variant (pcl::Feature::searchForNeighbors with setRadiusSearch, two_pass_normal_3d_omp.hpp:66): every
 // point within the radius (FLANN: squared distance strictly below (float)((double)r * r)) takes part; one thread per
 // point walks its 27 grid cells twice -- centroid, then centred products -- so nothing is stored per neighbour and the
@@ -1523,7 +1655,12 @@ static void knn_pass(KnnWorkspace& W, const float* xyz, size_t n, int k, const f
     // (swept at 20 M points of the synthetic room scan, tools/bench_normals.py: the estimate is low in the dense part of a scan,
     // where most points are; with the two-pass variant 1.2 - 1.5 is the optimum for k = 32 and 0.3 - 0.5 for k = 8; E3D_KNN_CELL_FACTOR overrides)
     static const double cell_factor_env = [] { const char* e = getenv("E3D_KNN_CELL_FACTOR"); const double v = e ? atof(e) : 0.0; return v > 0 ? v : 0.0; }();
-    const double cell_factor = cell_factor_env > 0 ? cell_factor_env : (k > 16 ? 1.3 : 0.45);
+    // k > kKnnMaxK (k_knn_large): the k-th neighbour of a surface patch lies sqrt(factor) cells away and the nearest face of the
+    // 27-cell block at least one cell, so below 1 a query of an evenly sampled surface is resolved on its first level; every
+    // retry scans four times the candidates
+    const bool large = k > kKnnMaxK;
+    if (large && (k > kKnnLargeMaxK || want_normals)) throw Error(E3D_ERR_INVALID, fmt("knn_pass: k = %d is beyond the normal estimation's lists", k));
+    const double cell_factor = cell_factor_env > 0 ? cell_factor_env : (large ? 0.6 : (k > 16 ? 1.3 : 0.45));
     double cell = std::sqrt((double)k * area / (cell_factor * M_PI * (double)n));
     cell = std::max(cell, extent / 1.0e6);
     double magnitude = 0;
@@ -1579,9 +1716,15 @@ static void knn_pass(KnnWorkspace& W, const float* xyz, size_t n, int k, const f
     // relative Poisson noise of the count is larger on the low side
     const int rep_target = rep_target_env > 0 ? (int)rep_target_env : std::min((k + cap1) / 2, 2 * k + 6);
     const size_t lds1 = single_variant == 5 ? (size_t)(8 + cap1 / 2) * kKnnBlock * 4 : (size_t)cap1 * kKnnBlock * 4;
+    if (!large) {
     if (single) E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(single_variant)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
     E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(sel)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(sel_list)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_list));
+    }
+    // k_knn_large: a buffer of twice the power of two at or above k keys per query (k <= 1024: at most kLargeLdsMax = 16 KB)
+    unsigned large_cap = 512u;
+    while (large_cap < 2u * (unsigned)k) large_cap <<= 1;
+    const size_t large_lds = (size_t)large_cap * sizeof(unsigned long long);
     DevBuf<unsigned>& fb_todo = W.fb_todo;
     if (sel == 3) { fb_todo.reserve(n); L.counter.reserve(4); }
     static const double level_step = [] { const char* e = getenv("E3D_KNN_LEVEL_STEP"); const double v = e ? atof(e) : 0.0; return v > 1 ? v : 2.0; }();   // cell growth per retry level (4 -> 2: -7 % at k = 32)
@@ -1666,6 +1809,19 @@ static void knn_pass(KnnWorkspace& W, const float* xyz, size_t n, int k, const f
     auto search_level = [&](LevelBuffers& LB, const KnnGrid& G, const unsigned* todo_list, size_t n_list, unsigned* next_list,
                             unsigned& n_next_out, bool merge_fb_into_next, unsigned* single_list) {
       E3D_HIP(hipMemsetAsync(LB.counter.p + 1, 0, 3 * sizeof(unsigned), s));
+      if (large) {
+        // one wave, one block per query; what it cannot resolve on this grid is all there is to hand on
+        if (large_lds > kLargeLdsMax) throw Error(E3D_ERR_INVALID, "knn_pass: list buffer beyond the LDS budget");
+        const unsigned gx = (unsigned)std::min(n_list, (size_t)1 << 20), gy = (unsigned)div_up(n_list, (size_t)std::max(gx, 1u));
+        if (n_list > 0)
+          hipLaunchKernelGGL(k_knn_large, dim3(gx, gy), dim3(64), large_lds, s, LB.P4.p, todo_list, n_list, LB.table.p, G, k, large_cap, Q4.p,
+                             knn_indices ? d_knn.p : nullptr, d_mean_out ? d_mean_out->p : nullptr, next_list, LB.counter.p + 1);
+        unsigned n_left = 0;
+        W.read_back(&n_left, LB.counter.p + 1, sizeof(unsigned));
+        E3D_HIP(hipGetLastError());
+        n_next_out = n_left;
+        return 0u;
+      }
       if (seed_cap) E3D_HIP(hipMemsetAsync(seed_flag_p, 0, seed_cap, s));
       const int lsel = (sel == 3 && !G.S) ? sel_list : sel;            // the two-pass variant needs the dense directory
       if (lsel == 3 && single && todo_list == nullptr && n_list == n && single_list != nullptr) {
@@ -1748,7 +1904,7 @@ static void knn_pass(KnnWorkspace& W, const float* xyz, size_t n, int k, const f
       // build for ~1 % of the queries
       // (a long list is cheaper on a grid of twice the cell size with the two-pass kernels: the list-maintaining variant over 125 cells
       // took 20 ms for the 2 M far-field queries of a scanner-sampled scan, a grid build is 1.7 ms)
-      if (n_next > 0 && wide_pass && (size_t)n_next * 64 <= n) {
+      if (n_next > 0 && wide_pass && !large && (size_t)n_next * 64 <= n) {
         unsigned* wide_out = (next == todo_a.p) ? todo_b.p : todo_a.p;
         unsigned cw[1] = {0};
         E3D_HIP(hipMemsetAsync(L.counter.p + 1, 0, sizeof(unsigned), s));
@@ -1910,7 +2066,7 @@ extern "C" int e3d_local_outlier_removal(const float* xyz, size_t n, int mean_k,
                                          uint8_t* inlier, float* mean_distances) {
   try {
     if ((!xyz && n) || (!inlier && n)) throw Error(E3D_ERR_INVALID, "e3d_local_outlier_removal: null argument");
-    if (mean_k < 1 || mean_k + 1 > kKnnMaxK) throw Error(E3D_ERR_INVALID, fmt("e3d_local_outlier_removal: mean_k = %d outside [1, %d]", mean_k, kKnnMaxK - 1));
+    if (mean_k < 1 || mean_k > kKnnLargeMaxK - 1) throw Error(E3D_ERR_INVALID, fmt("e3d_local_outlier_removal: mean_k = %d outside [1, %d]", mean_k, kKnnLargeMaxK - 1));
     if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_local_outlier_removal: more than 2^31-1 points");
     require_device();
     if (n == 0) return 0;
