@@ -42,6 +42,19 @@ inline std::string fmt(const char* f, ...) {
   return std::string(buf);
 }
 
+// Environment switches: a number (the default when unset); on unless the value starts with '0'; off unless it starts with '1'
+inline double env_double(const char* name, double dflt) { const char* e = getenv(name); return e ? atof(e) : dflt; }
+inline int env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
+inline bool env_default_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
+inline bool env_default_off(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
+
+// The C-ABI's error convention: an e3d::Error returns its code, any other exception E3D_ERR_INVALID (include/e3d_hip.h), and
+// e3d_last_error() has the text
+#define E3D_TRY try {
+#define E3D_CATCH()                                                                         \
+  } catch (const e3d::Error& e) { e3d::set_last_error(e.what()); return e.code; }           \
+  catch (const std::exception& e) { e3d::set_last_error(e.what()); return E3D_ERR_INVALID; }
+
 #define E3D_HIP(expr)                                                                     \
   do {                                                                                    \
     hipError_t e3d_err__ = (expr);                                                        \

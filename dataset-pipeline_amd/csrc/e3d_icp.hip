@@ -36,14 +36,6 @@ static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 const char* last_error_cstr() { return g_last_error.c_str(); }
 
-// environment switches of this file: a number; on unless the value starts with '0'; off unless it starts with '1'
-static double env_double(const char* name, double dflt) {
-  const char* e = getenv(name);
-  return e ? atof(e) : dflt;
-}
-static bool env_default_on(const char* name) { const char* e = getenv(name); return !(e && e[0] == '0'); }
-static bool env_default_off(const char* name) { const char* e = getenv(name); return e && e[0] == '1'; }
-
 static int g_device = 0;
 // E3D_NN_MODE / e3d_set_nn_mode: 0 auto, 1 per-query, 2 hash-table buckets, 3 dense rows, 4 dense rows + MFMA filter,
 // 5 dense rows with the half-cell directory of the bounded search built whatever the density and used for every list (tests)
@@ -2041,11 +2033,6 @@ static bool align_meshes(e3d_icp* h, float max_d, float thr, bool print, int ite
 // =================================================================================================
 // C-ABI
 // =================================================================================================
-#define E3D_TRY try {
-#define E3D_CATCH()                                                                         \
-  } catch (const e3d::Error& e) { e3d::set_last_error(e.what()); return e.code; }           \
-  catch (const std::exception& e) { e3d::set_last_error(e.what()); return E3D_ERR_INVALID; }
-
 extern "C" {
 
 int e3d_abi_version(void) { return E3D_ABI_VERSION; }

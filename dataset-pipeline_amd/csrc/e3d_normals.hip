@@ -1490,6 +1490,43 @@ __global__ __launch_bounds__(kKnnBlock) void k_radius_normals(const float4* __re
   if (out_count) out_count[q_oi] = cnt;
 }
 
+// The environment switches of the kNN pass (knn_pass, KnnWorkspace::read_back), read once per process.  They are for experiments and
+// A / B timing: the search is exact under every setting.  What a pass makes of them for its k and n: make_knn_plan.
+struct KnnSwitches {
+  static double above(double v, double bound, double dflt) { return v > bound ? v : dflt; }
+  // the factor of the starting cell size (0: by k).  Swept at 20 M points of the synthetic room scan (tools/bench_normals.py): the
+  // area estimate is low in the dense part of a scan, where most points are; with the two-pass variant 1.2 - 1.5 is the optimum
+  // for k = 32 and 0.3 - 0.5 for k = 8
+  double cell_factor = above(env_double("E3D_KNN_CELL_FACTOR", 0.0), 0.0, 0.0);
+  int select = env_int("E3D_KNN_SELECT", -1);          // experiments: 0 heap, 1 flat, 2 grouped, 3 two-pass, where the variant can serve k (-1: by k)
+  // spare list slots of the two-pass variant (-1: by k).  It serves the single scan's leftovers, so its occupancy matters little:
+  // with 4 a fifth of a scanner-sampled scan's leftovers overflowed into the list-maintaining variant (20 M points, scanner-sampled:
+  // k = 32 18.8 -> 17.5 ms with 20, k = 8 11.3 -> 11.0 with 12; uniform scan unchanged; profiles/round5_normals_cap_extra.txt)
+  int cap_extra = env_int("E3D_KNN_CAP_EXTRA", -1);
+  int single = env_int("E3D_KNN_SINGLE", 1);           // 0: no single-pass variant, every query takes the two passes
+  int cap1 = env_int("E3D_KNN_CAP1", 0);               // list slots of single-pass variant 4 (k + 9 .. 36; else 32)
+  // the single-pass variant's sampling: one query in how many is sampled (0: 8), how many samples a query averages (1, 2 or 4; else 2)
+  // and the candidate count the threshold aims at (0: by k and capacity)
+  int rep_stride = env_int("E3D_KNN_REP_STRIDE", 0), rep_avg = env_int("E3D_KNN_REP_AVG", 0);
+  double rep_target = env_double("E3D_KNN_REP_TARGET", 0.0);
+  // where the sampled thresholds come from: up to this k the block population of the sampled query alone (k_knn_hist's `estimate`,
+  // the default with a dense directory: the sampling kernel touches no candidate, 0.51 -> 0.1 ms at 20 M points; 5.70 -> 5.33 ms at
+  // k = 8, 8.38 -> 7.98 at k = 32, scanner-sampled 17.5 -> 16.8 / 11.2 -> 10.6), beyond it (0: always) its distance histogram.  The
+  // scale widens the estimate: 1.05 measured best between 0.8 and 1.25.
+  int est = env_int("E3D_KNN_EST", 64);
+  float est_scale = (float)above(env_double("E3D_KNN_EST_SCALE", 1.05), 0.0, 1.05);
+  double level_step = above(env_double("E3D_KNN_LEVEL_STEP", 0.0), 1.0, 2.0);   // cell growth per retry level (4 -> 2: -7 % at k = 32)
+  bool wide = env_int("E3D_KNN_WIDE", 1) != 0;             // 0: no 125-cell pass, unresolved queries wait for the next, coarser level
+  bool seed = env_int("E3D_KNN_SEED", 1) != 0;             // 0: its lane-per-query form starts without the k nearest of the 27 cells
+  bool wide_wave = env_int("E3D_KNN_WIDE_WAVE", 1) != 0;   // 0: lane per query whatever k (default: wave per query for k <= 64)
+  int wide_spread = [] { const int v = env_int("E3D_KNN_WIDE_SPREAD", 0); return v >= 1 && v <= 64 ? v : 4; }();   // lanes per query of the lane-per-query form
+  int dense_log2 = std::min(env_int("E3D_KNN_DENSE_LOG2", 30), 31);   // a level whose bounding grid has more than 2^this cells takes the hash table
+  unsigned xcd = (unsigned)std::min(std::max(env_int("E3D_KNN_XCD", 64), 0), 4096);   // KnnGrid::xcd_map (knn_block; 0: off)
+  bool pinned = env_default_on("E3D_KNN_PINNED");      // 0: read-backs through pageable memory (as rounds 1 - 5, for A / B timing)
+};
+static const KnnSwitches& knn_switches() { static const KnnSwitches sw; return sw; }
+static bool knn_stats() { return getenv("E3D_KNN_STATS") != nullptr; }   // a line per phase on stderr; looked up at each use
+
 // grid keys for an arbitrary cell size (points taken from AoS xyz)
 struct LevelBuffers {
   DevBuf<unsigned long long> ka, kb;
@@ -1501,7 +1538,6 @@ struct LevelBuffers {
   DevBuf<unsigned> coarse;         // its coarse form (one word per 4096 cells), from which the directory is written
   DevBuf<unsigned char> sel_bin;   // pass A results of the two-pass variant: the selected bin per query
 };
-
 
 // Device buffers of one kNN call.  A 20 M point call touches ~5 GB in ~20 buffers; allocating and freeing them costs several
 // milliseconds per call (hipMalloc maps pages, hipFree synchronises the device), so finished calls park their workspace in a
@@ -1521,8 +1557,7 @@ struct KnnWorkspace {
   PinBuf<unsigned> mailbox;            // the few words a call reads back (bounding box, list lengths): pinned, not the pageable staging path
   // a few words back from the device and the stream synchronised
   void read_back(void* dst, const void* src_dev, size_t bytes) {
-    static const bool pinned = [] { const char* e = getenv("E3D_KNN_PINNED"); return !(e && e[0] == '0'); }();     // (0: as rounds 1 - 5, for A / B timing)
-    if (!pinned) { E3D_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, stream)); E3D_HIP(hipStreamSynchronize(stream)); return; }
+    if (!knn_switches().pinned) { E3D_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDeviceToHost, stream)); E3D_HIP(hipStreamSynchronize(stream)); return; }
     mailbox.reserve(64);
     E3D_HIP(hipMemcpyAsync(mailbox.p, src_dev, bytes, hipMemcpyDeviceToHost, stream));
     E3D_HIP(hipStreamSynchronize(stream));
@@ -1559,7 +1594,7 @@ struct WorkspaceLease {
   }
   ~WorkspaceLease() {
     if (!ws) return;
-    static const double keep_gb = [] { const char* e = getenv("E3D_WORKSPACE_KEEP_GB"); return e ? atof(e) : 32.0; }();
+    static const double keep_gb = env_double("E3D_WORKSPACE_KEEP_GB", 32.0);
     if ((double)ws->bytes() > keep_gb * 1073741824.0) { delete ws; return; }
     std::lock_guard<std::mutex> lock(workspace_mutex());
     workspace_pool().push_back(ws);
@@ -1612,8 +1647,308 @@ __global__ __launch_bounds__(256) void k_knn_kth(const float* __restrict__ xyz, 
   kth[i] = j < 0 ? INFINITY : sqdist_l2(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2]);
 }
 
-// The exact kNN pass over a host cloud.  Results stay on the device: normals + curvature (if want_normals), the neighbour
-// index lists (if d_knn) and the mean neighbour distance (if d_mean), all in input order.
+// What a kNN pass runs for its k and n: kernel variants, list capacities, LDS bytes, sampling.  A function of its arguments and the
+// switches alone (no HIP call).
+struct KnnPlan {
+  bool large;                              // k > kKnnMaxK: k_knn_large (one wave per query) on every level
+  double cell_factor;                      // factor of the starting cell size
+  int sel, sel_list, cap;                  // k_knn_normals variants: the main one, the list-maintaining one (also variant 3's fallback); list slots per thread of `sel`
+  size_t lds, lds_list;                    // dynamic LDS bytes of `sel` and of `sel_list`
+  bool single;                             // level 0 starts with the single-pass variant
+  int single_variant, cap1;                // the single-pass variant (4 or 5) and its list slots per thread
+  size_t lds1;                             // dynamic LDS bytes of the single-pass variant
+  int rep_stride, rep_avg;                 // single-pass sampling: one query in rep_stride is sampled, a query averages rep_avg samples
+  int rep_target;                          // candidate count that k_knn_hist aims the sampled thresholds at
+  bool rep_estimate; float rep_est_scale;  // sampled thresholds from the block population (k_knn_hist's `estimate`, widened by the scale), not the distance histogram
+  unsigned large_cap; size_t large_lds;    // k_knn_large: keys per query in LDS, and their bytes
+  bool wave_per_query;                     // the 125-cell pass starts with k_knn_wide_wave
+  unsigned seed_cap;                       // longest list whose queries leave seeds for the lane-per-query 125-cell pass (0: none)
+};
+
+static KnnPlan make_knn_plan(int k, size_t n, bool want_normals, const KnnSwitches& sw) {
+  KnnPlan P{};
+  P.large = k > kKnnMaxK;
+  if (P.large && (k > kKnnLargeMaxK || want_normals)) throw Error(E3D_ERR_INVALID, fmt("knn_pass: k = %d is beyond the normal estimation's lists", k));
+  // k > kKnnMaxK (k_knn_large): the k-th neighbour of a surface patch lies sqrt(factor) cells away and the nearest face of the
+  // 27-cell block at least one cell, so below 1 a query of an evenly sampled surface is resolved on its first level; every
+  // retry scans four times the candidates
+  P.cell_factor = sw.cell_factor > 0 ? sw.cell_factor : (P.large ? 0.6 : (k > 16 ? 1.3 : 0.45));
+  P.sel_list = k <= 16 ? 1 : (k <= 32 ? 2 : 0);
+  constexpr int kTwoPassMaxK = 60;                                        // k + 4 list slots <= the largest sorting network (64)
+  const int forced = sw.select;                                           // (a variant is forced only where it can serve k)
+  P.sel = (forced >= 0 && forced <= 3 && (forced < 2 || (forced == 2 && k <= 32) || (forced == 3 && k <= kTwoPassMaxK))) ? forced : (k <= kTwoPassMaxK ? 3 : 0);
+  // spare list slots of the two-pass variant (KnnSwitches::cap_extra; k > 32: the two-pass variant is the main kernel there, its
+  // LDS list decides the occupancy: 4 as before)
+  const int cap_extra = sw.cap_extra >= 0 ? sw.cap_extra : (k <= 16 ? 12 : (k <= 32 ? 20 : 4));
+  P.cap = P.sel == 3 ? std::min(((std::max(k + cap_extra, 12) + 1) & ~1), 64) : k;
+  P.lds = P.sel == 3 ? (size_t)P.cap * kKnnBlock * 4 : (size_t)P.cap * kKnnBlock * 8;
+  P.lds_list = (size_t)k * kKnnBlock * 8;
+  // the single-pass variant (see k_knn_normals): sampled thresholds, level 0 only; its leftovers take the two-pass variant
+  constexpr int kSinglePassMaxK = kKnnTagSlots / 2;                        // variant 5 hands back k positions in its cap / 2 dwords
+  P.single = P.sel == 3 && sw.single != 0 && k <= kSinglePassMaxK && k >= 3;
+  // small k: 32-bit [key | tag] entries (variant 4, 36 slots: the occupancy of the two-pass variant at k = 32); beyond that
+  // the 64 slots would leave 10 waves per CU, so the list holds 16-bit tags and the keys are computed afterwards (variant 5)
+  P.single_variant = k <= 10 ? 4 : 5;
+  // (32: 16 KB of LDS per block, five waves per SIMD with variant 4's 86 registers)
+  P.cap1 = P.single_variant == 5 ? kKnnTagSlots : ((sw.cap1 >= k + 9 && sw.cap1 <= 36) ? sw.cap1 : 32);
+  P.lds1 = P.single_variant == 5 ? (size_t)(8 + P.cap1 / 2) * kKnnBlock * 4 : (size_t)P.cap1 * kKnnBlock * 4;
+  P.rep_stride = sw.rep_stride > 0 ? sw.rep_stride : 8;
+  P.rep_avg = (sw.rep_avg == 1 || sw.rep_avg == 2 || sw.rep_avg == 4) ? sw.rep_avg : 2;
+  P.rep_estimate = sw.est != 0 && k <= sw.est;
+  P.rep_est_scale = sw.est_scale;
+  // the count the threshold aims at: the middle of [k, capacity] (k = 32: 48 of 64), a little below it for small k where the
+  // relative Poisson noise of the count is larger on the low side
+  P.rep_target = sw.rep_target > 0 ? (int)sw.rep_target : std::min((k + P.cap1) / 2, 2 * k + 6);
+  // k_knn_large: a buffer of twice the power of two at or above k keys per query (k <= 1024: at most kLargeLdsMax = 16 KB)
+  P.large_cap = 512u;
+  while (P.large_cap < 2u * (unsigned)k) P.large_cap <<= 1;
+  P.large_lds = (size_t)P.large_cap * sizeof(unsigned long long);
+  if (P.large && P.large_lds > kLargeLdsMax) throw Error(E3D_ERR_INVALID, "knn_pass: list buffer beyond the LDS budget");
+  // seeds of the 125-cell pass (it takes lists of at most n / 64 queries).  Only the lane-per-query wide pass reads them: with the
+  // wave-per-query pass -- the default for k <= 64 -- nothing would, and the scan kernels would write k positions per unresolved
+  // query plus a memset per level for nothing
+  P.wave_per_query = sw.wide_wave && P.sel == 3 && k <= 64;
+  P.seed_cap = (sw.wide && sw.seed && P.sel == 3 && !P.wave_per_query) ? (unsigned)(n / 64 + 1) : 0u;
+  return P;
+}
+
+static auto knn_normals_kernel(int v) {
+  return v == 0 ? k_knn_normals<0> : (v == 1 ? k_knn_normals<1> : (v == 2 ? k_knn_normals<2> : (v == 3 ? k_knn_normals<3> : (v == 4 ? k_knn_normals<4> : k_knn_normals<5>))));
+}
+
+// Grid of cell size `cell_size` over the bounding box: two cells of margin below the minimum.  No directory yet, slack and xcd_map 0.
+static KnnGrid knn_grid_over(const float bb[6], double cell_size) {
+  KnnGrid G{};
+  G.cell = (float)cell_size;
+  G.g.inv_cell = (float)(1.0 / (double)G.cell);
+  for (int a = 0; a < 3; ++a) { G.g.origin[a] = (float)((double)bb[a] - 2.0 * cell_size); G.dmin[a] = bb[a]; G.dmax[a] = bb[3 + a]; }
+  return G;
+}
+
+// The hash-table form of G over the n points of `xyz` (AoS, on the device): the points in cell order into LB.P4 (w = input index
+// as bits), the occupied cells into LB.table, G.g.mask set.  The caller has reserved LB.ka, kb, va, vb, counter and P4.
+static void build_hash_grid(const float* xyz, size_t n, LevelBuffers& LB, KnnGrid& G, hipStream_t s) {
+  launch_cell_keys(xyz, n, G.g, LB.ka.p, LB.va.p, s);
+  sort_pairs_u64_u32(LB.ka.p, LB.kb.p, LB.va.p, LB.vb.p, n, 63, LB.temp, s);
+  launch_permute(xyz, nullptr, LB.vb.p, n, LB.P4.p, nullptr, s);
+  E3D_HIP(hipMemsetAsync(LB.counter.p, 0, 2 * sizeof(unsigned), s));
+  launch_count_cells(LB.kb.p, n, LB.counter.p, s);
+  unsigned n_cells = 0;
+  E3D_HIP(hipMemcpyAsync(&n_cells, LB.counter.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+  E3D_HIP(hipStreamSynchronize(s));
+  size_t tsize = 64;
+  while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
+  LB.table.reserve(tsize);
+  G.g.mask = (unsigned)(tsize - 1);
+  E3D_HIP(hipMemsetAsync(LB.table.p, 0xFF, sizeof(HashEntry) * tsize, s));
+  launch_build_table(LB.kb.p, n, LB.table.p, G.g.mask, s);
+}
+
+// The arguments of k_knn_normals that most launches leave alone
+struct KnnNormalsExtra {
+  unsigned *fb_todo = nullptr, *fb_count = nullptr;   // variants 3 to 5: the queries the kernel could not settle, and their count
+  const unsigned char* sel_bins = nullptr;            // variants 3 to 5: k_knn_hist's results
+  int reach = 1, rep_stride = 1, rep_avg = 1;         // (reach 2: rep_stride is the lanes per query)
+  bool seeded = false;                                // the run's seed buffers are passed, not nullptr
+  unsigned seed_cap = 0;
+};
+
+// One kNN pass (knn_pass): what its three phases share, then build_level, search_level and wide_level.
+struct KnnRun {
+  KnnWorkspace& W;                                                   // buffers (W.L: those of the level) and stream
+  const KnnSwitches& sw;
+  const KnnPlan& P;
+  size_t n; int k; const float* viewpoint;
+  const float* xyz = nullptr;                                        // the cloud on the device (AoS)
+  float *out_n = nullptr, *out_c = nullptr, *out_mean = nullptr;     // results in input order (nullptr: not wanted)
+  int* out_knn = nullptr;
+  unsigned* seed_pos = nullptr;                                      // P.seed_cap seeds (nullptr: none)
+  unsigned char* seed_flag = nullptr;
+  float bb[6] = {};                                                  // bounding box of the cloud,
+  double extent = 0, magnitude = 0;                                  // its largest side and largest coordinate
+  // queries in level-0 cell order (spatially coherent for every level): level 0's sorted points themselves; a further level sorts
+  // into the other buffer (the two are swapped then)
+  const float4* Q4 = nullptr;
+
+  // k_knn_normals<variant> on the level in W.L: the listed queries (list == nullptr: all), a lane each (reach 2: x.rep_stride lanes),
+  // with `cap` list slots in `lds` bytes of LDS; the unresolved ones are appended to `next` (device counter W.L.counter[1])
+  void launch_knn_normals(int variant, const KnnGrid& G, const unsigned* list, size_t n_list, int cap, size_t lds, unsigned* next,
+                          const KnnNormalsExtra& x = {}) const {
+    const size_t lanes = n_list * (size_t)(x.reach == 2 ? x.rep_stride : 1);
+    hipLaunchKernelGGL(knn_normals_kernel(variant), dim3((unsigned)div_up(lanes, kKnnBlock)), dim3(kKnnBlock), lds, W.stream, W.L.P4.p, n, list, n_list, W.L.table.p, G, k, cap,
+                       viewpoint[0], viewpoint[1], viewpoint[2], Q4, out_n, out_c, out_knn, out_mean, next, W.L.counter.p + 1,
+                       x.fb_todo, x.fb_count, x.sel_bins, x.reach, x.rep_stride, x.rep_avg, 1.0f,
+                       x.seeded ? seed_pos : nullptr, x.seeded ? seed_flag : nullptr, x.seed_cap);
+  }
+
+  // Grid of cell size `cell_size` over all points into W.L: sorted points, dense directory when the bounding grid has at most
+  // 2^sw.dense_log2 cells (else the hash table); false if the extent does not fit 21-bit cell coordinates.
+  bool build_level(double cell_size, KnnGrid& G) {
+    G = knn_grid_over(bb, cell_size);
+    G.xcd_map = sw.xcd;
+    G.slack = (float)(16.0 * FLT_EPSILON * (magnitude + 4.0 * cell_size) + 1e-4 * cell_size);
+    if (extent / cell_size > (double)((1 << 21) - 8)) return false;
+    W.L.ka.reserve(n); W.L.kb.reserve(n); W.L.va.reserve(n); W.L.vb.reserve(n); W.L.counter.reserve(4); W.L.P4.reserve(n + 8);   // (+ 8: the scan kernels read whole batches)
+    // dense directory over the bounding grid (cells 0 .. cell of the bbox maximum + 2 per axis) unless it would be huge.  With it
+    // the sort key is the 32-bit linear cell index (same (z, y, x) order as the 63-bit key: 4 radix passes instead of 8).
+    QueryRange qr{};
+    double prod = 1.0;
+    for (int a = 0; a < 3; ++a) {
+      qr.lo[a] = 0;
+      const double cmax = std::floor(((double)bb[3 + a] - (double)G.g.origin[a]) * (double)G.g.inv_cell);
+      qr.D[a] = (unsigned)std::max(1.0, std::min(cmax + 4.0, 2097152.0));
+      prod *= (double)qr.D[a];
+    }
+    if (prod > (double)((size_t)1 << sw.dense_log2)) {
+      build_hash_grid(xyz, n, W.L, G, W.stream);   // no dense directory (the bounding grid is too large): hash table of the occupied cells
+      return true;
+    }
+    const size_t ncell = (size_t)prod;
+    int bits = 1;
+    while (((size_t)1 << bits) < ncell) ++bits;
+    unsigned* k32_in = reinterpret_cast<unsigned*>(W.L.ka.p);
+    unsigned* k32_out = reinterpret_cast<unsigned*>(W.L.kb.p);
+    hipLaunchKernelGGL(k_cell_keys_dense, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, W.stream, xyz, n, G.g, qr.D[0], qr.D[1], qr.D[2], k32_in, W.L.va.p);
+    sort_pairs_u32_u32(k32_in, k32_out, W.L.va.p, W.L.vb.p, n, bits, W.L.temp, W.stream);
+    launch_permute(xyz, nullptr, W.L.vb.p, n, W.L.P4.p, nullptr, W.stream);
+    W.L.dense.reserve(ncell + 2);
+    const size_t n_tiles = div_up(ncell + 2, (size_t)kDirTile);
+    const size_t n_words = n_tiles * (kDirTile / 32);                 // one bit per cell, whole tiles
+    W.L.coarse.reserve(n_tiles + 1 + n_words);
+    unsigned* const occupied = W.L.coarse.p + n_tiles + 1;
+    E3D_HIP(hipMemsetAsync(W.L.coarse.p, 0, sizeof(unsigned) * (n_tiles + 1 + n_words), W.stream));
+    hipLaunchKernelGGL(k_dir_mark, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, W.stream, k32_out, n, W.L.coarse.p, W.L.dense.p, occupied);
+    exclusive_max_scan_u32(W.L.coarse.p, n_tiles + 1, W.L.temp, W.stream);
+    hipLaunchKernelGGL(k_dense_directory, dim3((unsigned)n_tiles), dim3(256), 0, W.stream, k32_out, occupied, W.L.coarse.p, W.L.dense.p, ncell + 2);
+    G.S = W.L.dense.p;
+    for (int a = 0; a < 3; ++a) G.D[a] = qr.D[a];
+    return true;
+  }
+
+  // One search of the listed queries (todo_list == nullptr: all) on the built level.  Results of resolved queries are written; the
+  // others are appended to `next_list` (device counter W.L.counter[1]: k-th neighbour beyond the 27 cells).  Fallback queries of
+  // the two-pass variant (W.L.counter[2]) join that list when a wide pass follows (sw.wide) or run through the list-maintaining
+  // variant on the same grid right away.  single_list: room for the single-pass variant's leftovers (nullptr: it does not run).
+  // n_next_out: length of next_list; returns the number of fallback queries.
+  unsigned search_level(const KnnGrid& G, const unsigned* todo_list, size_t n_list, unsigned* next_list, unsigned& n_next_out,
+                        unsigned* single_list) {
+    unsigned* const next_count = W.L.counter.p + 1;
+    E3D_HIP(hipMemsetAsync(next_count, 0, 3 * sizeof(unsigned), W.stream));
+    if (P.large) {
+      // one wave, one block per query; what it cannot resolve on this grid is all there is to hand on
+      const unsigned gx = (unsigned)std::min(n_list, (size_t)1 << 20), gy = (unsigned)div_up(n_list, (size_t)std::max(gx, 1u));
+      if (n_list > 0)
+        hipLaunchKernelGGL(k_knn_large, dim3(gx, gy), dim3(64), P.large_lds, W.stream, W.L.P4.p, todo_list, n_list, W.L.table.p, G, k, P.large_cap, Q4,
+                           out_knn, out_mean, next_list, next_count);
+      W.read_back(&n_next_out, next_count, sizeof(unsigned));
+      E3D_HIP(hipGetLastError());
+      return 0u;
+    }
+    if (P.seed_cap) E3D_HIP(hipMemsetAsync(seed_flag, 0, P.seed_cap, W.stream));
+    const int lsel = (P.sel == 3 && !G.S) ? P.sel_list : P.sel;            // the two-pass variant needs the dense directory
+    if (lsel == 3 && P.single && todo_list == nullptr && n_list == n && single_list != nullptr) {
+      // single pass over all queries with sampled thresholds; those whose count missed the window are listed in single_list and
+      // take the two passes below (the next-level list keeps growing: same counter)
+      const size_t n_reps = div_up(n_list, (size_t)P.rep_stride);
+      W.L.sel_bin.reserve(n_list);
+      hipLaunchKernelGGL(k_knn_hist, dim3((unsigned)div_up(n_reps, kKnnHistBlock)), dim3(kKnnHistBlock), 0, W.stream, W.L.P4.p, (const unsigned*)nullptr, n_reps,
+                         W.L.table.p, G, P.rep_target, Q4, W.L.sel_bin.p, (unsigned)P.rep_stride, (P.rep_estimate && G.S) ? P.rep_est_scale : 0.f);
+      KnnNormalsExtra x;
+      x.fb_todo = single_list; x.fb_count = W.L.counter.p + 3; x.sel_bins = W.L.sel_bin.p;
+      x.rep_stride = P.rep_stride; x.rep_avg = P.rep_avg;
+      x.seeded = true; x.seed_cap = P.seed_cap;
+      launch_knn_normals(P.single_variant, G, nullptr, n_list, P.cap1, P.lds1, next_list, x);
+      unsigned n_single_fb = 0;
+      W.read_back(&n_single_fb, W.L.counter.p + 3, sizeof(unsigned));
+      E3D_HIP(hipGetLastError());
+      if (knn_stats()) fprintf(stderr, "[knn] single pass (variant %d): %zu queries, target %d of %d slots, %u to the two-pass variant\n", P.single_variant, n_list, P.rep_target, P.cap1, n_single_fb);
+      todo_list = single_list;
+      n_list = n_single_fb;
+    }
+    if (lsel == 3 && n_list > 0) {
+      W.L.sel_bin.reserve(n_list);
+      hipLaunchKernelGGL(k_knn_hist, dim3((unsigned)div_up(n_list, kKnnHistBlock)), dim3(kKnnHistBlock), 0, W.stream, W.L.P4.p, todo_list, n_list,
+                         W.L.table.p, G, k, Q4, W.L.sel_bin.p, 1u, 0.f);
+    }
+    if (n_list > 0) {
+      KnnNormalsExtra x;
+      x.fb_todo = W.fb_todo.p; x.fb_count = W.L.counter.p + 2; x.sel_bins = W.L.sel_bin.p;
+      x.seeded = lsel == 3; x.seed_cap = P.seed_cap;
+      launch_knn_normals(lsel, G, todo_list, n_list, lsel == 3 ? P.cap : k, lsel == 3 ? P.lds : P.lds_list, next_list, x);
+    }
+    unsigned cnts[2] = {0, 0};
+    W.read_back(cnts, next_count, 2 * sizeof(unsigned));
+    E3D_HIP(hipGetLastError());
+    const unsigned n_fb = cnts[1];
+    if (sw.wide && n_fb > 0 && ((size_t)cnts[0] + n_fb) * 64 <= n) {
+      // the two-pass variant's leftovers join the wide pass that follows (its first 27 cells are this level's block, the shell
+      // beyond them is skipped by the face test once the list is full): one launch instead of two
+      E3D_HIP(hipMemcpyAsync(next_list + cnts[0], W.fb_todo.p, sizeof(unsigned) * n_fb, hipMemcpyDeviceToDevice, W.stream));
+      cnts[0] += n_fb;
+    } else if (n_fb > 0) {
+      // queries the two-pass variant could not settle on this level (see its comment): the list-maintaining variant, same
+      // grid, appending its unresolved ones to the same next-level list
+      launch_knn_normals(P.sel_list, G, W.fb_todo.p, (size_t)n_fb, k, P.lds_list, next_list);
+      W.read_back(cnts, next_count, sizeof(unsigned));
+      E3D_HIP(hipGetLastError());
+    }
+    n_next_out = cnts[0];
+    return n_fb;
+  }
+
+  // The wide pass over a short list: the few that need a wider look (the k-th neighbour lies outside the 27 cells: sparse regions,
+  // outliers) take the list-maintaining variant over the 125 cells of the same grid, which reaches as far as a grid of twice the
+  // cell size would -- no second grid build for ~1 % of the queries.  (A long list is cheaper on a grid of twice the cell size with
+  // the two-pass kernels: the list-maintaining variant over 125 cells took 20 ms for the 2 M far-field queries of a scanner-sampled
+  // scan, a grid build is 1.7 ms.)  What is still unresolved is appended to wide_out; returns its length.
+  unsigned wide_level(const KnnGrid& G, int level, const unsigned* list, unsigned n_list, unsigned* wide_out) {
+    unsigned* const out_count = W.L.counter.p + 1;
+    E3D_HIP(hipMemsetAsync(out_count, 0, sizeof(unsigned), W.stream));
+    auto lane_per_query = [&](const unsigned* q, size_t n_q, bool seeded) {
+      KnnNormalsExtra x;
+      x.reach = 2; x.rep_stride = sw.wide_spread;
+      x.seeded = seeded; x.seed_cap = P.seed_cap;
+      launch_knn_normals(P.sel_list, G, q, n_q, k, P.lds_list, wide_out, x);
+    };
+    if (P.wave_per_query && G.S) {
+      // one wave per query (k_knn_wide_wave); what it hands back (more candidates than its lanes hold, long tie runs) takes the
+      // lane-per-query kernel
+      E3D_HIP(hipMemsetAsync(W.L.counter.p + 2, 0, sizeof(unsigned), W.stream));
+      hipLaunchKernelGGL(k_knn_wide_wave, dim3((unsigned)div_up((size_t)n_list, (size_t)kWideWaves)), dim3(64 * kWideWaves), 0, W.stream, W.L.P4.p, list, (size_t)n_list, G, k,
+                         viewpoint[0], viewpoint[1], viewpoint[2], Q4, out_n, out_c, out_knn, out_mean, wide_out, out_count, W.fb_todo.p, W.L.counter.p + 2);
+      unsigned n_back = 0;
+      W.read_back(&n_back, W.L.counter.p + 2, sizeof(unsigned));
+      E3D_HIP(hipGetLastError());
+      if (knn_stats()) fprintf(stderr, "[knn] level %d wave-per-query pass: %u queries, %u handed to the lane-per-query kernel\n", level, n_list, n_back);
+      if (n_back > 0) lane_per_query(W.fb_todo.p, (size_t)n_back, false);
+    } else {
+      lane_per_query(list, (size_t)n_list, true);
+    }
+    unsigned n_out = 0;
+    W.read_back(&n_out, out_count, sizeof(unsigned));
+    E3D_HIP(hipGetLastError());
+    if (knn_stats()) fprintf(stderr, "[knn] level %d wide pass todo %u next %u\n", level, n_list, n_out);
+    return n_out;
+  }
+};
+
+// E3D_KNN_PROF builds: the cycle counters of k_knn_hist and k_knn_normals<3> since the last call
+static void print_knn_prof([[maybe_unused]] hipStream_t s) {
+#ifdef E3D_KNN_PROF
+  unsigned long long hp[32], zero[32] = {};
+  E3D_HIP(hipStreamSynchronize(s));
+  E3D_HIP(hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_knn_prof), sizeof hp));
+  E3D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_knn_prof), zero, sizeof zero));
+  fprintf(stderr, "[knn prof] hist: waves %llu cycles/wave:", hp[15]);
+  for (int i = 0; i < 5; ++i) fprintf(stderr, " %.0f", hp[15] ? (double)hp[i] / (double)hp[15] : 0.0);
+  fprintf(stderr, "\n[knn prof] normals<3>: waves %llu cycles/wave:", hp[31]);
+  for (int i = 0; i < 10; ++i) fprintf(stderr, " %.0f", hp[31] ? (double)hp[16 + i] / (double)hp[31] : 0.0);
+  fprintf(stderr, "\n");
+#endif
+}
+
+// The exact kNN pass over a cloud.  Results stay on the device: normals + curvature (if want_normals), the neighbour
+// index lists (if want_knn, W.d_knn) and the mean neighbour distance (if want_mean, W.d_mean), all in input order.
 // direct_n / direct_c: device buffers that take the normals / curvatures as they are computed (no staging in W.d_on / W.d_oc);
 // a cloud that already lies in device memory is read in place.
 // d_kth (needs want_knn): device buffer of n floats that receives each query's k-th squared distance, in input order.
@@ -1622,333 +1957,83 @@ __global__ __launch_bounds__(256) void k_knn_kth(const float* __restrict__ xyz, 
 static void knn_pass(KnnWorkspace& W, const float* xyz, size_t n, int k, const float* viewpoint, bool want_normals, bool want_knn,
                      bool want_mean, float* direct_n = nullptr, float* direct_c = nullptr, float* d_kth = nullptr,
                      const float4** query_order = nullptr) {
-    hipStream_t s = W.stream;
-    DevBuf<float>&bbox_partial = W.bbox_partial, &bbox_out = W.bbox_out;
-    DevBuf<int>* d_knn_out = want_knn ? &W.d_knn : nullptr;
-    DevBuf<float>* d_mean_out = want_mean ? &W.d_mean : nullptr;
-    const bool in_place = is_device_pointer(xyz);
-    if (!in_place) W.raw.reserve(3 * n);
-    struct { const float* p; } raw{in_place ? xyz : W.raw.p};
-    struct { float* p; } d_on{nullptr}, d_oc{nullptr};
-    if (want_normals) {
-      if (direct_n && direct_c) { d_on.p = direct_n; d_oc.p = direct_c; }
-      else { W.d_on.reserve(3 * n); W.d_oc.reserve(n); d_on.p = W.d_on.p; d_oc.p = W.d_oc.p; }
-    }
-    if (d_knn_out) d_knn_out->reserve(n * (size_t)k);
-    if (d_mean_out) d_mean_out->reserve(n);
-    const bool knn_indices = d_knn_out != nullptr;
-    DevBuf<int> no_knn;
-    DevBuf<int>& d_knn = d_knn_out ? *d_knn_out : no_knn;
-    if (!in_place) copy_in(W.raw.p, xyz, sizeof(float) * 3 * n, s);
-    bbox_partial.reserve(6 * (size_t)kMaxBboxBlocks); bbox_out.reserve(6);
-    launch_bbox_aos(raw.p, n, bbox_partial.p, bbox_out.p, s);
-    float bb[6];
-    W.read_back(bb, bbox_out.p, sizeof bb);
-    double ext[3], extent = 0, vol = 1;
-    for (int a = 0; a < 3; ++a) { ext[a] = (double)bb[3 + a] - (double)bb[a]; extent = std::max(extent, ext[a]); }
-    if (!(extent > 0) || !std::isfinite(extent)) extent = 1.0;
-    // starting cell size: k points inside ~1.5 cells^2 of a surface-like cloud whose area is estimated from the
-    // bounding box faces; the multi-level retry makes any choice exact, this only sets the speed
-    double area = 2.0 * (ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2]);
-    if (!(area > 0)) area = extent * extent;
-    (void)vol;
-    // (swept at 20 M points of the synthetic room scan, tools/bench_normals.py: the estimate is low in the dense part of a scan,
-    // where most points are; with the two-pass variant 1.2 - 1.5 is the optimum for k = 32 and 0.3 - 0.5 for k = 8; E3D_KNN_CELL_FACTOR overrides)
-    static const double cell_factor_env = [] { const char* e = getenv("E3D_KNN_CELL_FACTOR"); const double v = e ? atof(e) : 0.0; return v > 0 ? v : 0.0; }();
-    // k > kKnnMaxK (k_knn_large): the k-th neighbour of a surface patch lies sqrt(factor) cells away and the nearest face of the
-    // 27-cell block at least one cell, so below 1 a query of an evenly sampled surface is resolved on its first level; every
-    // retry scans four times the candidates
-    const bool large = k > kKnnMaxK;
-    if (large && (k > kKnnLargeMaxK || want_normals)) throw Error(E3D_ERR_INVALID, fmt("knn_pass: k = %d is beyond the normal estimation's lists", k));
-    const double cell_factor = cell_factor_env > 0 ? cell_factor_env : (large ? 0.6 : (k > 16 ? 1.3 : 0.45));
-    double cell = std::sqrt((double)k * area / (cell_factor * M_PI * (double)n));
-    cell = std::max(cell, extent / 1.0e6);
-    double magnitude = 0;
-    for (int a = 0; a < 6; ++a) magnitude = std::max(magnitude, std::fabs((double)bb[a]));
+  const KnnSwitches& sw = knn_switches();
+  const KnnPlan P = make_knn_plan(k, n, want_normals, sw);
+  hipStream_t s = W.stream;
+  LevelBuffers& L = W.L;
+  KnnRun R{W, sw, P, n, k, viewpoint};
+  const bool in_place = is_device_pointer(xyz);
+  if (!in_place) W.raw.reserve(3 * n);
+  R.xyz = in_place ? xyz : W.raw.p;
+  if (want_normals) {
+    if (direct_n && direct_c) { R.out_n = direct_n; R.out_c = direct_c; }
+    else { W.d_on.reserve(3 * n); W.d_oc.reserve(n); R.out_n = W.d_on.p; R.out_c = W.d_oc.p; }
+  }
+  if (want_knn) { W.d_knn.reserve(n * (size_t)k); R.out_knn = W.d_knn.p; }
+  if (want_mean) { W.d_mean.reserve(n); R.out_mean = W.d_mean.p; }
+  if (!in_place) copy_in(W.raw.p, xyz, sizeof(float) * 3 * n, s);
+  W.bbox_partial.reserve(6 * (size_t)kMaxBboxBlocks); W.bbox_out.reserve(6);
+  launch_bbox_aos(R.xyz, n, W.bbox_partial.p, W.bbox_out.p, s);
+  W.read_back(R.bb, W.bbox_out.p, sizeof R.bb);
+  double ext[3];
+  for (int a = 0; a < 3; ++a) { ext[a] = (double)R.bb[3 + a] - (double)R.bb[a]; R.extent = std::max(R.extent, ext[a]); }
+  if (!(R.extent > 0) || !std::isfinite(R.extent)) R.extent = 1.0;
+  for (int a = 0; a < 6; ++a) R.magnitude = std::max(R.magnitude, std::fabs((double)R.bb[a]));
+  // starting cell size: k points inside ~1.5 cells^2 of a surface-like cloud whose area is estimated from the
+  // bounding box faces; the multi-level retry makes any choice exact, this only sets the speed
+  double area = 2.0 * (ext[0] * ext[1] + ext[1] * ext[2] + ext[0] * ext[2]);
+  if (!(area > 0)) area = R.extent * R.extent;
+  double cell = std::sqrt((double)k * area / (P.cell_factor * M_PI * (double)n));
+  cell = std::max(cell, R.extent / 1.0e6);
 
-    LevelBuffers& L = W.L;
-    L.ka.reserve(n); L.kb.reserve(n); L.va.reserve(n); L.vb.reserve(n); L.counter.reserve(4);
-    L.P4.reserve(n + 8);
-    // queries in level-0 cell order (spatially coherent for every level): level 0's sorted points themselves; a further level sorts
-    // into the other buffer (the two are swapped then)
-    struct { const float4* p; } Q4{nullptr};
-    DevBuf<unsigned>&todo_a = W.todo_a, &todo_b = W.todo_b;
-    todo_a.reserve(n); todo_b.reserve(n);
-    unsigned* todo = nullptr;
-    size_t n_todo = n;
-    static const int forced_sel = [] { const char* e = getenv("E3D_KNN_SELECT"); return e ? atoi(e) : -1; }();     // experiments: 0 heap, 1 flat, 2 grouped, 3 two-pass
-    const int sel_list = k <= 16 ? 1 : (k <= 32 ? 2 : 0);                   // list-maintaining variant (also variant 3's fallback)
-    constexpr int kTwoPassMaxK = 60;                                        // k + 4 list slots <= the largest sorting network (64)
-    const int sel = (forced_sel >= 0 && forced_sel <= 3 && (forced_sel < 2 || (forced_sel == 2 && k <= 32) || (forced_sel == 3 && k <= kTwoPassMaxK))) ? forced_sel : (k <= kTwoPassMaxK ? 3 : 0);
-    // spare list slots of the two-pass variant (it serves the single scan's leftovers, so its occupancy matters little): with 4 a
-    // fifth of a scanner-sampled scan's leftovers overflowed into the list-maintaining variant (20 M points, scanner-sampled:
-    // k = 32 18.8 -> 17.5 ms with 20, k = 8 11.3 -> 11.0 with 12; uniform scan unchanged; profiles/round5_normals_cap_extra.txt)
-    static const int cap_extra_env = [] { const char* e = getenv("E3D_KNN_CAP_EXTRA"); return e ? atoi(e) : -1; }();
-    // (k > 32: the two-pass variant is the main kernel there, its LDS list decides the occupancy: 4 as before)
-    const int cap_extra = cap_extra_env >= 0 ? cap_extra_env : (k <= 16 ? 12 : (k <= 32 ? 20 : 4));
-    const int cap = sel == 3 ? std::min(((std::max(k + cap_extra, 12) + 1) & ~1), 64) : k;   // list entries per thread in LDS (<= the largest sorting network)
-    const size_t lds = sel == 3 ? (size_t)cap * kKnnBlock * 4 : (size_t)cap * kKnnBlock * 8, lds_list = (size_t)k * kKnnBlock * 8;
-    auto kernel_of = [](int v) {
-      return v == 0 ? k_knn_normals<0> : (v == 1 ? k_knn_normals<1> : (v == 2 ? k_knn_normals<2> : (v == 3 ? k_knn_normals<3> : (v == 4 ? k_knn_normals<4> : k_knn_normals<5>))));
-    };
-    // the single-pass variant (see k_knn_normals): sampled thresholds, level 0 only; its leftovers take the two-pass variant
-    static const int single_env = [] { const char* e = getenv("E3D_KNN_SINGLE"); return e ? atoi(e) : 1; }();
-    static const int rep_stride_env = [] { const char* e = getenv("E3D_KNN_REP_STRIDE"); return e ? atoi(e) : 0; }();
-    static const int rep_avg_env = [] { const char* e = getenv("E3D_KNN_REP_AVG"); return e ? atoi(e) : 0; }();
-    static const double rep_target_env = [] { const char* e = getenv("E3D_KNN_REP_TARGET"); return e ? atof(e) : 0.0; }();
-    constexpr int kSinglePassMaxK = kKnnTagSlots / 2;                        // variant 5 hands back k positions in its cap / 2 dwords
-    const bool single = sel == 3 && single_env != 0 && k <= kSinglePassMaxK && k >= 3;
-    // small k: 32-bit [key | tag] entries (variant 4, 36 slots: the occupancy of the two-pass variant at k = 32); beyond that
-    // the 64 slots would leave 10 waves per CU, so the list holds 16-bit tags and the keys are computed afterwards (variant 5)
-    const int single_variant = k <= 10 ? 4 : 5;
-    static const int cap1_env = [] { const char* e = getenv("E3D_KNN_CAP1"); return e ? atoi(e) : 0; }();
-    const int cap1 = single_variant == 5 ? kKnnTagSlots : ((cap1_env >= k + 9 && cap1_env <= 36) ? cap1_env : 32);   // list slots of the single-pass variant (32: 16 KB of LDS per block, five waves per SIMD with variant 4's 86 registers)
-    const int rep_stride = rep_stride_env > 0 ? rep_stride_env : 8;
-    const int rep_avg = (rep_avg_env == 1 || rep_avg_env == 2 || rep_avg_env == 4) ? rep_avg_env : 2;
-    // where the sampled thresholds come from: the block population of the sampled query alone (k_knn_hist's `estimate`, the default
-    // with a dense directory: the sampling kernel touches no candidate, 0.51 -> 0.1 ms at 20 M points; 5.70 -> 5.33 ms at k = 8,
-    // 8.38 -> 7.98 at k = 32, scanner-sampled 17.5 -> 16.8 / 11.2 -> 10.6) or its distance histogram (E3D_KNN_EST=0).  The scale
-    // (E3D_KNN_EST_SCALE) widens the estimate: 1.05 measured best between 0.8 and 1.25.
-    static const int rep_estimate_env = [] { const char* e = getenv("E3D_KNN_EST"); return e ? atoi(e) : 64; }();
-    const bool rep_estimate = rep_estimate_env != 0 && k <= rep_estimate_env;
-    static const float rep_est_scale = [] { const char* e = getenv("E3D_KNN_EST_SCALE"); const double v = e ? atof(e) : 1.05; return (float)(v > 0 ? v : 1.05); }();
-    // the count the threshold aims at: the middle of [k, capacity] (k = 32: 48 of 64), a little below it for small k where the
-    // relative Poisson noise of the count is larger on the low side
-    const int rep_target = rep_target_env > 0 ? (int)rep_target_env : std::min((k + cap1) / 2, 2 * k + 6);
-    const size_t lds1 = single_variant == 5 ? (size_t)(8 + cap1 / 2) * kKnnBlock * 4 : (size_t)cap1 * kKnnBlock * 4;
-    if (!large) {
-    if (single) E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(single_variant)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1));
-    E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(sel)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_of(sel_list)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_list));
+  L.ka.reserve(n); L.kb.reserve(n); L.va.reserve(n); L.vb.reserve(n); L.counter.reserve(4);
+  L.P4.reserve(n + 8);
+  W.todo_a.reserve(n); W.todo_b.reserve(n);
+  if (!P.large) {
+    if (P.single) E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_normals_kernel(P.single_variant)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds1));
+    E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_normals_kernel(P.sel)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds));
+    E3D_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(knn_normals_kernel(P.sel_list)), hipFuncAttributeMaxDynamicSharedMemorySize, (int)P.lds_list));
+  }
+  if (P.sel == 3) W.fb_todo.reserve(n);
+  if (P.seed_cap) {
+    W.seed_pos.reserve((size_t)P.seed_cap * (size_t)k); W.seed_flag.reserve(P.seed_cap);
+    R.seed_pos = W.seed_pos.p; R.seed_flag = W.seed_flag.p;
+  }
+
+  unsigned* todo = nullptr;           // the queries still to resolve (nullptr: all), in W.todo_a or W.todo_b
+  size_t n_todo = n;
+  auto other_list = [&](const unsigned* list) { return list == W.todo_a.p ? W.todo_b.p : W.todo_a.p; };
+  bool queries_kept = false;
+  for (int level = 0; level < 64 && n_todo > 0; ++level) {
+    KnnGrid G{};
+    if (level >= 1 && !queries_kept) { std::swap(W.Q4.p, L.P4.p); std::swap(W.Q4.cap, L.P4.cap); queries_kept = true; }   // (level 0's points stay the queries)
+    if (!R.build_level(cell, G)) { cell *= 4.0; --level; continue; }        // too many cells for 21-bit coordinates: coarsen
+    if (level == 0) R.Q4 = L.P4.p;
+    unsigned* next = other_list(todo);
+    unsigned n_next = 0;
+    // (level 0: no list yet, so the other list buffer is free for the single-pass variant's leftovers)
+    const unsigned n_fb = R.search_level(G, todo, n_todo, next, n_next, todo == nullptr ? W.todo_b.p : nullptr);
+    if (knn_stats()) {
+      fprintf(stderr, "[knn] level %d cell %g todo %zu fallback %u next %u\n", level, (double)cell, n_todo, n_fb, n_next);
+      print_knn_prof(s);
     }
-    // k_knn_large: a buffer of twice the power of two at or above k keys per query (k <= 1024: at most kLargeLdsMax = 16 KB)
-    unsigned large_cap = 512u;
-    while (large_cap < 2u * (unsigned)k) large_cap <<= 1;
-    const size_t large_lds = (size_t)large_cap * sizeof(unsigned long long);
-    DevBuf<unsigned>& fb_todo = W.fb_todo;
-    if (sel == 3) { fb_todo.reserve(n); L.counter.reserve(4); }
-    static const double level_step = [] { const char* e = getenv("E3D_KNN_LEVEL_STEP"); const double v = e ? atof(e) : 0.0; return v > 1 ? v : 2.0; }();   // cell growth per retry level (4 -> 2: -7 % at k = 32)
-    static const bool wide_pass = [] { const char* e = getenv("E3D_KNN_WIDE"); return e ? atoi(e) != 0 : true; }();
-    // seeds of the 125-cell pass (it takes lists of at most n / 64 queries)
-    static const bool seed_env = [] { const char* e = getenv("E3D_KNN_SEED"); return e ? atoi(e) != 0 : true; }();
-    // (only the lane-per-query wide pass reads them: with the wave-per-query pass -- the default for k <= 64 -- nothing would, and the
-    // scan kernels would write k positions per unresolved query plus a memset per level for nothing)
-    static const bool wide_wave = [] { const char* e = getenv("E3D_KNN_WIDE_WAVE"); return e ? atoi(e) != 0 : true; }();
-    const bool wave_per_query = wide_wave && sel == 3 && k <= 64;
-    const unsigned seed_cap = (wide_pass && seed_env && sel == 3 && !wave_per_query) ? (unsigned)(n / 64 + 1) : 0u;
-    if (seed_cap) { W.seed_pos.reserve((size_t)seed_cap * (size_t)k); W.seed_flag.reserve(seed_cap); }
-    unsigned* const seed_pos_p = seed_cap ? W.seed_pos.p : nullptr;
-    unsigned char* const seed_flag_p = seed_cap ? W.seed_flag.p : nullptr;
-    // Grid of cell size `cell_size` over all points into LB: sorted points, dense directory when the bounding grid has at most
-    // 2^dir_log2 cells (else the hash table); false if the extent does not fit 21-bit cell coordinates.
-    static const int dense_log2 = [] { const char* e = getenv("E3D_KNN_DENSE_LOG2"); return e ? std::min(atoi(e), 31) : 30; }();
-    auto build_level = [&](LevelBuffers& LB, double cell_size, int dir_log2, KnnGrid& G) -> bool {
-      G = KnnGrid{};
-      static const unsigned xcd_map = [] { const char* e = getenv("E3D_KNN_XCD"); const int v = e ? atoi(e) : 64; return (unsigned)std::min(std::max(v, 0), 4096); }();
-      G.xcd_map = xcd_map;
-      G.cell = (float)cell_size;
-      G.g.inv_cell = (float)(1.0 / (double)G.cell);
-      for (int a = 0; a < 3; ++a) { G.g.origin[a] = (float)((double)bb[a] - 2.0 * cell_size); G.dmin[a] = bb[a]; G.dmax[a] = bb[3 + a]; }
-      G.slack = (float)(16.0 * FLT_EPSILON * (magnitude + 4.0 * cell_size) + 1e-4 * cell_size);
-      if (extent / cell_size > (double)((1 << 21) - 8)) return false;
-      LB.ka.reserve(n); LB.kb.reserve(n); LB.va.reserve(n); LB.vb.reserve(n); LB.counter.reserve(4); LB.P4.reserve(n + 8);   // (+ 8: the scan kernels read whole batches)
-      // dense directory over the bounding grid (cells 0 .. cell of the bbox maximum + 2 per axis) unless it would be huge.  With it
-      // the sort key is the 32-bit linear cell index (same (z, y, x) order as the 63-bit key: 4 radix passes instead of 8).
-      QueryRange qr{};
-      double prod = 1.0;
-      for (int a = 0; a < 3; ++a) {
-        qr.lo[a] = 0;
-        const double cmax = std::floor(((double)bb[3 + a] - (double)G.g.origin[a]) * (double)G.g.inv_cell);
-        qr.D[a] = (unsigned)std::max(1.0, std::min(cmax + 4.0, 2097152.0));
-        prod *= (double)qr.D[a];
-      }
-      G.S = nullptr;
-      if (prod <= (double)((size_t)1 << dir_log2)) {
-        const size_t ncell = (size_t)prod;
-        int bits = 1;
-        while (((size_t)1 << bits) < ncell) ++bits;
-        unsigned* k32_in = reinterpret_cast<unsigned*>(LB.ka.p);
-        unsigned* k32_out = reinterpret_cast<unsigned*>(LB.kb.p);
-        hipLaunchKernelGGL(k_cell_keys_dense, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, s, raw.p, n, G.g, qr.D[0], qr.D[1], qr.D[2], k32_in, LB.va.p);
-        sort_pairs_u32_u32(k32_in, k32_out, LB.va.p, LB.vb.p, n, bits, LB.temp, s);
-        launch_permute(raw.p, nullptr, LB.vb.p, n, LB.P4.p, nullptr, s);
-        LB.dense.reserve(ncell + 2);
-        const size_t n_tiles = div_up(ncell + 2, (size_t)kDirTile);
-        const size_t n_words = n_tiles * (kDirTile / 32);                 // one bit per cell, whole tiles
-        LB.coarse.reserve(n_tiles + 1 + n_words);
-        unsigned* const occupied = LB.coarse.p + n_tiles + 1;
-        E3D_HIP(hipMemsetAsync(LB.coarse.p, 0, sizeof(unsigned) * (n_tiles + 1 + n_words), s));
-        hipLaunchKernelGGL(k_dir_mark, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, s, k32_out, n, LB.coarse.p, LB.dense.p, occupied);
-        exclusive_max_scan_u32(LB.coarse.p, n_tiles + 1, LB.temp, s);
-        hipLaunchKernelGGL(k_dense_directory, dim3((unsigned)n_tiles), dim3(256), 0, s, k32_out, occupied, LB.coarse.p, LB.dense.p, ncell + 2);
-        G.S = LB.dense.p;
-        for (int a = 0; a < 3; ++a) G.D[a] = qr.D[a];
-      } else {
-        launch_cell_keys(raw.p, n, G.g, LB.ka.p, LB.va.p, s);
-        sort_pairs_u64_u32(LB.ka.p, LB.kb.p, LB.va.p, LB.vb.p, n, 63, LB.temp, s);
-        launch_permute(raw.p, nullptr, LB.vb.p, n, LB.P4.p, nullptr, s);
-        // no dense directory (the bounding grid is too large): hash table of the occupied cells
-        E3D_HIP(hipMemsetAsync(LB.counter.p, 0, 2 * sizeof(unsigned), s));
-        launch_count_cells(LB.kb.p, n, LB.counter.p, s);
-        unsigned n_cells = 0;
-        E3D_HIP(hipMemcpyAsync(&n_cells, LB.counter.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-        E3D_HIP(hipStreamSynchronize(s));
-        size_t tsize = 64;
-        while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
-        LB.table.reserve(tsize);
-        G.g.mask = (unsigned)(tsize - 1);
-        E3D_HIP(hipMemsetAsync(LB.table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-        launch_build_table(LB.kb.p, n, LB.table.p, G.g.mask, s);
-      }
-      return true;
-    };
-    // One search of the listed queries (todo_list == nullptr: all) on a built level.  Results of resolved queries are written; the
-    // others are appended to `next_list` (device counter LB.counter[1]: k-th neighbour beyond the 27 cells).  Fallback queries of
-    // the two-pass variant (LB.counter[2]) join that list for the wide pass or run through the list-maintaining variant on the same
-    // grid right away.  n_next_out: length of next_list; returns the number of fallback queries.
-    auto search_level = [&](LevelBuffers& LB, const KnnGrid& G, const unsigned* todo_list, size_t n_list, unsigned* next_list,
-                            unsigned& n_next_out, bool merge_fb_into_next, unsigned* single_list) {
-      E3D_HIP(hipMemsetAsync(LB.counter.p + 1, 0, 3 * sizeof(unsigned), s));
-      if (large) {
-        // one wave, one block per query; what it cannot resolve on this grid is all there is to hand on
-        if (large_lds > kLargeLdsMax) throw Error(E3D_ERR_INVALID, "knn_pass: list buffer beyond the LDS budget");
-        const unsigned gx = (unsigned)std::min(n_list, (size_t)1 << 20), gy = (unsigned)div_up(n_list, (size_t)std::max(gx, 1u));
-        if (n_list > 0)
-          hipLaunchKernelGGL(k_knn_large, dim3(gx, gy), dim3(64), large_lds, s, LB.P4.p, todo_list, n_list, LB.table.p, G, k, large_cap, Q4.p,
-                             knn_indices ? d_knn.p : nullptr, d_mean_out ? d_mean_out->p : nullptr, next_list, LB.counter.p + 1);
-        unsigned n_left = 0;
-        W.read_back(&n_left, LB.counter.p + 1, sizeof(unsigned));
-        E3D_HIP(hipGetLastError());
-        n_next_out = n_left;
-        return 0u;
-      }
-      if (seed_cap) E3D_HIP(hipMemsetAsync(seed_flag_p, 0, seed_cap, s));
-      const int lsel = (sel == 3 && !G.S) ? sel_list : sel;            // the two-pass variant needs the dense directory
-      if (lsel == 3 && single && todo_list == nullptr && n_list == n && single_list != nullptr) {
-        // single pass over all queries with sampled thresholds; those whose count missed the window are listed in single_list and
-        // take the two passes below (the next-level list keeps growing: same counter)
-        const size_t n_reps = div_up(n_list, (size_t)rep_stride);
-        LB.sel_bin.reserve(n_list);
-        hipLaunchKernelGGL(k_knn_hist, dim3((unsigned)div_up(n_reps, kKnnHistBlock)), dim3(kKnnHistBlock), 0, s, LB.P4.p, (const unsigned*)nullptr, n_reps,
-                           LB.table.p, G, rep_target, Q4.p, LB.sel_bin.p, (unsigned)rep_stride, (rep_estimate && G.S) ? rep_est_scale : 0.f);
-        hipLaunchKernelGGL(kernel_of(single_variant), dim3((unsigned)div_up(n_list, kKnnBlock)), dim3(kKnnBlock), lds1, s, LB.P4.p, n, (const unsigned*)nullptr, n_list, LB.table.p, G, k, cap1,
-                           viewpoint[0], viewpoint[1], viewpoint[2], Q4.p, want_normals ? d_on.p : nullptr, want_normals ? d_oc.p : nullptr,
-                           knn_indices ? d_knn.p : nullptr, d_mean_out ? d_mean_out->p : nullptr, next_list, LB.counter.p + 1,
-                           single_list, LB.counter.p + 3, LB.sel_bin.p, 1, rep_stride, rep_avg, 1.0f, seed_pos_p, seed_flag_p, seed_cap);
-        unsigned n_single_fb = 0;
-        W.read_back(&n_single_fb, LB.counter.p + 3, sizeof(unsigned));
-        E3D_HIP(hipGetLastError());
-        if (getenv("E3D_KNN_STATS")) fprintf(stderr, "[knn] single pass (variant %d): %zu queries, target %d of %d slots, %u to the two-pass variant\n", single_variant, n_list, rep_target, cap1, n_single_fb);
-        todo_list = single_list;
-        n_list = n_single_fb;
-      }
-      const unsigned nblk = (unsigned)div_up(n_list, kKnnBlock);
-      if (lsel == 3 && n_list > 0) {
-        LB.sel_bin.reserve(n_list);
-        hipLaunchKernelGGL(k_knn_hist, dim3((unsigned)div_up(n_list, kKnnHistBlock)), dim3(kKnnHistBlock), 0, s, LB.P4.p, todo_list, n_list,
-                           LB.table.p, G, k, Q4.p, LB.sel_bin.p, 1u, 0.f);
-      }
-      if (n_list > 0)
-      hipLaunchKernelGGL(kernel_of(lsel), dim3(nblk), dim3(kKnnBlock), lsel == 3 ? lds : lds_list, s, LB.P4.p, n, todo_list, n_list, LB.table.p, G, k, lsel == 3 ? cap : k,
-                         viewpoint[0], viewpoint[1], viewpoint[2], Q4.p, want_normals ? d_on.p : nullptr, want_normals ? d_oc.p : nullptr,
-                         knn_indices ? d_knn.p : nullptr, d_mean_out ? d_mean_out->p : nullptr, next_list, LB.counter.p + 1,
-                         fb_todo.p, LB.counter.p + 2, LB.sel_bin.p, 1, 1, 1, 1.0f, lsel == 3 ? seed_pos_p : nullptr, lsel == 3 ? seed_flag_p : nullptr, seed_cap);
-      unsigned cnts[2] = {0, 0};
-      W.read_back(cnts, LB.counter.p + 1, 2 * sizeof(unsigned));
-      E3D_HIP(hipGetLastError());
-      const unsigned n_fb = cnts[1];
-      if (merge_fb_into_next && n_fb > 0 && ((size_t)cnts[0] + n_fb) * 64 <= n) {
-        // the two-pass variant's leftovers join the wide pass that follows (its first 27 cells are this level's block, the shell
-        // beyond them is skipped by the face test once the list is full): one launch instead of two
-        E3D_HIP(hipMemcpyAsync(next_list + cnts[0], fb_todo.p, sizeof(unsigned) * n_fb, hipMemcpyDeviceToDevice, s));
-        cnts[0] += n_fb;
-      } else if (n_fb > 0) {
-        // queries the two-pass variant could not settle on this level (see its comment): the list-maintaining variant, same
-        // grid, appending its unresolved ones to the same next-level list
-        hipLaunchKernelGGL(kernel_of(sel_list), dim3((unsigned)div_up((size_t)n_fb, kKnnBlock)), dim3(kKnnBlock), lds_list, s, LB.P4.p, n,
-                           fb_todo.p, (size_t)n_fb, LB.table.p, G, k, k, viewpoint[0], viewpoint[1], viewpoint[2], Q4.p,
-                           want_normals ? d_on.p : nullptr, want_normals ? d_oc.p : nullptr, knn_indices ? d_knn.p : nullptr,
-                           d_mean_out ? d_mean_out->p : nullptr, next_list, LB.counter.p + 1, nullptr, nullptr, nullptr, 1, 1, 1, 1.0f, nullptr, nullptr, 0u);
-        W.read_back(cnts, LB.counter.p + 1, sizeof(unsigned));
-        E3D_HIP(hipGetLastError());
-      }
-      n_next_out = cnts[0];
-      return n_fb;
-    };
-    bool queries_kept = false;
-    for (int level = 0; level < 64 && n_todo > 0; ++level) {
-      KnnGrid G{};
-      if (level >= 1 && !queries_kept) { std::swap(W.Q4.p, L.P4.p); std::swap(W.Q4.cap, L.P4.cap); queries_kept = true; }   // (level 0's points stay the queries)
-      if (!build_level(L, cell, dense_log2, G)) { cell *= 4.0; --level; continue; }        // too many cells for 21-bit coordinates: coarsen
-      if (level == 0) Q4.p = L.P4.p;
-      unsigned* next = (todo == todo_a.p) ? todo_b.p : todo_a.p;
-      unsigned n_next = 0;
-      // (level 0: no list yet, so the other list buffer is free for the single-pass variant's leftovers)
-      const unsigned n_fb = search_level(L, G, todo, n_todo, next, n_next, wide_pass, todo == nullptr ? todo_b.p : nullptr);
-      if (getenv("E3D_KNN_STATS")) fprintf(stderr, "[knn] level %d cell %g todo %zu fallback %u next %u\n", level, (double)cell, n_todo, n_fb, n_next);
-#ifdef E3D_KNN_PROF
-      if (getenv("E3D_KNN_STATS")) {
-        unsigned long long hp[32], zero[32] = {};
-        E3D_HIP(hipStreamSynchronize(s));
-        E3D_HIP(hipMemcpyFromSymbol(hp, HIP_SYMBOL(g_knn_prof), sizeof hp));
-        E3D_HIP(hipMemcpyToSymbol(HIP_SYMBOL(g_knn_prof), zero, sizeof zero));
-        fprintf(stderr, "[knn prof] hist: waves %llu cycles/wave:", hp[15]);
-        for (int i = 0; i < 5; ++i) fprintf(stderr, " %.0f", hp[15] ? (double)hp[i] / (double)hp[15] : 0.0);
-        fprintf(stderr, "\n[knn prof] normals<3>: waves %llu cycles/wave:", hp[31]);
-        for (int i = 0; i < 10; ++i) fprintf(stderr, " %.0f", hp[31] ? (double)hp[16 + i] / (double)hp[31] : 0.0);
-        fprintf(stderr, "\n");
-      }
-#endif
-      // the few that need a wider look (the k-th neighbour lies outside the 27 cells: sparse regions, outliers): the list-maintaining
-      // variant over the 125 cells of the same grid, which reaches as far as a grid of twice the cell size would -- no second grid
-      // build for ~1 % of the queries
-      // (a long list is cheaper on a grid of twice the cell size with the two-pass kernels: the list-maintaining variant over 125 cells
-      // took 20 ms for the 2 M far-field queries of a scanner-sampled scan, a grid build is 1.7 ms)
-      if (n_next > 0 && wide_pass && !large && (size_t)n_next * 64 <= n) {
-        unsigned* wide_out = (next == todo_a.p) ? todo_b.p : todo_a.p;
-        unsigned cw[1] = {0};
-        E3D_HIP(hipMemsetAsync(L.counter.p + 1, 0, sizeof(unsigned), s));
-        static const int wide_spread = [] { const char* e = getenv("E3D_KNN_WIDE_SPREAD"); const int v = e ? atoi(e) : 0; return v >= 1 && v <= 64 ? v : 4; }();
-        auto lane_per_query = [&](const unsigned* list, size_t n_list, bool seeded) {
-          hipLaunchKernelGGL(kernel_of(sel_list), dim3((unsigned)div_up(n_list * (size_t)wide_spread, kKnnBlock)), dim3(kKnnBlock), lds_list, s, L.P4.p, n,
-                             list, n_list, L.table.p, G, k, k, viewpoint[0], viewpoint[1], viewpoint[2], Q4.p,
-                             want_normals ? d_on.p : nullptr, want_normals ? d_oc.p : nullptr, knn_indices ? d_knn.p : nullptr,
-                             d_mean_out ? d_mean_out->p : nullptr, wide_out, L.counter.p + 1, nullptr, nullptr, nullptr, 2, wide_spread, 1, 1.0f,
-                             seeded ? seed_pos_p : nullptr, seeded ? seed_flag_p : nullptr, seed_cap);
-        };
-        if (wave_per_query && G.S) {
-          // one wave per query (k_knn_wide_wave); what it hands back (more candidates than its lanes hold, long tie runs) takes the
-          // lane-per-query kernel
-          E3D_HIP(hipMemsetAsync(L.counter.p + 2, 0, sizeof(unsigned), s));
-          hipLaunchKernelGGL(k_knn_wide_wave, dim3((unsigned)div_up((size_t)n_next, (size_t)kWideWaves)), dim3(64 * kWideWaves), 0, s, L.P4.p, next, (size_t)n_next, G, k,
-                             viewpoint[0], viewpoint[1], viewpoint[2], Q4.p, want_normals ? d_on.p : nullptr, want_normals ? d_oc.p : nullptr,
-                             knn_indices ? d_knn.p : nullptr, d_mean_out ? d_mean_out->p : nullptr, wide_out, L.counter.p + 1, fb_todo.p, L.counter.p + 2);
-          unsigned n_back = 0;
-          W.read_back(&n_back, L.counter.p + 2, sizeof(unsigned));
-          E3D_HIP(hipGetLastError());
-          if (getenv("E3D_KNN_STATS")) fprintf(stderr, "[knn] level %d wave-per-query pass: %u queries, %u handed to the lane-per-query kernel\n", level, n_next, n_back);
-          if (n_back > 0) lane_per_query(fb_todo.p, (size_t)n_back, false);
-        } else {
-          lane_per_query(next, (size_t)n_next, true);
-        }
-        W.read_back(cw, L.counter.p + 1, sizeof(unsigned));
-        E3D_HIP(hipGetLastError());
-        if (getenv("E3D_KNN_STATS")) fprintf(stderr, "[knn] level %d wide pass todo %u next %u\n", level, n_next, cw[0]);
-        next = wide_out;
-        n_next = cw[0];
-        cell *= 2.0;
-      }
-      todo = next;
-      n_todo = n_next;
-      cell *= level_step;
+    if (n_next > 0 && sw.wide && !P.large && (size_t)n_next * 64 <= n) {
+      unsigned* wide_out = other_list(next);
+      n_next = R.wide_level(G, level, next, n_next, wide_out);
+      next = wide_out;
+      cell *= 2.0;
     }
-    if (n_todo != 0) throw Error(E3D_ERR_INVALID, "e3d_normals_knn: internal error, unresolved queries remain");
-    if (d_kth) {
-      if (!knn_indices) throw Error(E3D_ERR_INVALID, "knn_pass: the k-th distance needs the neighbour lists");
-      hipLaunchKernelGGL(k_knn_kth, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, raw.p, d_knn.p, n, k, d_kth);
-      E3D_HIP(hipGetLastError());
-    }
-    if (query_order) *query_order = Q4.p;
+    todo = next;
+    n_todo = n_next;
+    cell *= sw.level_step;
+  }
+  if (n_todo != 0) throw Error(E3D_ERR_INVALID, "e3d_normals_knn: internal error, unresolved queries remain");
+  if (d_kth) {
+    if (!want_knn) throw Error(E3D_ERR_INVALID, "knn_pass: the k-th distance needs the neighbour lists");
+    hipLaunchKernelGGL(k_knn_kth, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, R.xyz, W.d_knn.p, n, k, d_kth);
+    E3D_HIP(hipGetLastError());
+  }
+  if (query_order) *query_order = R.Q4;
 }
 
 }  // namespace e3d
@@ -2014,183 +2099,145 @@ __global__ __launch_bounds__(kBlock) void k_libm_eval(int fn, const float* __res
 }  // namespace e3d
 
 extern "C" int e3d_libm_eval(int fn, const float* x, const float* y, size_t n, float* out) {
-  try {
-    if ((!x || !y || !out) && n) throw Error(E3D_ERR_INVALID, "e3d_libm_eval: null argument");
-    if (fn < 0 || fn > 5) throw Error(E3D_ERR_INVALID, "e3d_libm_eval: fn must be 0..5");
-    if (!n) return 0;
-    DevBuf<float> dx, dy, dout;
-    dx.reserve(n); dy.reserve(n); dout.reserve(n);
-    hipStream_t s = nullptr;
-    copy_in(dx.p, x, sizeof(float) * n, s); copy_in(dy.p, y, sizeof(float) * n, s);
-    hipLaunchKernelGGL(k_libm_eval, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, s, fn, dx.p, dy.p, n, dout.p);
-    copy_out(out, dout.p, sizeof(float) * n, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    return 0;
-  } catch (const e3d::Error& e) { e3d::set_last_error(e.what()); return e.code; }
-  catch (const std::exception& e) { e3d::set_last_error(e.what()); return E3D_ERR_INVALID; }
+  E3D_TRY
+  if ((!x || !y || !out) && n) throw Error(E3D_ERR_INVALID, "e3d_libm_eval: null argument");
+  if (fn < 0 || fn > 5) throw Error(E3D_ERR_INVALID, "e3d_libm_eval: fn must be 0..5");
+  if (!n) return 0;
+  DevBuf<float> dx, dy, dout;
+  dx.reserve(n); dy.reserve(n); dout.reserve(n);
+  hipStream_t s = nullptr;
+  copy_in(dx.p, x, sizeof(float) * n, s); copy_in(dy.p, y, sizeof(float) * n, s);
+  hipLaunchKernelGGL(k_libm_eval, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, s, fn, dx.p, dy.p, n, dout.p);
+  copy_out(out, dout.p, sizeof(float) * n, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  return 0;
+  E3D_CATCH()
 }
 
 extern "C" int e3d_normals_knn(const float* xyz, size_t n, int k, const float* viewpoint, float* out_normals,
                                float* out_curvature, int32_t* knn_indices) {
-  try {
-    if ((!xyz && n) || !viewpoint || (!out_normals && n) || (!out_curvature && n))
-      throw Error(E3D_ERR_INVALID, "e3d_normals_knn: null argument");
-    if (k < 1 || k > kKnnMaxK) throw Error(E3D_ERR_INVALID, fmt("e3d_normals_knn: k = %d outside [1, %d]", k, kKnnMaxK));
-    if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_normals_knn: more than 2^31-1 points");
-    require_device();
-    if (n == 0) return 0;
-    WorkspaceLease lease;
-    KnnWorkspace& W = *lease.ws;
-    hipStream_t s = W.stream;
-    const bool direct = is_device_pointer(out_normals) && is_device_pointer(out_curvature);   // results straight into the caller's device buffers
-    knn_pass(W, xyz, n, k, viewpoint, true, knn_indices != nullptr, false, direct ? out_normals : nullptr, direct ? out_curvature : nullptr);
-    DevBuf<int>& d_knn = W.d_knn;
-    if (!direct) {
-      copy_out(out_normals, W.d_on.p, sizeof(float) * 3 * n, s);
-      copy_out(out_curvature, W.d_oc.p, sizeof(float) * n, s);
-    }
-    if (knn_indices) copy_out(knn_indices, d_knn.p, sizeof(int) * n * (size_t)k, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    return 0;
-  } catch (const e3d::Error& e) {
-    e3d::set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return E3D_ERR_INVALID;
+  E3D_TRY
+  if ((!xyz && n) || !viewpoint || (!out_normals && n) || (!out_curvature && n))
+    throw Error(E3D_ERR_INVALID, "e3d_normals_knn: null argument");
+  if (k < 1 || k > kKnnMaxK) throw Error(E3D_ERR_INVALID, fmt("e3d_normals_knn: k = %d outside [1, %d]", k, kKnnMaxK));
+  if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_normals_knn: more than 2^31-1 points");
+  require_device();
+  if (n == 0) return 0;
+  WorkspaceLease lease;
+  KnnWorkspace& W = *lease.ws;
+  hipStream_t s = W.stream;
+  const bool direct = is_device_pointer(out_normals) && is_device_pointer(out_curvature);   // results straight into the caller's device buffers
+  knn_pass(W, xyz, n, k, viewpoint, true, knn_indices != nullptr, false, direct ? out_normals : nullptr, direct ? out_curvature : nullptr);
+  if (!direct) {
+    copy_out(out_normals, W.d_on.p, sizeof(float) * 3 * n, s);
+    copy_out(out_curvature, W.d_oc.p, sizeof(float) * n, s);
   }
+  if (knn_indices) copy_out(knn_indices, W.d_knn.p, sizeof(int) * n * (size_t)k, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  return 0;
+  E3D_CATCH()
 }
 
 // pcl::LocalStatisticalOutlierRemoval<PointT>::applyFilterIndices (src/geometry/local_statistical_outlier_removal.hpp:71-172)
 extern "C" int e3d_local_outlier_removal(const float* xyz, size_t n, int mean_k, double distance_factor_threshold, int negative,
                                          uint8_t* inlier, float* mean_distances) {
-  try {
-    if ((!xyz && n) || (!inlier && n)) throw Error(E3D_ERR_INVALID, "e3d_local_outlier_removal: null argument");
-    if (mean_k < 1 || mean_k > kKnnLargeMaxK - 1) throw Error(E3D_ERR_INVALID, fmt("e3d_local_outlier_removal: mean_k = %d outside [1, %d]", mean_k, kKnnLargeMaxK - 1));
-    if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_local_outlier_removal: more than 2^31-1 points");
-    require_device();
-    if (n == 0) return 0;
-    // non-finite points: distance 0 in the first pass, "problematic" (removed unless negative) in the second (:88-95, :115-125)
-    std::vector<float> finite;
-    std::vector<size_t> origin;
-    bool all_finite = true;
-    for (size_t i = 0; i < n && all_finite; ++i)
-      all_finite = std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2]);
-    const float* pts = xyz;
-    size_t m = n;
-    if (!all_finite) {
-      for (size_t i = 0; i < n; ++i)
-        if (std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2])) {
-          finite.insert(finite.end(), xyz + 3 * i, xyz + 3 * i + 3);
-          origin.push_back(i);
-        }
-      pts = finite.data(); m = origin.size();
-    }
-    // m <= mean_k: the search returns the m points there are (pcl::KdTreeFLANN clamps k), the mean still divides by mean_k and
-    // the second pass walks the shorter lists -- the neighbour lists are padded with -1 and the kernels stop there
-    if (m == 0) { for (size_t i = 0; i < n; ++i) { inlier[i] = 0; if (mean_distances) mean_distances[i] = 0.f; } return 0; }
-    WorkspaceLease lease;
-    KnnWorkspace& W = *lease.ws;
-    hipStream_t s = W.stream;
-    DevBuf<float>& d_mean = W.d_mean;
-    DevBuf<int>& d_knn = W.d_knn;
-    DevBuf<unsigned char>& d_in = W.d_in;
-    const float vp[3] = {0.f, 0.f, 0.f};
-    const int k = mean_k + 1;
-    knn_pass(W, pts, m, k, vp, false, true, true);
-    d_in.reserve(m);
-    hipLaunchKernelGGL(k_outlier_classify, dim3((unsigned)div_up(m, 256)), dim3(256), 0, s, d_knn.p, d_mean.p, m, k,
-                       distance_factor_threshold, negative, d_in.p);
-    if (all_finite) {
-      copy_out(inlier, d_in.p, m, s);
-      if (mean_distances) copy_out(mean_distances, d_mean.p, sizeof(float) * m, s);
-      E3D_HIP(hipStreamSynchronize(s));
-    } else {
-      std::vector<unsigned char> in(m);
-      std::vector<float> md(m);
-      copy_out(in.data(), d_in.p, m, s);
-      copy_out(md.data(), d_mean.p, sizeof(float) * m, s);
-      E3D_HIP(hipStreamSynchronize(s));
-      // a non-finite point is never an inlier: removed when !negative (:120-125); with negative it reaches the comparison
-      // with distance 0 <= threshold -> removed as well unless the threshold is NaN
-      for (size_t i = 0; i < n; ++i) { inlier[i] = 0; if (mean_distances) mean_distances[i] = 0.f; }
-      for (size_t j = 0; j < m; ++j) { inlier[origin[j]] = in[j]; if (mean_distances) mean_distances[origin[j]] = md[j]; }
-    }
-    return 0;
-  } catch (const e3d::Error& e) {
-    e3d::set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return E3D_ERR_INVALID;
+  E3D_TRY
+  if ((!xyz && n) || (!inlier && n)) throw Error(E3D_ERR_INVALID, "e3d_local_outlier_removal: null argument");
+  if (mean_k < 1 || mean_k > kKnnLargeMaxK - 1) throw Error(E3D_ERR_INVALID, fmt("e3d_local_outlier_removal: mean_k = %d outside [1, %d]", mean_k, kKnnLargeMaxK - 1));
+  if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_local_outlier_removal: more than 2^31-1 points");
+  require_device();
+  if (n == 0) return 0;
+  // non-finite points: distance 0 in the first pass, "problematic" (removed unless negative) in the second (:88-95, :115-125)
+  std::vector<float> finite;
+  std::vector<size_t> origin;
+  bool all_finite = true;
+  for (size_t i = 0; i < n && all_finite; ++i)
+    all_finite = std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2]);
+  const float* pts = xyz;
+  size_t m = n;
+  if (!all_finite) {
+    for (size_t i = 0; i < n; ++i)
+      if (std::isfinite(xyz[3 * i]) && std::isfinite(xyz[3 * i + 1]) && std::isfinite(xyz[3 * i + 2])) {
+        finite.insert(finite.end(), xyz + 3 * i, xyz + 3 * i + 3);
+        origin.push_back(i);
+      }
+    pts = finite.data(); m = origin.size();
   }
+  // m <= mean_k: the search returns the m points there are (pcl::KdTreeFLANN clamps k), the mean still divides by mean_k and
+  // the second pass walks the shorter lists -- the neighbour lists are padded with -1 and the kernels stop there
+  if (m == 0) { for (size_t i = 0; i < n; ++i) { inlier[i] = 0; if (mean_distances) mean_distances[i] = 0.f; } return 0; }
+  WorkspaceLease lease;
+  KnnWorkspace& W = *lease.ws;
+  hipStream_t s = W.stream;
+  DevBuf<float>& d_mean = W.d_mean;
+  DevBuf<int>& d_knn = W.d_knn;
+  DevBuf<unsigned char>& d_in = W.d_in;
+  const float vp[3] = {0.f, 0.f, 0.f};
+  const int k = mean_k + 1;
+  knn_pass(W, pts, m, k, vp, false, true, true);
+  d_in.reserve(m);
+  hipLaunchKernelGGL(k_outlier_classify, dim3((unsigned)div_up(m, 256)), dim3(256), 0, s, d_knn.p, d_mean.p, m, k,
+                     distance_factor_threshold, negative, d_in.p);
+  if (all_finite) {
+    copy_out(inlier, d_in.p, m, s);
+    if (mean_distances) copy_out(mean_distances, d_mean.p, sizeof(float) * m, s);
+    E3D_HIP(hipStreamSynchronize(s));
+  } else {
+    std::vector<unsigned char> in(m);
+    std::vector<float> md(m);
+    copy_out(in.data(), d_in.p, m, s);
+    copy_out(md.data(), d_mean.p, sizeof(float) * m, s);
+    E3D_HIP(hipStreamSynchronize(s));
+    // a non-finite point is never an inlier: removed when !negative (:120-125); with negative it reaches the comparison
+    // with distance 0 <= threshold -> removed as well unless the threshold is NaN
+    for (size_t i = 0; i < n; ++i) { inlier[i] = 0; if (mean_distances) mean_distances[i] = 0.f; }
+    for (size_t j = 0; j < m; ++j) { inlier[origin[j]] = in[j]; if (mean_distances) mean_distances[origin[j]] = md[j]; }
+  }
+  return 0;
+  E3D_CATCH()
 }
 
 extern "C" int e3d_normals_radius(const float* xyz, size_t n, float radius, const float* viewpoint, float* out_normals,
                                   float* out_curvature, int32_t* neighbor_counts) {
-  try {
-    if ((!xyz && n) || !viewpoint || (!out_normals && n) || (!out_curvature && n))
-      throw Error(E3D_ERR_INVALID, "e3d_normals_radius: null argument");
-    if (!(radius > 0.f) || !std::isfinite(radius)) throw Error(E3D_ERR_INVALID, "e3d_normals_radius: radius must be positive");
-    if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_normals_radius: more than 2^31-1 points");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-      throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-    if (n == 0) return 0;
-    hipStream_t s = nullptr;
-    E3D_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{s};
-    DevBuf<float> raw, d_on, d_oc, bbox_partial, bbox_out;
-    DevBuf<int> d_cnt;
-    raw.reserve(3 * n); d_on.reserve(3 * n); d_oc.reserve(n);
-    if (neighbor_counts) d_cnt.reserve(n);
-    copy_in(raw.p, xyz, sizeof(float) * 3 * n, s);
-    bbox_partial.reserve(6 * (size_t)kMaxBboxBlocks); bbox_out.reserve(6);
-    launch_bbox_aos(raw.p, n, bbox_partial.p, bbox_out.p, s);
-    float bb[6];
-    copy_out(bb, bbox_out.p, sizeof bb, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    double extent = 0, magnitude = 0;
-    for (int a = 0; a < 3; ++a) extent = std::max(extent, (double)bb[3 + a] - (double)bb[a]);
-    for (int a = 0; a < 6; ++a) magnitude = std::max(magnitude, std::fabs((double)bb[a]));
-    // cell = radius plus slack for the f32 cell-index computation: every point within the radius lies in the 27 cells
-    double cell = (double)radius * (1.0 + 1e-4) + 16.0 * FLT_EPSILON * (magnitude + 4.0 * (double)radius);
-    if (extent / cell > (double)((1 << 21) - 8)) throw Error(E3D_ERR_INVALID, "e3d_normals_radius: radius too small for the extent of the cloud");
-    KnnGrid G{};
-    G.cell = (float)cell;
-    G.g.inv_cell = (float)(1.0 / (double)G.cell);
-    for (int a = 0; a < 3; ++a) { G.g.origin[a] = (float)((double)bb[a] - 2.0 * cell); G.dmin[a] = bb[a]; G.dmax[a] = bb[3 + a]; }
-    LevelBuffers L;
-    L.ka.reserve(n); L.kb.reserve(n); L.va.reserve(n); L.vb.reserve(n); L.counter.reserve(4); L.P4.reserve(n);
-    launch_cell_keys(raw.p, n, G.g, L.ka.p, L.va.p, s);
-    sort_pairs_u64_u32(L.ka.p, L.kb.p, L.va.p, L.vb.p, n, 63, L.temp, s);
-    launch_permute(raw.p, nullptr, L.vb.p, n, L.P4.p, nullptr, s);
-    E3D_HIP(hipMemsetAsync(L.counter.p, 0, 2 * sizeof(unsigned), s));
-    launch_count_cells(L.kb.p, n, L.counter.p, s);
-    unsigned n_cells = 0;
-    E3D_HIP(hipMemcpyAsync(&n_cells, L.counter.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    E3D_HIP(hipStreamSynchronize(s));
-    size_t tsize = 64;
-    while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
-    L.table.reserve(tsize);
-    G.g.mask = (unsigned)(tsize - 1);
-    E3D_HIP(hipMemsetAsync(L.table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-    launch_build_table(L.kb.p, n, L.table.p, G.g.mask, s);
-    const double rr = (double)radius;
-    const float r2 = (float)(rr * rr);      // pcl::KdTreeFLANN::radiusSearch: static_cast<float>(radius * radius)
-    hipLaunchKernelGGL(k_radius_normals, dim3((unsigned)div_up(n, kKnnBlock)), dim3(kKnnBlock), 0, s, L.P4.p, n, L.table.p, G, r2,
-                       viewpoint[0], viewpoint[1], viewpoint[2], d_on.p, d_oc.p, neighbor_counts ? d_cnt.p : nullptr);
-    copy_out(out_normals, d_on.p, sizeof(float) * 3 * n, s);
-    copy_out(out_curvature, d_oc.p, sizeof(float) * n, s);
-    if (neighbor_counts) copy_out(neighbor_counts, d_cnt.p, sizeof(int) * n, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    E3D_HIP(hipGetLastError());
-    return 0;
-  } catch (const e3d::Error& e) {
-    e3d::set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return E3D_ERR_INVALID;
-  }
+  E3D_TRY
+  if ((!xyz && n) || !viewpoint || (!out_normals && n) || (!out_curvature && n))
+    throw Error(E3D_ERR_INVALID, "e3d_normals_radius: null argument");
+  if (!(radius > 0.f) || !std::isfinite(radius)) throw Error(E3D_ERR_INVALID, "e3d_normals_radius: radius must be positive");
+  if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_normals_radius: more than 2^31-1 points");
+  require_device();
+  if (n == 0) return 0;
+  hipStream_t s = nullptr;
+  E3D_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{s};
+  DevBuf<float> raw, d_on, d_oc, bbox_partial, bbox_out;
+  DevBuf<int> d_cnt;
+  raw.reserve(3 * n); d_on.reserve(3 * n); d_oc.reserve(n);
+  if (neighbor_counts) d_cnt.reserve(n);
+  copy_in(raw.p, xyz, sizeof(float) * 3 * n, s);
+  bbox_partial.reserve(6 * (size_t)kMaxBboxBlocks); bbox_out.reserve(6);
+  launch_bbox_aos(raw.p, n, bbox_partial.p, bbox_out.p, s);
+  float bb[6];
+  copy_out(bb, bbox_out.p, sizeof bb, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  double extent = 0, magnitude = 0;
+  for (int a = 0; a < 3; ++a) extent = std::max(extent, (double)bb[3 + a] - (double)bb[a]);
+  for (int a = 0; a < 6; ++a) magnitude = std::max(magnitude, std::fabs((double)bb[a]));
+  // cell = radius plus slack for the f32 cell-index computation: every point within the radius lies in the 27 cells
+  double cell = (double)radius * (1.0 + 1e-4) + 16.0 * FLT_EPSILON * (magnitude + 4.0 * (double)radius);
+  if (extent / cell > (double)((1 << 21) - 8)) throw Error(E3D_ERR_INVALID, "e3d_normals_radius: radius too small for the extent of the cloud");
+  KnnGrid G = knn_grid_over(bb, cell);
+  LevelBuffers L;
+  L.ka.reserve(n); L.kb.reserve(n); L.va.reserve(n); L.vb.reserve(n); L.counter.reserve(4); L.P4.reserve(n);
+  build_hash_grid(raw.p, n, L, G, s);
+  const double rr = (double)radius;
+  const float r2 = (float)(rr * rr);      // pcl::KdTreeFLANN::radiusSearch: static_cast<float>(radius * radius)
+  hipLaunchKernelGGL(k_radius_normals, dim3((unsigned)div_up(n, kKnnBlock)), dim3(kKnnBlock), 0, s, L.P4.p, n, L.table.p, G, r2,
+                     viewpoint[0], viewpoint[1], viewpoint[2], d_on.p, d_oc.p, neighbor_counts ? d_cnt.p : nullptr);
+  copy_out(out_normals, d_on.p, sizeof(float) * 3 * n, s);
+  copy_out(out_curvature, d_oc.p, sizeof(float) * n, s);
+  if (neighbor_counts) copy_out(neighbor_counts, d_cnt.p, sizeof(int) * n, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  E3D_HIP(hipGetLastError());
+  return 0;
+  E3D_CATCH()
 }

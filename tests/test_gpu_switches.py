@@ -3,7 +3,7 @@ each setting runs in its own interpreter: the certificate search of several dire
 pair or one launch per pair (E3D_ICP_BATCH = 0 / 1; default 2: one launch per kernel and batch), the far lists of a batch keyed, sorted and searched in one launch each against pair by pair (E3D_NN_FAR_BATCH), the LM step's damped solves on host threads (E3D_LM_SOLVE_THREADS), the certificates' motion bound per query against the clouds' global one (E3D_NN_PERQUERY), the key kernel that settles queries with an empty 27-cell block against sorting them all (E3D_NN_PRUNE), certificates tested in every outer iteration against skipped while none holds (E3D_NN_CERT_SKIP) and against no certificates at all (E3D_NN_CERT=0: every query searched in every iteration), resident against compacted correspondence rows (E3D_ICP_RESIDENT), the speculative last LM step
 (E3D_LM_SPECULATE), the row update's per-block results written by the certificate kernel for the blocks it settles whole against the update
 computing them all (E3D_NN_FUSE_UPDATE = 0; E3D_NN_FUSE_GATE = 1: for every certified pair, not only the nearly settled ones), far-list queries that start the bounded search from a probe of their own half cell against sort + row kernel for all of them (E3D_NN_SEED = 0; E3D_NN_SEED_FRAC / _NEAR / _FRESH: from the first search on, other seed distances); the kNN estimator's single scan with sampled thresholds against the two-pass kernels (E3D_KNN_SINGLE), with
-and without the lists the 125-cell pass starts from (E3D_KNN_SEED), the wave-per-query form of that pass (E3D_KNN_WIDE_WAVE), the sampled thresholds from the block population against the distance histogram, and deliberately poor ones (E3D_KNN_EST, E3D_KNN_EST_SCALE); (B): an iteration's cost taken from the next Apply's accumulation against the separate cost pass (E3D_REG_FUSE_COST = 0)."""
+and without the lists the 125-cell pass starts from (E3D_KNN_SEED), the wave-per-query form of that pass (E3D_KNN_WIDE_WAVE), the sampled thresholds from the block population against the distance histogram, and deliberately poor ones (E3D_KNN_EST, E3D_KNN_EST_SCALE), and the switches that change the pass's host-side numbers only (E3D_KNN_CELL_FACTOR, _LEVEL_STEP, _CAP_EXTRA, _WIDE, _DENSE_LOG2, _PINNED, _CAP1 with _REP_TARGET); (B): an iteration's cost taken from the next Apply's accumulation against the separate cost pass (E3D_REG_FUSE_COST = 0)."""
 import json
 import os
 import subprocess
@@ -150,7 +150,12 @@ def test_seeded_far_lists_match_the_oracle():
 def test_knn_scan_variants_agree():
     base = _run(KNN_CODE, {})
     for env in ({"E3D_KNN_SINGLE": "0"}, {"E3D_KNN_SEED": "0"}, {"E3D_KNN_WIDE_SPREAD": "1"}, {"E3D_KNN_WIDE_WAVE": "0"}, {"E3D_KNN_XCD": "0"},
-                {"E3D_KNN_REP_STRIDE": "32", "E3D_KNN_REP_AVG": "1"}, {"E3D_KNN_EST": "0"}, {"E3D_KNN_EST_SCALE": "0.5"}, {"E3D_KNN_EST_SCALE": "3"}):
+                {"E3D_KNN_REP_STRIDE": "32", "E3D_KNN_REP_AVG": "1"}, {"E3D_KNN_EST": "0"}, {"E3D_KNN_EST_SCALE": "0.5"}, {"E3D_KNN_EST_SCALE": "3"},
+                # host-side numbers only (every kernel stays at a (variant, k) that default runs use): starting cell, growth per level,
+                # spare slots of the two-pass lists, no 125-cell pass, every level on the hash table (the list-maintaining variants
+                # serve all queries), read-backs through pageable memory, the single scan's slots and target
+                {"E3D_KNN_CELL_FACTOR": "0.9"}, {"E3D_KNN_LEVEL_STEP": "4"}, {"E3D_KNN_CAP_EXTRA": "4"}, {"E3D_KNN_WIDE": "0"}, {"E3D_KNN_DENSE_LOG2": "12"},
+                {"E3D_KNN_PINNED": "0"}, {"E3D_KNN_CAP1": "20", "E3D_KNN_REP_TARGET": "12"}):
         assert _run(KNN_CODE, env) == base, env
 
 
