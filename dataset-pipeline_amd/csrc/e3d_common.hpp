@@ -51,6 +51,8 @@ inline bool env_default_off(const char* name) { const char* e = getenv(name); re
 // The C-ABI's error convention: an e3d::Error returns its code, any other exception E3D_ERR_INVALID (include/e3d_hip.h), and
 // e3d_last_error() has the text
 #define E3D_TRY try {
+// ... of an entry point that takes a handle: it runs on the handle's device, whatever the calling thread's current device is
+#define E3D_TRY_ON(h) try { if (h) E3D_HIP(hipSetDevice((h)->device));
 #define E3D_CATCH()                                                                         \
   } catch (const e3d::Error& e) { e3d::set_last_error(e.what()); return e.code; }           \
   catch (const std::exception& e) { e3d::set_last_error(e.what()); return E3D_ERR_INVALID; }

@@ -2454,13 +2454,37 @@ struct e3d_reg {
 
 namespace e3d {
 
+// The environment switches of the registration host code, parsed once at first use (INTEGRATION.md lists them)
+struct RegSwitches {
+  bool pinned = env_default_on("E3D_REG_PINNED");              // 0: read_back through pageable memory (as rounds 1 - 5, for A / B timing)
+  bool splat_order = env_default_on("E3D_REG_SPLAT_ORDER");    // 0: the splat points keep the caller's order (e3d_reg_set_splat_points)
+  bool separable_min_filter = false;                           // E3D_REG_MIN_FILTER=separable: the splat depth's minimum filter in two launches
+  int pass2_blocks = 1024;                                     // E3D_REG_PASS2_BLOCKS: the most workgroups of a pass-2 launch (below)
+  enum Pass2 { mfma64, tile32, mfma32, valu } pass2 = mfma64;  // E3D_REG_PASS2=tile32|mfma32|valu: the pass-2 kernel (launch_pass2)
+  bool pass2_mfma10 = getenv("E3D_REG_PASS2_MFMA10") != nullptr;      // experiment: the single-launch system on the matrix cores too
+  enum Solver { by_size, dense, arrow } solver = by_size;      // E3D_REG_SOLVER=dense|arrow forces one solve of Apply (DampedSolver; tests)
+  bool fuse_cost = env_int("E3D_REG_FUSE_COST", 1) != 0;       // 0: the separate cost pass in every iteration (e3d_reg_run_on_current_scale)
+  RegSwitches() {
+    const char* e = getenv("E3D_REG_MIN_FILTER");
+    separable_min_filter = e && !strcmp(e, "separable");
+    // pass 2: one resident round of workgroups (two of these 256-thread groups fit a CU): 512 on MI355X; measured 0.684 / 0.694 / 0.704 /
+    // 0.711 ms for 512 / 1024 / 2048 / 4096 at the configs[3] shape
+    int dev = 0, cus = 0;
+    if ((e = getenv("E3D_REG_PASS2_BLOCKS"))) pass2_blocks = std::max(8, atoi(e));
+    else if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
+      pass2_blocks = 2 * cus;
+    if ((e = getenv("E3D_REG_PASS2"))) pass2 = !strcmp(e, "valu") ? valu : (!strcmp(e, "tile32") ? tile32 : (!strcmp(e, "mfma32") ? mfma32 : mfma64));
+    if ((e = getenv("E3D_REG_SOLVER"))) solver = !strcmp(e, "dense") ? dense : (!strcmp(e, "arrow") ? arrow : by_size);
+  }
+};
+static const RegSwitches& reg_switches() { static const RegSwitches sw; return sw; }
+
 static void rsync(e3d_reg* h) { E3D_HIP(hipStreamSynchronize(h->stream)); }
 // A few words back from the device, through the handle's pinned mailbox, and the stream synchronised: hipMemcpyAsync into pageable
 // memory (a stack variable) goes through the runtime's staging path and costs several times the copy into pinned memory -- an
 // iteration of RunOnCurrentScale reads ~120 such results (pair counts, kept / dropped candidates, the sums of every pass).
 static void read_back(e3d_reg* h, void* dst, const void* src_dev, size_t bytes) {
-  static const bool pinned = [] { const char* e = getenv("E3D_REG_PINNED"); return !(e && e[0] == '0'); }();     // (0: as rounds 1 - 5, for A / B timing)
-  if (bytes == 0 || !pinned) { copy_out(dst, src_dev, bytes, h->stream); rsync(h); return; }
+  if (bytes == 0 || !reg_switches().pinned) { copy_out(dst, src_dev, bytes, h->stream); rsync(h); return; }
   if (bytes > h->mailbox.cap) h->mailbox.reserve(std::max(bytes, (size_t)65536));
   E3D_HIP(hipMemcpyAsync(h->mailbox.p, src_dev, bytes, hipMemcpyDeviceToHost, h->stream));
   E3D_HIP(hipStreamSynchronize(h->stream));
@@ -2499,6 +2523,12 @@ struct Phase {
   }
 };
 static unsigned nblk(size_t n) { return (unsigned)div_up(n ? n : 1, kBlock); }
+// workgroups of a kernel that leaves one partial result per group: four observations per thread, at most `cap` groups
+static int partial_blocks(size_t n, size_t cap) { return (int)std::min<size_t>(std::max<size_t>(div_up(n, kBlock * 4), 1), cap); }
+static RegWeights reg_weights(const e3d_reg* h) {
+  return RegWeights{h->prm.robust_weighting_type, h->prm.robust_weighting_parameter, h->prm.fixed_residuals_weight, h->prm.variable_residuals_weight};
+}
+static int image_owner(const e3d_reg* h, int image_id) { return h->world <= 1 ? 0 : ((image_id % h->world) + h->world) % h->world; }
 
 // Sums over the ranks.  With the library's own communicator (e3d_reg_set_comm) both run as RCCL all-reduces on the handle's
 // stream -- the small f64 blocks staged through HBM, the descriptors in place -- otherwise through the callbacks.
@@ -2782,276 +2812,11 @@ static void obs_intensities(e3d_reg* h, ImageDev& im, Obs& O) {
   }
 }
 
-}  // namespace e3d
 
-#define R_TRY try {
-// entry points that take a handle run on the handle's device, whatever the calling thread's current device is
-#define R_TRYH try { if (h) E3D_HIP(hipSetDevice(h->device));
-#define R_CATCH()                                                                            \
-  } catch (const e3d::Error& e) { e3d::set_last_error(e.what()); return e.code; }            \
-  catch (const std::exception& e) { e3d::set_last_error(e.what()); return E3D_ERR_INVALID; }
-
-extern "C" {
-
-e3d_reg_t* e3d_reg_create(const e3d_reg_params* params) {
-  try {
-    check_params(params);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-    std::unique_ptr<e3d_reg> h(new e3d_reg());
-    E3D_HIP(hipGetDevice(&h->device));
-    E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->prm = *params;
-    return h.release();
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return nullptr;
-  }
-}
-void e3d_reg_destroy(e3d_reg_t* reg) { delete reg; }
-
-int e3d_reg_set_params(e3d_reg_t* h, const e3d_reg_params* params) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  check_params(params);
-  if (params->point_neighbor_count != h->prm.point_neighbor_count && !h->scales.empty())
-    throw Error(E3D_ERR_INVALID, "point_neighbor_count cannot change after point scales were set");
-  h->prm = *params;
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_set_point_scale(e3d_reg_t* h, int point_scale, const float* xyz, size_t n, float point_radius,
-                            const uint32_t* neighbor_indices, const float* fixed_descriptors) {
-  R_TRYH
-  if (!h || (!xyz && n) || (!neighbor_indices && n)) throw Error(E3D_ERR_INVALID, "e3d_reg_set_point_scale: null argument");
-  hipStream_t s = h->stream;
-  const int K = h->prm.point_neighbor_count;
-  PointScale& S = h->scales[point_scale];
-  S.n = n; S.radius = point_radius;
-  S.pts.reserve(n); S.nbr.reserve(n * K); S.fixed_desc.reserve(n * K); S.var_desc.reserve(n * K);
-  S.obs_counts.reserve(n); S.row_of_point.reserve(n);
-  DevBuf<float> tmp; tmp.reserve(3 * n);
-  copy_in(tmp.p, xyz, sizeof(float) * 3 * n, s);
-  hipLaunchKernelGGL(k_xyz_to_float4, dim3(nblk(n)), dim3(kBlock), 0, s, tmp.p, n, S.pts.p);
-  copy_in(S.nbr.p, neighbor_indices, sizeof(unsigned) * n * K, s);
-  S.has_fixed = fixed_descriptors != nullptr;
-  if (fixed_descriptors) copy_in(S.fixed_desc.p, fixed_descriptors, sizeof(float) * n * K, s);
-  else E3D_HIP(hipMemsetAsync(S.fixed_desc.p, 0, sizeof(float) * n * K, s));
-  E3D_HIP(hipMemsetAsync(S.var_desc.p, 0, sizeof(float) * n * K, s));
-  hipLaunchKernelGGL(k_fill_i32, dim3(nblk(n)), dim3(kBlock), 0, s, S.obs_counts.p, n, fixed_descriptors ? 99999 : 0);   // problem.cc:568-570
-  rsync(h);
-  for (auto& kv : h->images) kv.second.obs.erase(point_scale);
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_set_variable_descriptors(e3d_reg_t* h, int point_scale, const float* descriptors, const int32_t* counts) {
-  R_TRYH
-  if (!h || !descriptors || !counts) throw Error(E3D_ERR_INVALID, "null argument");
-  PointScale& S = get_scale(h, point_scale);
-  copy_in(S.var_desc.p, descriptors, sizeof(float) * S.n * h->prm.point_neighbor_count, h->stream);
-  copy_in(S.obs_counts.p, counts, sizeof(int) * S.n, h->stream);
-  rsync(h);
-  return 0;
-  R_CATCH()
-}
-int e3d_reg_get_variable_descriptors(e3d_reg_t* h, int point_scale, float* descriptors, int32_t* counts) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  PointScale& S = get_scale(h, point_scale);
-  if (descriptors) copy_out(descriptors, S.var_desc.p, sizeof(float) * S.n * h->prm.point_neighbor_count, h->stream);
-  if (counts) copy_out(counts, S.obs_counts.p, sizeof(int) * S.n, h->stream);
-  rsync(h);
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_set_intrinsics(e3d_reg_t* h, int intrinsics_id, int camera_type, int width, int height, const float* parameters,
-                           int n_parameters, int min_image_scale, int n_levels) {
-  R_TRYH
-  if (!h || !parameters) throw Error(E3D_ERR_INVALID, "null argument");
-  if (camera_type < 0 || camera_type >= kNumCameraModels)
-    throw Error(E3D_ERR_INVALID, "unknown camera model (E3D_CAMERA_* of e3d_hip.h)");
-  if (n_parameters != cam_param_count(camera_type)) throw Error(E3D_ERR_INVALID, fmt("camera model %d takes %d parameters, got %d", camera_type, cam_param_count(camera_type), n_parameters));
-  if (n_levels < 1 || n_levels > kRegMaxLevels || width < 2 || height < 2 || min_image_scale < 0) throw Error(E3D_ERR_INVALID, "bad pyramid description");
-  Intrin in;
-  in.type = camera_type; in.min_image_scale = min_image_scale; in.n_params = n_parameters;
-  in.width = width; in.height = height;
-  for (int i = 0; i < n_parameters; ++i) in.params[i] = parameters[i];
-  build_model_pyramid(h, in, n_levels);
-  h->intr[intrinsics_id] = in;                          // (a camera mask belongs to the previous description of this id and goes with it)
-  return 0;
-  R_CATCH()
-}
-
-/* Intrinsics::camera_mask (src/opt/intrinsics.h:104, loaded by Image::LoadImageData, image.cc:62-72): one u8 mask per pyramid level
- * of the camera, shared by all its images; an observation is dropped where the image mask OR the camera mask is non-zero
- * (visibility_estimator.cc:335-345,482-503).  level_masks[l] = width_l x height_l bytes (host or device) or NULL; level_masks == NULL
- * removes the mask.  Call after e3d_reg_set_intrinsics. */
-int e3d_reg_set_camera_mask(e3d_reg_t* h, int intrinsics_id, const uint8_t* const* level_masks) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  auto it = h->intr.find(intrinsics_id);
-  if (it == h->intr.end()) throw Error(E3D_ERR_INDEX, "no such intrinsics");
-  Intrin& in = it->second;
-  if (!level_masks) { in.cam_mask.reset(); }
-  else {
-    auto masks = std::make_shared<std::vector<DevBuf<unsigned char>>>(in.levels.size());
-    for (size_t l = 0; l < in.levels.size(); ++l) {
-      if (!level_masks[l]) continue;
-      const size_t bytes = (size_t)in.levels[l].width * (size_t)in.levels[l].height;
-      (*masks)[l].reserve(bytes);
-      copy_in((*masks)[l].p, level_masks[l], bytes, h->stream);
-    }
-    rsync(h);
-    in.cam_mask = masks;
-  }
-  for (auto& kv : h->images)
-    if (kv.second.intrinsics_id == intrinsics_id)
-      for (auto& o : kv.second.obs) o.second.rows_valid = false;
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_get_intrinsics_level(e3d_reg_t* h, int intrinsics_id, int level, int* width, int* height, float* parameters,
-                                 float* cutoff2) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  auto it = h->intr.find(intrinsics_id);
-  if (it == h->intr.end() || level < 0 || level >= (int)it->second.levels.size()) throw Error(E3D_ERR_INDEX, "no such intrinsics level");
-  const CamLevel& c = it->second.levels[level];
-  if (width) *width = c.width;
-  if (height) *height = c.height;
-  if (parameters) {
-    if (cam_unique_focal(c.model)) {
-      parameters[0] = c.fx; parameters[1] = c.cx; parameters[2] = c.cy;
-      for (int i = 3; i < it->second.n_params; ++i) parameters[i] = c.q[i - 3];
-    } else {
-      parameters[0] = c.fx; parameters[1] = c.fy; parameters[2] = c.cx; parameters[3] = c.cy;
-      for (int i = 4; i < it->second.n_params; ++i) parameters[i] = c.q[i - 4];
-    }
-  }
-  if (cutoff2) *cutoff2 = cam_is_fisheye(c.model) ? c.inner_cutoff2 : c.cutoff2;
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_set_image(e3d_reg_t* h, int image_id, int intrinsics_id, const uint8_t* const* level_pixels,
-                      const uint8_t* const* level_masks) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null argument");
-  auto it = h->intr.find(intrinsics_id);
-  if (it == h->intr.end()) throw Error(E3D_ERR_INDEX, "intrinsics not set");
-  const Intrin& in = it->second;
-  if (!h->owns(image_id)) {                     // another rank's image: only its id, intrinsics and pose are kept here
-    ImageDev& im = h->images[image_id];
-    im.intrinsics_id = intrinsics_id;
-    im.pix.clear(); im.mask.clear(); im.has_mask.clear(); im.obs.clear();
-    im.depth_scale = -1;
-    return 0;
-  }
-  if (!level_pixels) throw Error(E3D_ERR_INVALID, "null argument");
-  ImageDev& im = h->images[image_id];
-  im.intrinsics_id = intrinsics_id;
-  const int L = (int)in.levels.size();
-  im.pix.resize(L); im.mask.resize(L); im.has_mask.assign(L, false);
-  for (int l = 0; l < L; ++l) {
-    const size_t bytes = (size_t)in.levels[l].width * in.levels[l].height;
-    if (!level_pixels[l]) throw Error(E3D_ERR_INVALID, "missing pyramid level");
-    im.pix[l].reserve(bytes);
-    copy_in(im.pix[l].p, level_pixels[l], bytes, h->stream);
-    if (level_masks && level_masks[l]) {
-      im.mask[l].reserve(bytes);
-      copy_in(im.mask[l].p, level_masks[l], bytes, h->stream);
-      im.has_mask[l] = true;
-    }
-  }
-  rsync(h);
-  im.obs.clear();
-  im.depth_scale = -1;
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_set_image_pose(e3d_reg_t* h, int image_id, const float q[4], const float t[3]) {
-  R_TRYH
-  if (!h || !q || !t) throw Error(E3D_ERR_INVALID, "null argument");
-  ImageDev& im = get_image(h, image_id);
-  SE3f T;
-  T.q.w = q[0]; T.q.x = q[1]; T.q.y = q[2]; T.q.z = q[3];
-  for (int i = 0; i < 3; ++i) T.t[i] = t[i];
-  set_pose(im, T);
-  for (auto& kv : im.obs) kv.second.rows_valid = false;
-  if (!h->frames.empty()) compose_rig_poses(h);
-  return 0;
-  R_CATCH()
-}
-
-/* opt::Rig: image_T_rig of every camera of a rig (camera 0 = reference, normally identity) */
-int e3d_reg_set_rig(e3d_reg_t* h, int rig_id, int n_cameras, const float* q, const float* t) {
-  R_TRYH
-  if (!h || !q || !t || n_cameras < 1) throw Error(E3D_ERR_INVALID, "bad rig");
-  RigState r;
-  r.image_T_rig.resize(n_cameras);
-  for (int c = 0; c < n_cameras; ++c) {
-    SE3f T;
-    T.q.w = q[4 * c]; T.q.x = q[4 * c + 1]; T.q.y = q[4 * c + 2]; T.q.z = q[4 * c + 3];
-    for (int i = 0; i < 3; ++i) T.t[i] = t[3 * c + i];
-    r.image_T_rig[c] = T;
-  }
-  h->rigs[rig_id] = r;
-  if (!h->frames.empty()) compose_rig_poses(h);
-  return 0;
-  R_CATCH()
-}
-int e3d_reg_get_rig(e3d_reg_t* h, int rig_id, int camera_index, float q[4], float t[3]) {
-  R_TRYH
-  if (!h || !q || !t) throw Error(E3D_ERR_INVALID, "null argument");
-  auto it = h->rigs.find(rig_id);
-  if (it == h->rigs.end() || camera_index < 0 || camera_index >= (int)it->second.image_T_rig.size()) throw Error(E3D_ERR_INDEX, "no such rig camera");
-  const SE3f& T = it->second.image_T_rig[camera_index];
-  q[0] = T.q.w; q[1] = T.q.x; q[2] = T.q.y; q[3] = T.q.z;
-  for (int i = 0; i < 3; ++i) t[i] = T.t[i];
-  return 0;
-  R_CATCH()
-}
-/* opt::RigImages: one frame of a rig = one image per camera, image_ids[0] is the reference image.  The poses of the other
- * images become image_T_rig[camera] * image_T_global(reference). */
-int e3d_reg_add_rig_images(e3d_reg_t* h, int rig_id, const int* image_ids, int n_cameras) {
-  R_TRYH
-  if (!h || !image_ids) throw Error(E3D_ERR_INVALID, "null argument");
-  auto it = h->rigs.find(rig_id);
-  if (it == h->rigs.end() || (int)it->second.image_T_rig.size() != n_cameras) throw Error(E3D_ERR_INVALID, "rig not set or camera count mismatch");
-  RigFrame f; f.rig_id = rig_id;
-  for (int c = 0; c < n_cameras; ++c) {
-    ImageDev& im = get_image(h, image_ids[c]);
-    if (im.rig_id >= 0) throw Error(E3D_ERR_INVALID, fmt("image %d already belongs to a rig frame", image_ids[c]));
-    f.image_ids.push_back(image_ids[c]);
-  }
-  for (int c = 0; c < n_cameras; ++c) {
-    ImageDev& im = h->images.at(image_ids[c]);
-    im.rig_id = rig_id; im.camera_index = c; im.ref_image_id = image_ids[0];
-  }
-  h->frames.push_back(f);
-  compose_rig_poses(h);
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_get_image_pose(e3d_reg_t* h, int image_id, float q[4], float t[3]) {
-  R_TRYH
-  if (!h || !q || !t) throw Error(E3D_ERR_INVALID, "null argument");
-  const ImageDev& im = get_image(h, image_id);
-  q[0] = im.pose_q.q.w; q[1] = im.pose_q.q.x; q[2] = im.pose_q.q.y; q[3] = im.pose_q.q.z;
-  for (int i = 0; i < 3; ++i) t[i] = im.pose_q.t[i];
-  return 0;
-  R_CATCH()
-}
-
-}  // extern "C"
-
-namespace e3d {
+// =====================================================================================================================================
+// The operators behind the C-ABI: each throws e3d::Error and runs on the handle's stream; the entry point of the same name at the end
+// of the file adds the null checks, the handle's device and the error convention.  The driver below calls these directly.
+// =====================================================================================================================================
 // OcclusionGeometry::RenderDepthMap, mesh branch (:211-271): rasterise all meshes, then mask the occlusion boundaries
 static void render_depth_meshes(e3d_reg* h, ImageDev& im, const Intrin& in, const CamLevel& cam) {
   hipStream_t s = h->stream;
@@ -3113,116 +2878,12 @@ static void render_depth_meshes(e3d_reg* h, ImageDev& im, const Intrin& in, cons
                                                    m->vertices.p, m->normals.p, im.pose, pos, cam, h->prm.splat_radius, D.p, im.depth.p));
   }
 }
-}  // namespace e3d
 
-extern "C" {
-
-/* OcclusionGeometry::AddMesh / AddSplats (occlusion_geometry.cc:64-182): one more triangle mesh (vertices already in the
- * global frame).  compute_edges != 0 also extracts the edges used for masking occlusion boundaries (meshes: yes, splat
- * geometry: no). */
-int e3d_reg_add_occlusion_mesh(e3d_reg_t* h, const float* vertices, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
-                               int compute_edges) {
-  R_TRYH
-  if (!h || !vertices || !triangles || !n_vertices || !n_triangles) throw Error(E3D_ERR_INVALID, "empty mesh");
-  if (n_triangles >= ((size_t)1 << 31) || n_vertices >= ((size_t)1 << 32)) throw Error(E3D_ERR_INVALID, "mesh too large");
-  hipStream_t s = h->stream;
-  std::unique_ptr<MeshDev> m(new MeshDev());
-  m->n_vertices = n_vertices; m->n_triangles = n_triangles;
-  DevBuf<float> tmp; tmp.reserve(3 * n_vertices);
-  copy_in(tmp.p, vertices, sizeof(float) * 3 * n_vertices, s);
-  m->vertices.reserve(n_vertices);
-  hipLaunchKernelGGL(k_xyz_to_float4, dim3(nblk(n_vertices)), dim3(kBlock), 0, s, tmp.p, n_vertices, m->vertices.p);
-  m->triangles.reserve(3 * n_triangles);
-  copy_in(m->triangles.p, triangles, sizeof(unsigned) * 3 * n_triangles, s);
-  rsync(h);
-  for (size_t i = 0; i < 3 * n_triangles; ++i) if (triangles[i] >= n_vertices) throw Error(E3D_ERR_INDEX, "triangle refers to a missing vertex");
-  if (compute_edges) {
-    const size_t ne = 3 * n_triangles;
-    DevBuf<unsigned long long> ka, kb;
-    DevBuf<unsigned> va, vb, cnt;
-    ka.reserve(ne); kb.reserve(ne); va.reserve(ne); vb.reserve(ne); cnt.reserve(1);
-    m->normals.reserve(n_triangles);
-    hipLaunchKernelGGL(k_face_normals, dim3(nblk(n_triangles)), dim3(kBlock), 0, s, m->vertices.p, m->triangles.p, n_triangles, m->normals.p,
-                       ka.p, va.p);
-    sort_pairs_u64_u32(ka.p, kb.p, va.p, vb.p, ne, 64, h->sort_temp, s);
-    m->edges.reserve(ne);
-    E3D_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_filter_edges, dim3(nblk(ne)), dim3(kBlock), 0, s, kb.p, vb.p, ne, m->vertices.p, m->normals.p, m->edges.p, cnt.p);
-    unsigned n_edges = 0;
-    copy_out(&n_edges, cnt.p, sizeof n_edges, s);
-    rsync(h);
-    m->n_edges = n_edges;
-  }
-  h->meshes.push_back(std::move(m));
-  for (auto& kv : h->images) kv.second.depth_scale = -1;
-  return (int)h->meshes.size();
-  R_CATCH()
-}
-int e3d_reg_clear_occlusion_meshes(e3d_reg_t* h) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  h->meshes.clear();
-  for (auto& kv : h->images) kv.second.depth_scale = -1;
-  return 0;
-  R_CATCH()
-}
-/* min_occlusion_depth / max_occlusion_depth (near / far plane of the mesh renderer) and mask_occlusion_boundaries of
- * OcclusionGeometry::RenderDepthMap (occlusion_geometry.h:80-86); defaults 0.05, 100, true */
-int e3d_reg_set_occlusion_options(e3d_reg_t* h, float min_depth, float max_depth, int mask_occlusion_boundaries) {
-  R_TRYH
-  if (!h || !(min_depth > 0) || !(max_depth > min_depth)) throw Error(E3D_ERR_INVALID, "bad occlusion depth range");
-  h->min_occlusion_depth = min_depth; h->max_occlusion_depth = max_depth; h->mask_occlusion_boundaries = mask_occlusion_boundaries != 0;
-  return 0;
-  R_CATCH()
-}
-int64_t e3d_reg_occlusion_edge_count(e3d_reg_t* h, int mesh_index) {
-  R_TRYH
-  if (!h || mesh_index < 0 || mesh_index >= (int)h->meshes.size()) throw Error(E3D_ERR_INDEX, "no such mesh");
-  return (int64_t)h->meshes[mesh_index]->n_edges;
-  R_CATCH()
-}
-
-int e3d_reg_set_splat_points(e3d_reg_t* h, const float* xyz, size_t n) {
-  R_TRYH
-  if (!h || (!xyz && n)) throw Error(E3D_ERR_INVALID, "null argument");
-  DevBuf<float> tmp; tmp.reserve(3 * n);
-  copy_in(tmp.p, xyz, sizeof(float) * 3 * n, h->stream);
-  h->splat.reserve(n);
-  // The splat points are only ever reduced to a depth map (a minimum: order free), so the library keeps them in Morton order of
-  // their positions: neighbouring threads of k_splat_bin then hit neighbouring pixels, and the one atomicMin per point lands in
-  // cache lines other lanes of the wave touch too (measured: 0.41 -> see DESIGN 10.3 ms per 10 M points of a 24 MP image with the
-  // points in random order before).  E3D_REG_SPLAT_ORDER=0 keeps the caller's order.
-  static const bool reorder = [] { const char* e = getenv("E3D_REG_SPLAT_ORDER"); return !(e && e[0] == '0'); }();
-  if (reorder && n > 1 && n < ((size_t)1 << 32)) {
-    hipStream_t s = h->stream;
-    DevBuf<float> bbp, bbo;
-    bbp.reserve(6 * (size_t)kMaxBboxBlocks); bbo.reserve(6);
-    launch_bbox_aos(tmp.p, n, bbp.p, bbo.p, s);
-    float bb[6];
-    copy_out(bb, bbo.p, sizeof bb, s);
-    rsync(h);
-    float ext = 0.f;
-    for (int k = 0; k < 3; ++k) ext = std::max(ext, bb[3 + k] - bb[k]);
-    const float inv = (ext > 0.f && std::isfinite(ext)) ? 1023.f / ext : 0.f;
-    for (int k = 0; k < 2; ++k) { h->sp_keys[k].reserve(n); h->sp_vals[k].reserve(n); }
-    hipLaunchKernelGGL(k_morton_keys, dim3(nblk(n)), dim3(kBlock), 0, s, tmp.p, n, std::isfinite(bb[0]) ? bb[0] : 0.f, std::isfinite(bb[1]) ? bb[1] : 0.f,
-                       std::isfinite(bb[2]) ? bb[2] : 0.f, inv, h->sp_keys[0].p, h->sp_vals[0].p);
-    sort_pairs_u32_u32(h->sp_keys[0].p, h->sp_keys[1].p, h->sp_vals[0].p, h->sp_vals[1].p, n, 30, h->sort_temp, s);
-    hipLaunchKernelGGL(k_gather_xyz_to_float4, dim3(nblk(n)), dim3(kBlock), 0, s, tmp.p, h->sp_vals[1].p, n, h->splat.p);
-  } else {
-    hipLaunchKernelGGL(k_xyz_to_float4, dim3(nblk(n)), dim3(kBlock), 0, h->stream, tmp.p, n, h->splat.p);
-  }
-  rsync(h);
-  h->n_splat = n;
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_render_depth(e3d_reg_t* h, int image_id, int image_scale, float* depth_out) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+// OcclusionGeometry::RenderDepthMap of one image at one image scale into im.depth: the meshes, or the splat points as squares
+// (z-buffer of the points, tiles of the small splats, minimum filter); depth_out (host, may be null) gets a copy
+static void render_depth(e3d_reg* h, int image_id, int image_scale, float* depth_out) {
   ImageDev& im = get_image(h, image_id);
-  if (!h->owns(image_id)) throw Error(E3D_ERR_INVALID, fmt("image %d belongs to rank %d", image_id, e3d_reg_image_owner(h, image_id)));
+  if (!h->owns(image_id)) throw Error(E3D_ERR_INVALID, fmt("image %d belongs to rank %d", image_id, image_owner(h, image_id)));
   const Intrin& in = h->intr.at(im.intrinsics_id);
   const int lvl = std::max(0, image_scale - in.min_image_scale);
   if (lvl >= (int)in.levels.size()) throw Error(E3D_ERR_INDEX, "image scale beyond the pyramid");
@@ -3250,7 +2911,7 @@ int e3d_reg_render_depth(e3d_reg_t* h, int image_id, int image_scale, float* dep
     E3D_HIP(hipMemsetAsync(h->tile_start.p, 0, sizeof(unsigned) * n_tiles, s));
     E3D_HIP(hipMemsetAsync(h->tile_end.p, 0, sizeof(unsigned) * n_tiles, s));
     unsigned n_pairs = 0;
-    static const bool separable = [] { const char* e = getenv("E3D_REG_MIN_FILTER"); return e && !strcmp(e, "separable"); }();
+    const bool separable = reg_switches().separable_min_filter;
     const size_t zpx = (size_t)(cam.width + 2 * kSplatMax) * (cam.height + 2 * kSplatMax);
     h->zbuf.reserve(zpx);
     {
@@ -3296,14 +2957,39 @@ int e3d_reg_render_depth(e3d_reg_t* h, int image_id, int image_scale, float* dep
   }
   if (depth_out) { copy_out(depth_out, im.depth.p, sizeof(float) * px, h->stream); rsync(h); }     // (else: every reader runs on the stream)
   im.depth_scale = image_scale;
-  return 0;
-  R_CATCH()
 }
 
-int64_t e3d_reg_observe(e3d_reg_t* h, int image_id, int point_scale, int image_scale, int border_size, const uint32_t* indices,
-                        size_t n_indices) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+// The candidates an evaluation pass kept (h->valid, h->tx / ty / ts; per-block counts in h->block_counts for an all-points pass), counted
+// and compacted into O; true if the compaction has written S.row_of_point for the new list
+static bool compact_observations(e3d_reg* h, PointScale& S, Obs& O, size_t count, bool all) {
+  hipStream_t s = h->stream;
+  const size_t nb = div_up(count, kBlock);
+  bool map_written = false;
+  h->chunk_sum.reserve(div_up(nb, 256) + 1); h->chunk_d2.reserve(div_up(nb, 256) + 1);
+  h->d_total.reserve(2); h->d_total_d2.reserve(1);
+  {
+    KT kt(h, "obs.scan", (double)count);
+    // (an all-points pass: k_obs_eval has written the per-block counts itself)
+    launch_match_scan(all ? nullptr : h->valid.p, nullptr, count, h->block_counts.p, h->block_offsets.p, h->block_d2.p, h->chunk_sum.p,
+                      h->chunk_d2.p, h->d_total.p, h->d_total_d2.p, s);
+  }
+  unsigned long long total = 0;
+  read_back(h, &total, h->d_total.p, sizeof total);
+  O.n = (size_t)total;
+  O.idx.reserve(O.n); O.x.reserve(O.n); O.y.reserve(O.n); O.s.reserve(O.n);
+  if (O.n) {
+    KT kt(h, "obs.compact", (double)count);
+    hipLaunchKernelGGL(k_obs_compact, dim3(nblk(count)), dim3(kBlock), 0, s, h->valid.p, h->tx.p, h->ty.p, h->ts.p, count,
+                       h->block_offsets.p, O.idx.p, O.x.p, O.y.p, O.s.p, all ? S.row_of_point.p : nullptr);
+    map_written = all;
+  }
+  return map_written;
+}
+
+// The observations of one (image, point scale): every point of the scale tested against the rendered depth map, the masks and
+// the image border (indices == nullptr), or the listed points re-projected; compacted into im.obs[point_scale].  Returns their number.
+static size_t observe(e3d_reg* h, int image_id, int point_scale, int image_scale, int border_size, const uint32_t* indices,
+                      size_t n_indices) {
   hipStream_t s = h->stream;
   ImageDev& im = get_image(h, image_id);
   PointScale& S = get_scale(h, point_scale);
@@ -3350,24 +3036,7 @@ int64_t e3d_reg_observe(e3d_reg_t* h, int image_id, int point_scale, int image_s
       O.n = count;
       std::swap(O.idx, h->cand); std::swap(O.x, h->tx); std::swap(O.y, h->ty); std::swap(O.s, h->ts);
     } else {
-      h->chunk_sum.reserve(div_up(nb, 256) + 1); h->chunk_d2.reserve(div_up(nb, 256) + 1);
-      h->d_total.reserve(2); h->d_total_d2.reserve(1);
-      {
-        KT kt(h, "obs.scan", (double)count);
-        // (an all-points pass: k_obs_eval has written the per-block counts itself)
-        launch_match_scan(all ? nullptr : h->valid.p, nullptr, count, h->block_counts.p, h->block_offsets.p, h->block_d2.p, h->chunk_sum.p,
-                          h->chunk_d2.p, h->d_total.p, h->d_total_d2.p, s);
-      }
-      unsigned long long total = 0;
-      read_back(h, &total, h->d_total.p, sizeof total);
-      O.n = (size_t)total;
-      O.idx.reserve(O.n); O.x.reserve(O.n); O.y.reserve(O.n); O.s.reserve(O.n);
-      if (O.n) {
-        KT kt(h, "obs.compact", (double)count);
-        hipLaunchKernelGGL(k_obs_compact, dim3(nblk(count)), dim3(kBlock), 0, s, h->valid.p, h->tx.p, h->ty.p, h->ts.p, count,
-                           h->block_offsets.p, O.idx.p, O.x.p, O.y.p, O.s.p, all ? S.row_of_point.p : nullptr);
-        map_written = all;
-      }
+      map_written = compact_observations(h, S, O, count, all);
     }
   }
   if (flags_kept && O.n == count) {
@@ -3375,69 +3044,72 @@ int64_t e3d_reg_observe(e3d_reg_t* h, int image_id, int point_scale, int image_s
   } else {
     finish_observations(h, S, O, map_written);
   }
-  return (int64_t)O.n;        // (the stream is not synchronised here: every reader of O runs on it)
-  R_CATCH()
+  return O.n;        // (the stream is not synchronised here: every reader of O runs on it)
 }
 
-int e3d_reg_get_observations(e3d_reg_t* h, int image_id, int point_scale, uint32_t* idx, float* x, float* y, float* scale,
-                             uint8_t* flags) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  Obs& O = get_obs(get_image(h, image_id), point_scale);
-  if (idx) copy_out(idx, O.idx.p, sizeof(unsigned) * O.n, h->stream);
-  if (x) copy_out(x, O.x.p, sizeof(float) * O.n, h->stream);
-  if (y) copy_out(y, O.y.p, sizeof(float) * O.n, h->stream);
-  if (scale) copy_out(scale, O.s.p, sizeof(float) * O.n, h->stream);
-  if (flags) copy_out(flags, O.flags.p, O.n, h->stream);
-  rsync(h);
-  return 0;
-  R_CATCH()
-}
+// Row ranges of the kernels with per-thread accumulators (k_reg_pass2, k_reg_depth_acc) by local system size: every launch keeps
+// <= 75 accumulators.  E3D_ROWS_<V>(K) runs K(V, first row, end row, first launch of the system) for each launch.  A dispatch names
+// the sizes it has kernels for, in its own order (the order of the instantiations is the order of the kernels in the code object).
+#define E3D_ROWS_9(K) K(9, 0, 9, true);
+#define E3D_ROWS_10(K) K(10, 0, 10, true);
+#define E3D_ROWS_11(K) K(11, 0, 5, true); K(11, 5, 11, false);
+#define E3D_ROWS_13(K) K(13, 0, 4, true); K(13, 4, 13, false);
+#define E3D_ROWS_14(K) K(14, 0, 4, true); K(14, 4, 14, false);
+#define E3D_ROWS_15(K) K(15, 0, 3, true); K(15, 3, 8, false); K(15, 8, 15, false);
+#define E3D_ROWS_16(K) K(16, 0, 3, true); K(16, 3, 8, false); K(16, 8, 16, false);
+#define E3D_ROWS_17(K) K(17, 0, 3, true); K(17, 3, 8, false); K(17, 8, 17, false);
+#define E3D_ROWS_18(K) K(18, 0, 3, true); K(18, 3, 7, false); K(18, 7, 18, false);
+#define E3D_ROWS_19(K) K(19, 0, 2, true); K(19, 2, 6, false); K(19, 6, 11, false); K(19, 11, 19, false);
+#define E3D_ROWS_20(K) K(20, 0, 2, true); K(20, 2, 6, false); K(20, 6, 11, false); K(20, 11, 20, false);
+#define E3D_ROWS_24(K) K(24, 0, 2, true); K(24, 2, 5, false); K(24, 5, 9, false); K(24, 9, 14, false); K(24, 14, 24, false);
+#define E3D_ROWS_CASE(V_, K) case V_: E3D_ROWS_##V_(K) break;
 
-int e3d_reg_set_observations(e3d_reg_t* h, int image_id, int point_scale, size_t n, const uint32_t* idx, const float* x,
-                             const float* y, const float* scale) {
-  R_TRYH
-  if (!h || (n && (!idx || !x || !y || !scale))) throw Error(E3D_ERR_INVALID, "null argument");
-  ImageDev& im = get_image(h, image_id);
-  PointScale& S = get_scale(h, point_scale);
-  Obs& O = im.obs[point_scale];
-  O.active = true;
-  O.n = n;
-  O.idx.reserve(n); O.x.reserve(n); O.y.reserve(n); O.s.reserve(n);
-  copy_in(O.idx.p, idx, sizeof(unsigned) * n, h->stream); copy_in(O.x.p, x, sizeof(float) * n, h->stream);
-  copy_in(O.y.p, y, sizeof(float) * n, h->stream); copy_in(O.s.p, scale, sizeof(float) * n, h->stream);
-  O.inten_valid = false;
-  finish_observations(h, S, O);
-  rsync(h);
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_pass1(e3d_reg_t* h, int image_id, int point_scale, float* intensities, float* j_intrinsics, float* j_pose) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  ImageDev& im = get_image(h, image_id);
-  PointScale& S = get_scale(h, point_scale);
-  Obs& O = get_obs(im, point_scale);
-  prepare_rows(h, im, S, O);
-  const int I = cam_param_count(image_model(h, im));
-  const int off_pose = 1 + I + (im.dependent() ? 6 : 0);
-  const size_t stride = 4 * (size_t)rows4(local_unknowns(h, im));
-  std::vector<float> rows(stride * O.n);
-  copy_out(rows.data(), O.rows.p, sizeof(float) * stride * O.n, h->stream);
-  rsync(h);
-  for (size_t i = 0; i < O.n; ++i) {
-    const float* r = rows.data() + stride * i;
-    if (intensities) intensities[i] = r[0];
-    if (j_intrinsics) for (int c = 0; c < I; ++c) j_intrinsics[(size_t)I * i + c] = r[1 + c];
-    if (j_pose) for (int c = 0; c < 6; ++c) j_pose[6 * i + c] = r[off_pose + c];
+// Pass 2 of one observation list into h->partial; returns the number of partials per entry of the slot
+static int launch_pass2(e3d_reg* h, const PointScale& S, const Obs& O, int V, int nb) {
+  hipStream_t s = h->stream;
+  const RegSwitches& sw = reg_switches();
+  const RegWeights w = reg_weights(h);
+  // matrix-core kernel: systems that would need several per-thread-accumulator launches (V > 10), default neighbour count
+  if (sw.pass2 != RegSwitches::valu && (V > 10 || sw.pass2_mfma10) && h->prm.point_neighbor_count == 5) {
+    const int n_partials = nb * (kBlock / kWave);       // one partial per wave
+    h->partial.reserve((size_t)n_partials * reg_slot(V));
+    // Default: the f64 matrix instruction on exact products -- every term at least as accurate as the reference's
+    // fl32(fl32(w J_i) J_j), all sums in f64 as in intrinsics_and_pose_optimizer.cc:1246-1247.  E3D_REG_PASS2 = tile32 / mfma32: the
+    // narrower f32-chain kernels (opt-in: faster, ~1e-9 of the entry scale away).
+    auto launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, dim3(nb), dim3(kBlock), 0, s, O.rows.p, O.idx.p, O.flags.p, O.n, O.nrow.p, S.fixed_desc.p, S.var_desc.p,
+                         S.obs_counts.p, w, h->partial.p);
+    };
+#define E3D_PASS2M(V_)                                                                                     \
+  case V_:                                                                                                 \
+    if (sw.pass2 == RegSwitches::mfma64) launch(k_reg_pass2_mfma<5, V_>);                                  \
+    else if constexpr ((V_) <= 16 || (V_) == 18) {                                                         \
+      if (sw.pass2 == RegSwitches::mfma32) launch(k_reg_pass2_mfma32<5, V_>);                              \
+      else launch(k_reg_pass2_tile32<5, V_>);                                                              \
+    } else launch(k_reg_pass2_mfma32<5, V_>);                                                              \
+    break;
+    switch (V) {
+      E3D_PASS2M(10) E3D_PASS2M(11) E3D_PASS2M(13) E3D_PASS2M(15) E3D_PASS2M(19) E3D_PASS2M(14) E3D_PASS2M(16) E3D_PASS2M(17) E3D_PASS2M(18)
+      E3D_PASS2M(20) E3D_PASS2M(24)
+      default: throw Error(E3D_ERR_INVALID, "unsupported local system size");
+    }
+#undef E3D_PASS2M
+    return n_partials;
   }
-  return 0;
-  R_CATCH()
+  // E3D_REG_PASS2=valu, small systems, other neighbour counts: per-thread accumulators
+#define E3D_PASS2(V_, R0_, R1_, B_)                                                                                              \
+  hipLaunchKernelGGL((k_reg_pass2<8, V_, R0_, R1_, B_>), dim3(nb), dim3(kBlock), 0, s, O.rows.p, O.idx.p, O.flags.p, O.n, O.nrow.p, \
+                     h->prm.point_neighbor_count, S.fixed_desc.p, S.var_desc.p, S.obs_counts.p, w, h->partial.p)
+  switch (V) {
+    E3D_ROWS_CASE(9, E3D_PASS2) E3D_ROWS_CASE(10, E3D_PASS2) E3D_ROWS_CASE(13, E3D_PASS2) E3D_ROWS_CASE(15, E3D_PASS2)
+    E3D_ROWS_CASE(19, E3D_PASS2) E3D_ROWS_CASE(11, E3D_PASS2) E3D_ROWS_CASE(14, E3D_PASS2) E3D_ROWS_CASE(16, E3D_PASS2)
+    E3D_ROWS_CASE(17, E3D_PASS2) E3D_ROWS_CASE(18, E3D_PASS2) E3D_ROWS_CASE(20, E3D_PASS2) E3D_ROWS_CASE(24, E3D_PASS2)
+    default: throw Error(E3D_ERR_INVALID, "unsupported local system size");
+  }
+#undef E3D_PASS2
+  return nb;
 }
 
-}  // extern "C"
-namespace e3d {
 // The accumulation of one (image, point scale): pass 1, pass 2 and the reduction of the partials enqueued; the reg_slot(V) numbers
 // {upper triangle of H by rows, b, fixed sum, variable sum, fixed count, variable count} land at d_out (device).  e3d_reg_accumulate
 // reads them at once; the optimizer's driver enqueues every image of an Apply and reads all of them with one copy.
@@ -3450,87 +3122,16 @@ static int accumulate_enqueue(e3d_reg* h, int image_id, int point_scale, double*
   h->t_pass1->start(s);
   { KT kt(h, "accumulate.pass1", (double)O.n); prepare_rows(h, im, S, O); }
   h->t_pass1->stop(s);
-  std::unique_ptr<KT> kt2(new KT(h, "accumulate.pass2", (double)O.n));
-  // one resident round of workgroups (two of these 256-thread groups fit a CU): 512 on MI355X; measured 0.684 / 0.694 / 0.704 / 0.711 ms
-  // for 512 / 1024 / 2048 / 4096 at the configs[3] shape
-  static const int max_blocks = [] {
-    if (const char* e = getenv("E3D_REG_PASS2_BLOCKS")) return std::max(8, atoi(e));
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) return 1024;
-    return 2 * cus;
-  }();
-  const int nb = (int)std::min<size_t>(std::max<size_t>(div_up(O.n, kBlock * 4), 1), (size_t)max_blocks);
+  const int nb = partial_blocks(O.n, (size_t)reg_switches().pass2_blocks);
   const int V = local_unknowns(h, im), slot = reg_slot(V);
   h->partial.reserve((size_t)nb * slot); h->red.reserve(slot);
-  const RegWeights w{h->prm.robust_weighting_type, h->prm.robust_weighting_parameter, h->prm.fixed_residuals_weight,
-                     h->prm.variable_residuals_weight};
-  static const bool valu_pass2 = [] { const char* e = getenv("E3D_REG_PASS2"); return e && !strcmp(e, "valu"); }();
-  int n_partials = nb;
-  // matrix-core kernel: systems that would need several per-thread-accumulator launches (V > 10), default neighbour count
-  static const bool mfma10 = getenv("E3D_REG_PASS2_MFMA10") != nullptr;     // experiment: the single-launch system on the matrix cores too
-  h->t_pass2->start(s);
-  if (!valu_pass2 && (V > 10 || mfma10) && h->prm.point_neighbor_count == 5) {
-    n_partials = nb * (kBlock / kWave);       // one partial per wave
-    h->partial.reserve((size_t)n_partials * slot);
-    // Default: the f64 matrix instruction on exact products -- every term at least as accurate as the reference's
-    // fl32(fl32(w J_i) J_j), all sums in f64 as in intrinsics_and_pose_optimizer.cc:1246-1247.  E3D_REG_PASS2 = tile32 / mfma32: the
-    // narrower f32-chain kernels (opt-in: faster, ~1e-9 of the entry scale away).
-    static const std::string p2 = [] { const char* e = getenv("E3D_REG_PASS2"); return std::string(e ? e : ""); }();
-    static const bool tile32 = p2 == "tile32", mfma32g = p2 == "mfma32";
-    static const bool mfma64 = !(tile32 || mfma32g);
-#define E3D_PASS2M(V_)                                                                                                         \
-  if (mfma64)                                                                                                                  \
-    hipLaunchKernelGGL((k_reg_pass2_mfma<5, V_>), dim3(nb), dim3(kBlock), 0, s, O.rows.p, O.idx.p, O.flags.p, O.n, O.nrow.p,   \
-                       S.fixed_desc.p, S.var_desc.p, S.obs_counts.p, w, h->partial.p);                                          \
-  else if constexpr ((V_) <= 16 || (V_) == 18) {                                                                               \
-    if (mfma32g)                                                                                                               \
-      hipLaunchKernelGGL((k_reg_pass2_mfma32<5, V_>), dim3(nb), dim3(kBlock), 0, s, O.rows.p, O.idx.p, O.flags.p, O.n, O.nrow.p, \
-                         S.fixed_desc.p, S.var_desc.p, S.obs_counts.p, w, h->partial.p);                                        \
-    else                                                                                                                       \
-      hipLaunchKernelGGL((k_reg_pass2_tile32<5, V_>), dim3(nb), dim3(kBlock), 0, s, O.rows.p, O.idx.p, O.flags.p, O.n, O.nrow.p, \
-                         S.fixed_desc.p, S.var_desc.p, S.obs_counts.p, w, h->partial.p);                                        \
-  } else                                                                                                                       \
-    hipLaunchKernelGGL((k_reg_pass2_mfma32<5, V_>), dim3(nb), dim3(kBlock), 0, s, O.rows.p, O.idx.p, O.flags.p, O.n, O.nrow.p, \
-                       S.fixed_desc.p, S.var_desc.p, S.obs_counts.p, w, h->partial.p)
-    switch (V) {
-      case 10: E3D_PASS2M(10); break;
-      case 11: E3D_PASS2M(11); break;
-      case 13: E3D_PASS2M(13); break;
-      case 15: E3D_PASS2M(15); break;
-      case 19: E3D_PASS2M(19); break;
-      case 14: E3D_PASS2M(14); break;
-      case 16: E3D_PASS2M(16); break;
-      case 17: E3D_PASS2M(17); break;
-      case 18: E3D_PASS2M(18); break;
-      case 20: E3D_PASS2M(20); break;
-      case 24: E3D_PASS2M(24); break;
-      default: throw Error(E3D_ERR_INVALID, "unsupported local system size");
-    }
-#undef E3D_PASS2M
-  } else {
-#define E3D_PASS2(V_, R0_, R1_, B_)                                                                                              \
-  hipLaunchKernelGGL((k_reg_pass2<8, V_, R0_, R1_, B_>), dim3(nb), dim3(kBlock), 0, s, O.rows.p, O.idx.p, O.flags.p, O.n, O.nrow.p, \
-                     h->prm.point_neighbor_count, S.fixed_desc.p, S.var_desc.p, S.obs_counts.p, w, h->partial.p)
-  switch (V) {     // E3D_REG_PASS2=valu: per-thread accumulators; row ranges chosen so that every launch keeps <= 75 of them
-    case 9: E3D_PASS2(9, 0, 9, true); break;
-    case 10: E3D_PASS2(10, 0, 10, true); break;
-    case 13: E3D_PASS2(13, 0, 4, true); E3D_PASS2(13, 4, 13, false); break;
-    case 15: E3D_PASS2(15, 0, 3, true); E3D_PASS2(15, 3, 8, false); E3D_PASS2(15, 8, 15, false); break;
-    case 19: E3D_PASS2(19, 0, 2, true); E3D_PASS2(19, 2, 6, false); E3D_PASS2(19, 6, 11, false); E3D_PASS2(19, 11, 19, false); break;
-    case 11: E3D_PASS2(11, 0, 5, true); E3D_PASS2(11, 5, 11, false); break;
-    case 14: E3D_PASS2(14, 0, 4, true); E3D_PASS2(14, 4, 14, false); break;
-    case 16: E3D_PASS2(16, 0, 3, true); E3D_PASS2(16, 3, 8, false); E3D_PASS2(16, 8, 16, false); break;
-    case 17: E3D_PASS2(17, 0, 3, true); E3D_PASS2(17, 3, 8, false); E3D_PASS2(17, 8, 17, false); break;
-    case 18: E3D_PASS2(18, 0, 3, true); E3D_PASS2(18, 3, 7, false); E3D_PASS2(18, 7, 18, false); break;
-    case 20: E3D_PASS2(20, 0, 2, true); E3D_PASS2(20, 2, 6, false); E3D_PASS2(20, 6, 11, false); E3D_PASS2(20, 11, 20, false); break;
-    case 24: E3D_PASS2(24, 0, 2, true); E3D_PASS2(24, 2, 5, false); E3D_PASS2(24, 5, 9, false); E3D_PASS2(24, 9, 14, false);
-             E3D_PASS2(24, 14, 24, false); break;
-    default: throw Error(E3D_ERR_INVALID, "unsupported local system size");
+  int n_partials;
+  {
+    KT kt2(h, "accumulate.pass2", (double)O.n);
+    h->t_pass2->start(s);
+    n_partials = launch_pass2(h, S, O, V, nb);
+    h->t_pass2->stop(s);
   }
-#undef E3D_PASS2
-  }
-  h->t_pass2->stop(s);
-  kt2.reset();
   hipLaunchKernelGGL(k_reg_reduce, dim3(slot), dim3(kWave), 0, s, h->partial.p, n_partials, slot, use_own_red ? h->red.p : d_out);
   h->pass_observations += (double)O.n; h->pass_calls += 1;
   return V;
@@ -3546,49 +3147,7 @@ static void accumulate_unpack(int V, const double* r, double* H, double* b, doub
   sums[0] = r[NH + V]; sums[1] = r[NH + V + 1];
   counts[0] = (int64_t)r[NH + V + 2]; counts[1] = (int64_t)r[NH + V + 3];
 }
-}  // namespace e3d
-extern "C" {
 
-int e3d_reg_accumulate(e3d_reg_t* h, int image_id, int point_scale, double* H, double* b, double sums[2], int64_t counts[2]) {
-  R_TRYH
-  if (!h || !H || !b || !sums || !counts) throw Error(E3D_ERR_INVALID, "null argument");
-  const int V = accumulate_enqueue(h, image_id, point_scale, nullptr, true);
-  const int slot = reg_slot(V);
-  std::vector<double> r(slot);
-  read_back(h, r.data(), h->red.p, sizeof(double) * slot);
-  h->pass1_ms += h->t_pass1->ms(); h->pass2_ms += h->t_pass2->ms();      // (the pass timers of the call just made: the stream is idle)
-  accumulate_unpack(V, r.data(), H, b, sums, counts);
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_kernel_times(e3d_reg_t* h, double out[4], int reset) {
-  R_TRYH
-  if (!h || !out) throw Error(E3D_ERR_INVALID, "null argument");
-  out[0] = h->pass1_ms; out[1] = h->pass2_ms; out[2] = h->pass_observations; out[3] = h->pass_calls;
-  if (reset) { h->pass1_ms = h->pass2_ms = h->pass_observations = h->pass_calls = 0; }
-  return 0;
-  R_CATCH()
-}
-
-int e3d_reg_profile(e3d_reg_t* h, int enable, char* out, size_t capacity) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  if (out && capacity) {
-    std::string t;
-    for (const auto& kv : h->profile_ms) t += kv.first + "=" + fmt("%.4f", kv.second) + ";";
-    h->kflush();
-    for (const auto& kv : h->kgroups) t += "k:" + kv.first + "=" + fmt("%.4f,%lld,%.0f", kv.second.ms, kv.second.calls, kv.second.units) + ";";
-    std::snprintf(out, capacity, "%s", t.c_str());
-  }
-  if (enable != (h->profile_on ? 1 : 0)) { h->profile_ms.clear(); h->kflush(); h->kgroups.clear(); }
-  h->profile_on = enable != 0;
-  return 0;
-  R_CATCH()
-}
-
-}  // extern "C"
-namespace e3d {
 // CostCalculator::ComputeCost of one (image, point scale): kernels enqueued, the four results {fixed sum, variable sum, fixed count,
 // variable count} land in d_out[0..3] (device); the callers of the driver read many of them with one copy
 static void cost_enqueue(e3d_reg* h, int image_id, int point_scale, double* d_out) {
@@ -3598,10 +3157,9 @@ static void cost_enqueue(e3d_reg* h, int image_id, int point_scale, double* d_ou
   Obs& O = get_obs(im, point_scale);
   obs_intensities(h, im, O);
   // enough blocks for full occupancy (the loop is a chain of dependent gathers): 8 waves per SIMD on 256 CUs = 8192 blocks
-  const int nb = (int)std::min<size_t>(std::max<size_t>(div_up(O.n, kBlock * 4), 1), 8192);
+  const int nb = partial_blocks(O.n, 8192);
   h->partial.reserve((size_t)nb * 4);
-  const RegWeights w{h->prm.robust_weighting_type, h->prm.robust_weighting_parameter, h->prm.fixed_residuals_weight,
-                     h->prm.variable_residuals_weight};
+  const RegWeights w = reg_weights(h);
   KT kt(h, "cost", (double)O.n);
   if (h->prm.point_neighbor_count == 5)
     hipLaunchKernelGGL(k_reg_cost<5>, dim3(nb), dim3(kBlock), 0, s, O.inten.p, O.idx.p, O.flags.p, O.n, O.nrow.p,
@@ -3611,44 +3169,7 @@ static void cost_enqueue(e3d_reg* h, int image_id, int point_scale, double* d_ou
                        h->prm.point_neighbor_count, S.fixed_desc.p, S.var_desc.p, S.obs_counts.p, w, h->partial.p);
   hipLaunchKernelGGL(k_reg_reduce, dim3(4), dim3(kWave), 0, s, h->partial.p, nb, 4, d_out);
 }
-}  // namespace e3d
-extern "C" {
 
-int e3d_reg_cost(e3d_reg_t* h, int image_id, int point_scale, double sums[2], int64_t counts[2]) {
-  R_TRYH
-  if (!h || !sums || !counts) throw Error(E3D_ERR_INVALID, "null argument");
-  h->red.reserve(4);
-  cost_enqueue(h, image_id, point_scale, h->red.p);
-  double r[4];
-  read_back(h, r, h->red.p, sizeof r);
-  sums[0] = r[0]; sums[1] = r[1]; counts[0] = (int64_t)r[2]; counts[1] = (int64_t)r[3];
-  return 0;
-  R_CATCH()
-}
-
-// ---- depth residuals -------------------------------------------------------------------------------------------------------------
-/* Problem::SetFixedDepthMaps for one image (problem.cc:593-595): one f32 depth map per pyramid level of the image's camera
- * (level_depths[l]: width_l x height_l floats, host or device memory); level_depths == NULL removes them. */
-int e3d_reg_set_depth_maps(e3d_reg_t* h, int image_id, const float* const* level_depths) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  ImageDev& im = get_image(h, image_id);
-  const Intrin& in = h->intr.at(im.intrinsics_id);
-  im.depth_maps.clear();
-  if (!level_depths) return 0;
-  im.depth_maps.resize(in.levels.size());
-  for (size_t l = 0; l < in.levels.size(); ++l) {
-    if (!level_depths[l]) throw Error(E3D_ERR_INVALID, "e3d_reg_set_depth_maps: every pyramid level needs a depth map");
-    const size_t px = (size_t)in.levels[l].width * (size_t)in.levels[l].height;
-    im.depth_maps[l].reserve(px);
-    copy_in(im.depth_maps[l].p, level_depths[l], sizeof(float) * px, h->stream);
-  }
-  rsync(h);
-  return 0;
-  R_CATCH()
-}
-
-namespace e3d {
 static DepthPyramid make_depth_pyramid(e3d_reg* h, const ImageDev& im, int image_id) {
   const Intrin& in = h->intr.at(im.intrinsics_id);
   if (im.depth_maps.size() != in.levels.size())
@@ -3659,63 +3180,50 @@ static DepthPyramid make_depth_pyramid(e3d_reg* h, const ImageDev& im, int image
   for (size_t l = 0; l < in.levels.size(); ++l) D.map[l] = im.depth_maps[l].p;
   return D;
 }
-}  // namespace e3d
 
-/* The depth residuals of one (image, point scale): normal equations of the V = I + 6 local unknowns [intrinsics, pose] (row-major V x V,
- * upper triangle), b, the sum of the robust residuals and their count (intrinsics_and_pose_optimizer.cc:747-757, 1150-1214, 1219-1296). */
-int e3d_reg_depth_accumulate(e3d_reg_t* h, int image_id, int point_scale, double* H, double* b, double* sum, int64_t* count) {
-  R_TRYH
-  if (!h || !H || !b || !sum || !count) throw Error(E3D_ERR_INVALID, "null argument");
+// The depth residuals of one (image, point scale): normal equations of the V = I + 6 local unknowns [intrinsics, pose] (row-major V x V,
+// upper triangle), b, the sum of the robust residuals and their count (intrinsics_and_pose_optimizer.cc:747-757, 1150-1214, 1219-1296)
+static void depth_accumulate(e3d_reg* h, int image_id, int point_scale, double* H, double* b, double* sum, int64_t* count) {
   hipStream_t s = h->stream;
   ImageDev& im = get_image(h, image_id);
   PointScale& S = get_scale(h, point_scale);
   Obs& O = get_obs(im, point_scale);
   const DepthPyramid D = make_depth_pyramid(h, im, image_id);
   const int model = image_model(h, im);
-  const int V = h->intr.at(im.intrinsics_id).n_params + 6, NH = reg_h(V), slot = reg_slot(V);
+  const int V = h->intr.at(im.intrinsics_id).n_params + 6, slot = reg_slot(V);
   O.drows.reserve((size_t)rows4(V) * std::max<size_t>(O.n, 1));
   const float4 quat = make_float4(im.pose_q.q.w, im.pose_q.q.x, im.pose_q.q.y, im.pose_q.q.z);
   if (O.n)
     E3D_CAM_SWITCH(model, hipLaunchKernelGGL(k_reg_depth_rows<M>, dim3(nblk(O.n)), dim3(kBlock), 0, s, S.pts.p, S.radius, im.pose, quat,
                                              make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p, O.s.p, O.n, O.drows.p));
-  const int nb = (int)std::min<size_t>(std::max<size_t>(div_up(O.n, kBlock * 4), 1), 1024);
+  const int nb = partial_blocks(O.n, 1024);
   h->partial.reserve((size_t)nb * slot); h->red.reserve(slot);
   const int rt = h->prm.depth_robust_weighting_type;
   const float rp = h->prm.depth_robust_weighting_parameter, dw = h->prm.depth_residuals_weight;
 #define E3D_DEPTH(V_, R0_, R1_, B_) \
   hipLaunchKernelGGL((k_reg_depth_acc<V_, R0_, R1_, B_>), dim3(nb), dim3(kBlock), 0, s, O.drows.p, O.n, rt, rp, dw, h->partial.p)
-  switch (V) {     // row ranges: <= 75 accumulators per launch, as for the per-thread colour kernel
-    case 9: E3D_DEPTH(9, 0, 9, true); break;
-    case 10: E3D_DEPTH(10, 0, 10, true); break;
-    case 11: E3D_DEPTH(11, 0, 5, true); E3D_DEPTH(11, 5, 11, false); break;
-    case 13: E3D_DEPTH(13, 0, 4, true); E3D_DEPTH(13, 4, 13, false); break;
-    case 14: E3D_DEPTH(14, 0, 4, true); E3D_DEPTH(14, 4, 14, false); break;
-    case 18: E3D_DEPTH(18, 0, 3, true); E3D_DEPTH(18, 3, 7, false); E3D_DEPTH(18, 7, 18, false); break;
+  switch (V) {     // (the sizes of the camera models without a rig)
+    E3D_ROWS_CASE(9, E3D_DEPTH) E3D_ROWS_CASE(10, E3D_DEPTH) E3D_ROWS_CASE(11, E3D_DEPTH) E3D_ROWS_CASE(13, E3D_DEPTH)
+    E3D_ROWS_CASE(14, E3D_DEPTH) E3D_ROWS_CASE(18, E3D_DEPTH)
     default: throw Error(E3D_ERR_INVALID, "unsupported local system size");
   }
 #undef E3D_DEPTH
   hipLaunchKernelGGL(k_reg_reduce, dim3(slot), dim3(kWave), 0, s, h->partial.p, nb, slot, h->red.p);
   std::vector<double> r(slot);
   read_back(h, r.data(), h->red.p, sizeof(double) * slot);
-  std::fill(H, H + V * V, 0.0);
-  int e = 0;
-  for (int i = 0; i < V; ++i) for (int j = i; j < V; ++j) H[i * V + j] = r[e++];
-  for (int i = 0; i < V; ++i) b[i] = r[NH + i];
-  *sum = r[NH + V]; *count = (int64_t)r[NH + V + 2];
-  return 0;
-  R_CATCH()
+  double sums[2]; int64_t counts[2];      // {depth, unused}
+  accumulate_unpack(V, r.data(), H, b, sums, counts);
+  *sum = sums[0]; *count = counts[0];
 }
 
-/* CostCalculator, depth part (cost_calculator.cc:221-245): sum of the robust depth residuals of the stored observations, and their count */
-int e3d_reg_depth_cost(e3d_reg_t* h, int image_id, int point_scale, double* sum, int64_t* count) {
-  R_TRYH
-  if (!h || !sum || !count) throw Error(E3D_ERR_INVALID, "null argument");
+// CostCalculator, depth part (cost_calculator.cc:221-245): sum of the robust depth residuals of the stored observations, and their count
+static void depth_cost(e3d_reg* h, int image_id, int point_scale, double* sum, int64_t* count) {
   hipStream_t s = h->stream;
   ImageDev& im = get_image(h, image_id);
   PointScale& S = get_scale(h, point_scale);
   Obs& O = get_obs(im, point_scale);
   const DepthPyramid D = make_depth_pyramid(h, im, image_id);
-  const int nb = (int)std::min<size_t>(std::max<size_t>(div_up(O.n, kBlock * 4), 1), 1024);
+  const int nb = partial_blocks(O.n, 1024);
   h->partial.reserve((size_t)nb * 2); h->red.reserve(2);
   const float4 quat = make_float4(im.pose_q.q.w, im.pose_q.q.x, im.pose_q.q.y, im.pose_q.q.z);
   hipLaunchKernelGGL(k_reg_depth_cost, dim3(nb), dim3(kBlock), 0, s, S.pts.p, im.pose, quat, make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p,
@@ -3724,13 +3232,9 @@ int e3d_reg_depth_cost(e3d_reg_t* h, int image_id, int point_scale, double* sum,
   double r[2];
   read_back(h, r, h->red.p, sizeof r);
   *sum = r[0]; *count = (int64_t)r[1];
-  return 0;
-  R_CATCH()
 }
 
-int e3d_reg_color_begin(e3d_reg_t* h, int point_scale) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+static void color_begin(e3d_reg* h, int point_scale) {
   PointScale& S = get_scale(h, point_scale);
   {
     KT kt(h, "color.clear", (double)S.n);
@@ -3738,11 +3242,7 @@ int e3d_reg_color_begin(e3d_reg_t* h, int point_scale) {
     E3D_HIP(hipMemsetAsync(S.obs_counts.p, 0, sizeof(int) * S.n, h->stream));
   }
   rsync(h);
-  return 0;
-  R_CATCH()
 }
-}  // extern "C"
-namespace e3d {
 static void color_accumulate_enqueue(e3d_reg* h, int image_id, int point_scale) {
   ImageDev& im = get_image(h, image_id);
   PointScale& S = get_scale(h, point_scale);
@@ -3756,19 +3256,7 @@ static void color_accumulate_enqueue(e3d_reg* h, int image_id, int point_scale) 
     hipLaunchKernelGGL(k_color_accumulate<0>, dim3(nblk(O.n)), dim3(kBlock), 0, h->stream, O.inten.p, O.idx.p, O.flags.p, O.n,
                        O.nrow.p, h->prm.point_neighbor_count, S.var_desc.p, S.obs_counts.p);
 }
-}  // namespace e3d
-extern "C" {
-int e3d_reg_color_accumulate(e3d_reg_t* h, int image_id, int point_scale) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  color_accumulate_enqueue(h, image_id, point_scale);
-  rsync(h);
-  return 0;
-  R_CATCH()
-}
-int e3d_reg_color_finish(e3d_reg_t* h, int point_scale) {
-  R_TRYH
-  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+static void color_finish(e3d_reg* h, int point_scale) {
   PointScale& S = get_scale(h, point_scale);
   {
     KT kt(h, "color.finish", (double)S.n);
@@ -3776,20 +3264,13 @@ int e3d_reg_color_finish(e3d_reg_t* h, int point_scale) {
                        S.obs_counts.p);
   }
   rsync(h);
-  return 0;
-  R_CATCH()
 }
-
 
 // =====================================================================================================================================
 // Optimizer driver (host): the alternation of opt::Optimizer::RunOnCurrentScale (src/opt/optimizer.cc:49-182) and
-// IntrinsicsAndPoseOptimizer::Apply (src/opt/intrinsics_and_pose_optimizer.cc:48-259) over the kernel-level operators above.
+// IntrinsicsAndPoseOptimizer::Apply (src/opt/intrinsics_and_pose_optimizer.cc:48-259) over the operators above.
 // Images are visited in ascending image id (the reference iterates an unordered_map, whose order is unspecified).
-// Non-rig images, colour residuals.
 // =====================================================================================================================================
-}  // extern "C"
-
-namespace e3d {
 
 struct RegState {
   std::map<int, Intrin> intr;
@@ -3830,51 +3311,90 @@ static double compute_cost_value(const e3d_reg* h, const double sums[3], const i
   return r;
 }
 
+// What an observation pass of one point scale starts from: every point of the scale (with the occlusion, mask and saturation tests), or
+// a device list of n point indices that are only re-projected
+struct Candidates { bool all_points; const unsigned* idx; size_t n; };
+
+// The coarse-to-fine loop over the point scales of one image (visibility_estimator.cc: from the coarsest scale down, and no finer
+// once a scale with many observations is followed by one with none).  candidates(point_scale) says what each pass starts from;
+// returns the scales visited -- the ones the early-out skipped have empty observation vectors in the reference.
+template <class CandidatesOfScale>
+static std::vector<int> observe_coarse_to_fine(e3d_reg* h, int image_id, int image_scale, int border, CandidatesOfScale candidates) {
+  constexpr size_t kManyObservationsCount = 100;
+  static const unsigned dummy = 0;          // (an empty list is still a list: its pointer is not null)
+  std::vector<int> visited;
+  bool had_many = false;
+  for (auto it = h->scales.rbegin(); it != h->scales.rend(); ++it) {
+    const Candidates c = candidates(it->first);
+    const size_t n = observe(h, image_id, it->first, image_scale, border, c.all_points ? nullptr : (c.n ? c.idx : &dummy), c.all_points ? 0 : c.n);
+    visited.push_back(it->first);
+    if (n > kManyObservationsCount) had_many = true;
+    else if (n == 0 && had_many) break;
+  }
+  return visited;
+}
+
 // VisibilityEstimator::CreateObservationsForAllImages + DetermineIfAllNeighborsAreObserved; with cache_observations the
 // ObservationsCache::GetObservations path (observations_cache.cc:52-68): the cached point indices of each image are
 // re-projected with the current state, without occlusion / mask / saturation tests (visibility_estimator.cc:140-168).
 static void update_observations(e3d_reg* h, int border) {
-  constexpr size_t kManyObservationsCount = 100;
+  const bool cached = h->cache_observations;
   for (auto& kv : h->images) {
     if (!h->owns(kv.first)) continue;
     ImageDev& im = kv.second;
     const int scale = best_available_scale(h, h->intr.at(im.intrinsics_id));
-    const bool cached = h->cache_observations;
     if (cached && !im.has_observed)
       throw Error(E3D_ERR_INVALID, fmt("no observed point indices for image %d (e3d_reg_determine_observed_indices / e3d_reg_set_observed_indices)", kv.first));
     {
       Phase ph(h, "observations.occlusion_depth_map");
-      if (!cached && e3d_reg_render_depth(h, kv.first, scale, nullptr) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+      if (!cached) render_depth(h, kv.first, scale, nullptr);
     }
     Phase ph(h, "observations.visibility");
     for (auto& o : im.obs) { o.second.active = false; o.second.n = 0; }      // keep the device buffers
-    bool had_many = false;
-    for (auto it = h->scales.rbegin(); it != h->scales.rend(); ++it) {
-      int64_t n;
-      if (cached) {
-        auto ci = im.observed.find(it->first);
-        const size_t nv = (ci == im.observed.end()) ? 0 : ci->second.second;
-        static const unsigned dummy = 0;
-        n = e3d_reg_observe(h, kv.first, it->first, scale, border, nv ? ci->second.first.p : &dummy, nv);
-      } else {
-        n = e3d_reg_observe(h, kv.first, it->first, scale, border, nullptr, 0);
-      }
-      if (n < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
-      if ((size_t)n > kManyObservationsCount) had_many = true;
-      else if (n == 0 && had_many) break;
-    }
+    observe_coarse_to_fine(h, kv.first, scale, border, [&](int point_scale) {
+      if (!cached) return Candidates{true, nullptr, 0};
+      auto ci = im.observed.find(point_scale);
+      return ci == im.observed.end() ? Candidates{false, nullptr, 0} : Candidates{false, ci->second.first.p, ci->second.second};
+    });
   }
+}
+
+// ObservationsCache::DetermineAndSaveObservedPointIndices (observations_cache.cc:104-158) without the files: the full
+// visibility test at image scale 0, whose observed point indices become the cached lists.
+static void determine_observed_indices(e3d_reg* h) {
+  const int old_scale = h->prm.current_image_scale;
+  const bool old_cache = h->cache_observations;
+  h->prm.current_image_scale = 0;
+  h->cache_observations = false;
+  try { update_observations(h, 1); } catch (...) { h->prm.current_image_scale = old_scale; h->cache_observations = old_cache; throw; }
+  h->prm.current_image_scale = old_scale;
+  h->cache_observations = old_cache;
+  for (auto& kv : h->images) {
+    if (!h->owns(kv.first)) continue;
+    ImageDev& im = kv.second;
+    for (auto& sc : h->scales) {
+      auto& slot = im.observed[sc.first];
+      slot.second = 0;
+      if (!has_obs(im, sc.first)) continue;
+      Obs& O = im.obs.at(sc.first);
+      slot.first.reserve(O.n);
+      if (O.n) E3D_HIP(hipMemcpyAsync(slot.first.p, O.idx.p, sizeof(unsigned) * O.n, hipMemcpyDeviceToDevice, h->stream));
+      slot.second = O.n;
+    }
+    im.has_observed = true;
+  }
+  rsync(h);
 }
 
 static void color_update(e3d_reg* h) {
   for (auto& sc : h->scales) {
-    if (e3d_reg_color_begin(h, sc.first) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+    color_begin(h, sc.first);
     for (auto& kv : h->images)
       if (h->owns(kv.first) && has_obs(kv.second, sc.first)) color_accumulate_enqueue(h, kv.first, sc.first);     // (one stream: no sync between images)
     // the exchange step of (B): descriptor sums and observation counts over all images = over all ranks
     allreduce_device(h, sc.second.var_desc.p, sc.second.n * (size_t)h->prm.point_neighbor_count, 0);
     allreduce_device(h, sc.second.obs_counts.p, sc.second.n, 1);
-    if (e3d_reg_color_finish(h, sc.first) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+    color_finish(h, sc.first);
   }
 }
 
@@ -3888,27 +3408,41 @@ static void reduce_sums(e3d_reg* h, double sums[3], int64_t counts[3]) {
 // depth residuals are in use: every image needs its depth maps, and none may be a dependent rig image (as in the reference)
 static bool depth_in_use(const e3d_reg* h) { return h->prm.depth_residuals_weight > 0; }
 
+// The colour costs of many (image, point scale) pairs: enqueued back to back, read with ONE copy and added in the order of the
+// enqueues, each followed by the pair's depth cost.  h->red_all is reserved once, up front, for images x scales results: the buffer
+// must not move while results are pending.
+struct CostBatch {
+  e3d_reg* h;
+  std::vector<std::pair<int, int>> jobs;
+  explicit CostBatch(e3d_reg* hh) : h(hh) { h->red_all.reserve(4 * std::max<size_t>(h->images.size() * h->scales.size(), 1)); }
+  void enqueue(int image_id, int point_scale) {
+    cost_enqueue(h, image_id, point_scale, h->red_all.p + 4 * jobs.size());
+    jobs.emplace_back(image_id, point_scale);
+  }
+  // adds [fixed colour, variable colour, depth] of this rank's jobs to sums and counts
+  void finish(double sums[3], int64_t counts[3]) {
+    std::vector<double> r(4 * jobs.size());
+    read_back(h, r.data(), h->red_all.p, sizeof(double) * r.size());
+    for (size_t j = 0; j < jobs.size(); ++j) {
+      sums[0] += r[4 * j]; sums[1] += r[4 * j + 1]; counts[0] += (int64_t)r[4 * j + 2]; counts[1] += (int64_t)r[4 * j + 3];
+      if (depth_in_use(h)) {
+        double sd; int64_t cd;
+        depth_cost(h, jobs[j].first, jobs[j].second, &sd, &cd);
+        sums[2] += sd; counts[2] += cd;
+      }
+    }
+  }
+};
+
 // CostCalculator::ComputeCost over the stored observations
 static double total_cost(e3d_reg* h) {
   double sums[3] = {0, 0, 0};
   int64_t counts[3] = {0, 0, 0};
-  // the colour costs of all (image, scale) pairs are enqueued back to back and read with one copy; summed in the loop's order
-  std::vector<std::pair<int, int>> jobs;
+  CostBatch batch(h);
   for (auto& kv : h->images)
     for (auto& sc : h->scales)
-      if (h->owns(kv.first) && has_obs(kv.second, sc.first)) jobs.emplace_back(kv.first, sc.first);
-  h->red_all.reserve(4 * std::max<size_t>(jobs.size(), 1));
-  for (size_t j = 0; j < jobs.size(); ++j) cost_enqueue(h, jobs[j].first, jobs[j].second, h->red_all.p + 4 * j);
-  std::vector<double> r(4 * jobs.size());
-  read_back(h, r.data(), h->red_all.p, sizeof(double) * r.size());
-  for (size_t j = 0; j < jobs.size(); ++j) {
-    sums[0] += r[4 * j]; sums[1] += r[4 * j + 1]; counts[0] += (int64_t)r[4 * j + 2]; counts[1] += (int64_t)r[4 * j + 3];
-    if (depth_in_use(h)) {
-      double sd; int64_t cd;
-      if (e3d_reg_depth_cost(h, jobs[j].first, jobs[j].second, &sd, &cd) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
-      sums[2] += sd; counts[2] += cd;
-    }
-  }
+      if (h->owns(kv.first) && has_obs(kv.second, sc.first)) batch.enqueue(kv.first, sc.first);
+  batch.finish(sums, counts);
   reduce_sums(h, sums, counts);
   if (counts[0] == 0 && counts[1] == 0 && counts[2] == 0) return std::numeric_limits<double>::infinity();
   return compute_cost_value(h, sums, counts);
@@ -3926,39 +3460,32 @@ struct NormalSystem {
   std::map<int, std::map<int, std::pair<DevBuf<unsigned>*, size_t>>> vis;
 };
 
-static void accumulate_system(e3d_reg* h, NormalSystem& N) {
-  hipStream_t s = h->stream;
-  // CountAndIndexVariables: [intrinsics blocks][6 per image]
-  std::map<int, int>&intr_index = N.intr_index, &image_index = N.image_index, &rig_index = N.rig_index;
-  intr_index.clear(); image_index.clear(); rig_index.clear(); N.vis.clear();
+// CountAndIndexVariables: [intrinsics blocks][rig extrinsics][6 per image]; H and b in arrow form (e3d_math.hpp): shared block =
+// intrinsics + rig extrinsics, then one 6 x 6 block per pose
+static void index_variables(e3d_reg* h, NormalSystem& N) {
+  N.intr_index.clear(); N.image_index.clear(); N.rig_index.clear(); N.vis.clear();
   int V = 0;
-  for (auto& kv : h->intr) { intr_index[kv.first] = V; V += kv.second.n_params; }
-  for (auto& kv : h->rigs) { rig_index[kv.first] = V; V += 6 * ((int)kv.second.image_T_rig.size() - 1); }   // reference camera excluded (:455-460)
-  for (auto& kv : h->images) {                                                                             // dependent rig images share the
-    if (kv.second.dependent()) continue;                                                                   // reference image's pose (:461-472)
-    image_index[kv.first] = V; V += 6;
+  for (auto& kv : h->intr) { N.intr_index[kv.first] = V; V += kv.second.n_params; }
+  for (auto& kv : h->rigs) { N.rig_index[kv.first] = V; V += 6 * ((int)kv.second.image_T_rig.size() - 1); }   // reference camera excluded (:455-460)
+  for (auto& kv : h->images) {                                                                               // dependent rig images share the
+    if (kv.second.dependent()) continue;                                                                     // reference image's pose (:461-472)
+    N.image_index[kv.first] = V; V += 6;
   }
   N.V = V;
-  // H and b in arrow form (e3d_math.hpp): shared block = intrinsics + rig extrinsics, then one 6 x 6 block per pose
-  const int n_shared = V - 6 * (int)image_index.size();
-  ArrowSystem& Hb = N.Hb;
-  Hb.reset(n_shared, (int)image_index.size());
-  double* sums = N.sums;
-  int64_t* counts = N.counts;
-  for (int i = 0; i < 3; ++i) { sums[i] = 0; counts[i] = 0; }
-  // visibility lists = observed point indices of the current observations (device copies)
-  auto& vis = N.vis;
-  // Every (image, scale) of the Apply is enqueued back to back and its numbers read with ONE copy (one host round trip per image
-  // before: the device idled between images); then the blocks are added in the loop's order -- the same sums in the same order.
-  struct Job { int image_id, scale, Vl; size_t off; };
-  std::vector<Job> jobs;
+  N.Hb.reset(V - 6 * (int)N.image_index.size(), (int)N.image_index.size());
+  for (int i = 0; i < 3; ++i) { N.sums[i] = 0; N.counts[i] = 0; }
+}
+
+// Every (image, scale) of the Apply is enqueued back to back and its numbers read with ONE copy (one host round trip per image
+// before: the device idled between images).  The visibility lists = observed point indices of the current observations (device copies).
+struct AccJob { int image_id, scale, Vl; size_t off; };
+static std::vector<double> enqueue_accumulations(e3d_reg* h, NormalSystem& N, std::vector<AccJob>& jobs) {
   size_t total = 0;
   for (auto& kv : h->images) {
     if (!h->owns(kv.first)) continue;
-    ImageDev& im = kv.second;
     for (auto& sc : h->scales) {
-      if (!has_obs(im, sc.first)) continue;
-      const int Vl = local_unknowns(h, im);
+      if (!has_obs(kv.second, sc.first)) continue;
+      const int Vl = local_unknowns(h, kv.second);
       jobs.push_back({kv.first, sc.first, Vl, total});
       total += (size_t)reg_slot(Vl);
     }
@@ -3966,66 +3493,143 @@ static void accumulate_system(e3d_reg* h, NormalSystem& N) {
   h->acc_all.reserve(std::max<size_t>(total, 1));
   {
     Phase ph(h, "apply.accumulate");
-    for (const Job& j : jobs) {
+    for (const AccJob& j : jobs) {
       ImageDev& im = h->images.at(j.image_id);
       Obs& O = im.obs.at(j.scale);
       DevBuf<unsigned>* buf = &im.vis[j.scale];
       buf->reserve(O.n);
-      if (O.n) E3D_HIP(hipMemcpyAsync(buf->p, O.idx.p, sizeof(unsigned) * O.n, hipMemcpyDeviceToDevice, s));
-      vis[j.image_id][j.scale] = {buf, O.n};
+      if (O.n) E3D_HIP(hipMemcpyAsync(buf->p, O.idx.p, sizeof(unsigned) * O.n, hipMemcpyDeviceToDevice, h->stream));
+      N.vis[j.image_id][j.scale] = {buf, O.n};
       O.flags_src = O.n ? (const void*)buf->p : nullptr; O.flags_count = O.n;     // flags / nrow belong to exactly this list
       if (accumulate_enqueue(h, j.image_id, j.scale, h->acc_all.p + j.off, false) != j.Vl) throw Error(E3D_ERR_INVALID, "accumulate: local system size");
     }
   }
   std::vector<double> all(total);
-  {
-    Phase ph(h, "apply.accumulate");
-    read_back(h, all.data(), h->acc_all.p, sizeof(double) * total);
+  Phase ph(h, "apply.accumulate");
+  read_back(h, all.data(), h->acc_all.p, sizeof(double) * total);
+  return all;
+}
+
+// AccumulateOnHAndB's block updates: the upper triangle of a local Vl x Vl block and its b into the system, local unknown l at index_of(l)
+template <class IndexOf>
+static void scatter_block(ArrowSystem& Hb, int Vl, const double* H, const double* b, IndexOf index_of) {
+  for (int r = 0; r < Vl; ++r) {
+    for (int c = r; c < Vl; ++c)
+      if (!Hb.add(index_of(r), index_of(c), H[(size_t)r * Vl + c])) throw Error(E3D_ERR_INVALID, "normal equations: entry outside the arrow pattern");
+    Hb.b[index_of(r)] += b[r];
   }
-  for (const Job& j : jobs) {
+}
+
+// one exchange per Apply: [non-zero blocks of H, b, sums, counts] -- block-sparse: s^2 + (6 s + 36 + 6) per pose instead of V^2
+// (512 images: 0.5 MB instead of 76 MB)
+static void exchange(e3d_reg* h, NormalSystem& N) {
+  if (h->world <= 1) return;
+  const size_t np = N.Hb.packed_size();
+  std::vector<double> buf(np + 6);
+  N.Hb.pack(buf.data());
+  double* tail = buf.data() + np;
+  for (int i = 0; i < 3; ++i) { tail[i] = N.sums[i]; tail[3 + i] = (double)N.counts[i]; }
+  allreduce_host(h, buf.data(), buf.size());
+  N.Hb.unpack(buf.data());
+  for (int i = 0; i < 3; ++i) { N.sums[i] = tail[i]; N.counts[i] = (int64_t)tail[3 + i]; }
+}
+
+static void accumulate_system(e3d_reg* h, NormalSystem& N) {
+  index_variables(h, N);
+  std::vector<AccJob> jobs;
+  const std::vector<double> all = enqueue_accumulations(h, N, jobs);
+  // the blocks are added in the loop's order -- the same sums in the same order as image by image
+  for (const AccJob& j : jobs) {
     ImageDev& im = h->images.at(j.image_id);
-    const int I = h->intr.at(im.intrinsics_id).n_params;
+    const int I = h->intr.at(im.intrinsics_id).n_params, Vl = j.Vl;
     const bool dep = im.dependent();
-    const int ii = intr_index.at(im.intrinsics_id);
-    const int pi = image_index.at(dep ? im.ref_image_id : j.image_id);
-    const int ri = dep ? rig_index.at(im.rig_id) + 6 * (im.camera_index - 1) : -1;
-    const int Vl = j.Vl;
+    const int ii = N.intr_index.at(im.intrinsics_id);
+    const int pi = N.image_index.at(dep ? im.ref_image_id : j.image_id);
+    const int ri = dep ? N.rig_index.at(im.rig_id) + 6 * (im.camera_index - 1) : -1;
     std::vector<double> Hl((size_t)Vl * Vl), bl(Vl);
     double s2[2]; int64_t c2[2];
     accumulate_unpack(Vl, all.data() + j.off, Hl.data(), bl.data(), s2, c2);
-    sums[0] += s2[0]; sums[1] += s2[1]; counts[0] += c2[0]; counts[1] += c2[1];
-    // scatter the local [intrinsics(I), (rig extrinsics(6),) pose(6)] block (AccumulateOnHAndB's block updates)
-    auto gidx = [&](int l) { return l < I ? ii + l : ((dep && l < I + 6) ? ri + (l - I) : pi + (l - (Vl - 6))); };
-    for (int r = 0; r < Vl; ++r) {
-      for (int c = r; c < Vl; ++c)
-        if (!Hb.add(gidx(r), gidx(c), Hl[(size_t)r * Vl + c])) throw Error(E3D_ERR_INVALID, "normal equations: entry outside the arrow pattern");
-      Hb.b[gidx(r)] += bl[r];
-    }
+    N.sums[0] += s2[0]; N.sums[1] += s2[1]; N.counts[0] += c2[0]; N.counts[1] += c2[1];
+    // the local [intrinsics(I), (rig extrinsics(6),) pose(6)] block
+    scatter_block(N.Hb, Vl, Hl.data(), bl.data(), [&](int l) { return l < I ? ii + l : ((dep && l < I + 6) ? ri + (l - I) : pi + (l - (Vl - 6))); });
     if (depth_in_use(h)) {
       // depth residuals of every observation (intrinsics_and_pose_optimizer.cc:747-757); [intrinsics(I), pose(6)] block
       std::vector<double> Hd((size_t)(I + 6) * (I + 6)), bd(I + 6);
       double sd; int64_t cd;
-      if (e3d_reg_depth_accumulate(h, j.image_id, j.scale, Hd.data(), bd.data(), &sd, &cd) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
-      sums[2] += sd; counts[2] += cd;
-      auto didx = [&](int l) { return l < I ? ii + l : pi + (l - I); };
-      for (int r = 0; r < I + 6; ++r) {
-        for (int c = r; c < I + 6; ++c)
-          if (!Hb.add(didx(r), didx(c), Hd[(size_t)r * (I + 6) + c])) throw Error(E3D_ERR_INVALID, "normal equations: entry outside the arrow pattern");
-        Hb.b[didx(r)] += bd[r];
-      }
+      depth_accumulate(h, j.image_id, j.scale, Hd.data(), bd.data(), &sd, &cd);
+      N.sums[2] += sd; N.counts[2] += cd;
+      scatter_block(N.Hb, I + 6, Hd.data(), bd.data(), [&](int l) { return l < I ? ii + l : pi + (l - I); });
     }
   }
-  E3D_HIP(hipStreamSynchronize(s));
-  if (h->world > 1) {                       // one exchange per Apply: [non-zero blocks of H, b, sums, counts] -- block-sparse:
-    const size_t np = Hb.packed_size();     // s^2 + (6 s + 36 + 6) per pose instead of V^2 (512 images: 0.5 MB instead of 76 MB)
-    std::vector<double> buf(np + 6);
-    Hb.pack(buf.data());
-    double* tail = buf.data() + np;
-    for (int i = 0; i < 3; ++i) { tail[i] = sums[i]; tail[3 + i] = (double)counts[i]; }
-    allreduce_host(h, buf.data(), buf.size());
-    Hb.unpack(buf.data());
-    for (int i = 0; i < 3; ++i) { sums[i] = tail[i]; counts[i] = (int64_t)tail[3 + i]; }
+  rsync(h);
+  exchange(h, N);
+}
+
+// The damped solve of the normal equations.  Small systems: the reference's dense pivoted LDLT, operation for operation.  Large ones
+// (V > 384, i.e. more than ~60 images): Schur complement on the shared block -- same solution to f64 rounding, O(images) instead of
+// O(V^3) host work.  E3D_REG_SOLVER=dense|arrow forces one of them (tests).
+struct DampedSolver {
+  NormalSystem& N;
+  bool dense;
+  std::vector<double> H, Hlm, W;
+  std::vector<int> perm;
+  explicit DampedSolver(NormalSystem& n) : N(n) {
+    const RegSwitches::Solver forced = reg_switches().solver;
+    dense = forced == RegSwitches::dense || (forced == RegSwitches::by_size && N.V <= 384);
+    if (dense) N.Hb.to_dense(H);
   }
+  void solve(float lambda, double* x) {
+    if (!dense) { N.Hb.solve((double)(1 + lambda), x); return; }
+    Hlm = H;
+    for (int i = 0; i < N.V; ++i) Hlm[(size_t)i * N.V + i] *= (1 + lambda);       // multiplicative damping (:206)
+    ldlt_solve_upper(Hlm.data(), N.V, N.Hb.b.data(), x, W, perm);
+  }
+};
+
+// CreateDeltaState(-x): the state `old` moved by the solution x of the system N (camera pyramids rebuilt)
+static RegState make_trial_state(e3d_reg* h, const RegState& old, const NormalSystem& N, const std::vector<double>& x) {
+  RegState trial = old;
+  for (auto& kv : trial.intr) {
+    Intrin& in = kv.second;
+    const int base = N.intr_index.at(kv.first);
+    for (int i = 0; i < in.n_params; ++i) in.params[i] += -1 * x[base + i];      // float += double (intrinsics.cc:71-73)
+    build_model_pyramid(h, in, (int)in.levels.size());
+  }
+  for (auto& kv : trial.rigs)                                                                    // Rig::Update (rig.cc:9-23)
+    for (size_t c = 1; c < kv.second.image_T_rig.size(); ++c)
+      kv.second.image_T_rig[c] = se3_apply_update(&x[N.rig_index.at(kv.first) + 6 * ((int)c - 1)], old.rigs.at(kv.first).image_T_rig[c]);
+  for (auto& kv : trial.poses)
+    if (N.image_index.count(kv.first)) kv.second = se3_apply_update(&x[N.image_index.at(kv.first)], old.poses.at(kv.first));   // exp(-x) * T
+  return trial;
+}
+
+// ComputeResidualForState with the visibility lists fixed: the lists of N re-projected with the handle's (trial) state, image by image,
+// each image's costs enqueued behind its re-projection
+static double trial_cost(e3d_reg* h, NormalSystem& N) {
+  double ts[3] = {0, 0, 0}; int64_t tc[3] = {0, 0, 0};
+  CostBatch batch(h);
+  for (auto& kv : h->images) {
+    if (!h->owns(kv.first)) continue;
+    const int scale = best_available_scale(h, h->intr.at(kv.second.intrinsics_id));
+    std::vector<int> done;
+    {
+      Phase ph_obs(h, "apply.trial_reprojection");
+      auto& lists = N.vis[kv.first];
+      done = observe_coarse_to_fine(h, kv.first, scale, 1, [&](int point_scale) {
+        auto vi = lists.find(point_scale);
+        return vi == lists.end() ? Candidates{false, nullptr, 0} : Candidates{false, vi->second.first->p, vi->second.second};
+      });
+    }
+    Phase ph_cost(h, "apply.trial_cost");
+    for (auto& sc : h->scales)
+      if (std::find(done.begin(), done.end(), sc.first) != done.end()) batch.enqueue(kv.first, sc.first);
+  }
+  {
+    Phase ph_cost(h, "apply.trial_cost");
+    batch.finish(ts, tc);
+  }
+  reduce_sums(h, ts, tc);
+  return compute_cost_value(h, ts, tc);
 }
 
 // IntrinsicsAndPoseOptimizer::Apply.  `ready`: the normal equations of exactly this state and these observations, accumulated
@@ -4034,113 +3638,34 @@ static void apply_update(e3d_reg* h, bool print, bool* applied_update, float* la
   NormalSystem own;
   if (!ready) accumulate_system(h, own);
   NormalSystem& N = ready ? *ready : own;
-  std::map<int, int>&intr_index = N.intr_index, &image_index = N.image_index, &rig_index = N.rig_index;
-  const int V = N.V;
-  ArrowSystem& Hb = N.Hb;
-  auto& vis = N.vis;
-  const double* sums = N.sums;
-  const int64_t* counts = N.counts;
-  const double initial_residual = compute_cost_value(h, sums, counts);
+  const double initial_residual = compute_cost_value(h, N.sums, N.counts);
   if (print)
-    printf("    Initial residual: %g (#fixed residuals: %lld, #variable residuals: %lld)\n", initial_residual, (long long)counts[0], (long long)counts[1]);
+    printf("    Initial residual: %g (#fixed residuals: %lld, #variable residuals: %lld)\n", initial_residual, (long long)N.counts[0], (long long)N.counts[1]);
 
   const RegState old_state = get_state(h);
   *applied_update = false;
-  // Small systems: the reference's dense pivoted LDLT, operation for operation.  Large ones (V > 384, i.e. more than ~60 images):
-  // Schur complement on the shared block -- same solution to f64 rounding, O(images) instead of O(V^3) host work.
-  // E3D_REG_SOLVER=dense|arrow forces one of them (tests).
-  static const int forced_solver = [] { const char* e = getenv("E3D_REG_SOLVER"); return !e ? 0 : (!strcmp(e, "dense") ? 1 : (!strcmp(e, "arrow") ? 2 : 0)); }();
-  const bool dense_solve = forced_solver == 1 || (forced_solver == 0 && V <= 384);
-  std::vector<double> H, Hlm, x(V), W;
-  if (dense_solve) Hb.to_dense(H);
-  const std::vector<double>& b = Hb.b;
-  std::vector<int> perm;
+  DampedSolver solver(N);
+  std::vector<double> x(N.V);
   constexpr int kNumLMTries = 10;
   for (int lm = 0; lm < kNumLMTries; ++lm) {
     {
       Phase ph(h, "apply.host_solve");
-      if (dense_solve) {
-        Hlm = H;
-        for (int i = 0; i < V; ++i) Hlm[(size_t)i * V + i] *= (1 + (*lambda));       // multiplicative damping (:206)
-        ldlt_solve_upper(Hlm.data(), V, b.data(), x.data(), W, perm);
-      } else {
-        Hb.solve((double)(1 + (*lambda)), x.data());
-      }
-    }
-    // CreateDeltaState(-x)
-    std::unique_ptr<Phase> ph_state(new Phase(h, "apply.trial_state_and_camera_pyramids"));
-    RegState trial = old_state;
-    for (auto& kv : trial.intr) {
-      Intrin& in = kv.second;
-      const int base = intr_index.at(kv.first);
-      for (int i = 0; i < in.n_params; ++i) in.params[i] += -1 * x[base + i];      // float += double (intrinsics.cc:71-73)
-      build_model_pyramid(h, in, (int)in.levels.size());
-    }
-    for (auto& kv : trial.rigs)                                                                    // Rig::Update (rig.cc:9-23)
-      for (size_t c = 1; c < kv.second.image_T_rig.size(); ++c)
-        kv.second.image_T_rig[c] = se3_apply_update(&x[rig_index.at(kv.first) + 6 * ((int)c - 1)], old_state.rigs.at(kv.first).image_T_rig[c]);
-    for (auto& kv : trial.poses)
-      if (image_index.count(kv.first)) kv.second = se3_apply_update(&x[image_index.at(kv.first)], old_state.poses.at(kv.first));   // exp(-x) * T
-    // ComputeResidualForState with the visibility lists fixed
-    set_state(h, trial);
-    compose_rig_poses(h);
-    ph_state.reset();
-    double ts[3] = {0, 0, 0}; int64_t tc[3] = {0, 0, 0};
-    constexpr size_t kManyObservationsCount = 100;
-    std::vector<std::pair<int, int>> trial_jobs;
-    const size_t trial_cap = h->images.size() * h->scales.size();        // (red_all must not move while results are pending)
-    h->red_all.reserve(4 * std::max<size_t>(trial_cap, 1));
-    for (auto& kv : h->images) {
-      if (!h->owns(kv.first)) continue;
-      const int scale = best_available_scale(h, h->intr.at(kv.second.intrinsics_id));
-      bool had_many = false;
-      std::vector<int> done;
-      std::unique_ptr<Phase> ph_obs(new Phase(h, "apply.trial_reprojection"));
-      for (auto it = h->scales.rbegin(); it != h->scales.rend(); ++it) {
-        auto vi = vis[kv.first].find(it->first);
-        const size_t nv = (vi == vis[kv.first].end()) ? 0 : vi->second.second;
-        const unsigned* ptr = nv ? vi->second.first->p : nullptr;
-        static const unsigned dummy = 0;
-        const int64_t n = e3d_reg_observe(h, kv.first, it->first, scale, 1, ptr ? ptr : &dummy, nv);
-        if (n < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
-        done.push_back(it->first);
-        if ((size_t)n > kManyObservationsCount) had_many = true;
-        else if (n == 0 && had_many) break;
-      }
-      ph_obs.reset();
-      Phase ph_cost(h, "apply.trial_cost");
-      for (auto& sc : h->scales) {
-        // scales skipped by the early-out have empty observation vectors in the reference
-        if (std::find(done.begin(), done.end(), sc.first) == done.end()) continue;
-        trial_jobs.emplace_back(kv.first, sc.first);
-        h->red_all.reserve(4 * std::max<size_t>(trial_cap, trial_jobs.size()));
-        cost_enqueue(h, kv.first, sc.first, h->red_all.p + 4 * (trial_jobs.size() - 1));
-      }
+      solver.solve(*lambda, x.data());
     }
     {
-      // every trial cost was enqueued behind its image's re-projection: one copy, summed in the loop's order
-      Phase ph_cost(h, "apply.trial_cost");
-      std::vector<double> r(4 * trial_jobs.size());
-      read_back(h, r.data(), h->red_all.p, sizeof(double) * r.size());
-      for (size_t j = 0; j < trial_jobs.size(); ++j) {
-        ts[0] += r[4 * j]; ts[1] += r[4 * j + 1]; tc[0] += (int64_t)r[4 * j + 2]; tc[1] += (int64_t)r[4 * j + 3];
-        if (depth_in_use(h)) {
-          double sd; int64_t cd;
-          if (e3d_reg_depth_cost(h, trial_jobs[j].first, trial_jobs[j].second, &sd, &cd) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
-          ts[2] += sd; tc[2] += cd;
-        }
-      }
+      Phase ph(h, "apply.trial_state_and_camera_pyramids");
+      set_state(h, make_trial_state(h, old_state, N, x));
+      compose_rig_poses(h);
     }
-    reduce_sums(h, ts, tc);
-    const double new_residual = compute_cost_value(h, ts, tc);
+    const double new_residual = trial_cost(h, N);
     if (new_residual < initial_residual || lm == kNumLMTries - 1) {      // kAlwaysApplyLastUpdate
       if (print) printf("    LM update accepted, new residual: %g\n", new_residual);
       double mx = -std::numeric_limits<double>::infinity();
-      for (int i = 0; i < V; ++i) mx = std::max(mx, x[i]);               // x.maxCoeff(): signed max [QUIRK]
+      for (int i = 0; i < N.V; ++i) mx = std::max(mx, x[i]);             // x.maxCoeff(): signed max [QUIRK]
       *max_change = (float)mx;
       *lambda = 0.5f * (*lambda);
       *applied_update = true;
-      break;                                                             // state stays at `trial`
+      break;                                                             // the state stays at the trial
     } else {
       *lambda = 2.f * (*lambda);
       if (print) printf("    [%d of %d] LM update rejected (bad residual: %g), lambda increased to %g\n", lm + 1, kNumLMTries, new_residual, (double)*lambda);
@@ -4151,21 +3676,563 @@ static void apply_update(e3d_reg* h, bool print, bool* applied_update, float* la
 
 }  // namespace e3d
 
+// =====================================================================================================================================
+// The C-ABI (include/e3d_hip.h): null checks, the handle's device, the call, the error convention
+// =====================================================================================================================================
 extern "C" {
+
+e3d_reg_t* e3d_reg_create(const e3d_reg_params* params) {
+  try {
+    check_params(params);
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
+    std::unique_ptr<e3d_reg> h(new e3d_reg());
+    E3D_HIP(hipGetDevice(&h->device));
+    E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->prm = *params;
+    return h.release();
+  } catch (const std::exception& e) {
+    e3d::set_last_error(e.what());
+    return nullptr;
+  }
+}
+void e3d_reg_destroy(e3d_reg_t* reg) { delete reg; }
+
+int e3d_reg_set_params(e3d_reg_t* h, const e3d_reg_params* params) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  check_params(params);
+  if (params->point_neighbor_count != h->prm.point_neighbor_count && !h->scales.empty())
+    throw Error(E3D_ERR_INVALID, "point_neighbor_count cannot change after point scales were set");
+  h->prm = *params;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_set_point_scale(e3d_reg_t* h, int point_scale, const float* xyz, size_t n, float point_radius,
+                            const uint32_t* neighbor_indices, const float* fixed_descriptors) {
+  E3D_TRY_ON(h)
+  if (!h || (!xyz && n) || (!neighbor_indices && n)) throw Error(E3D_ERR_INVALID, "e3d_reg_set_point_scale: null argument");
+  hipStream_t s = h->stream;
+  const int K = h->prm.point_neighbor_count;
+  PointScale& S = h->scales[point_scale];
+  S.n = n; S.radius = point_radius;
+  S.pts.reserve(n); S.nbr.reserve(n * K); S.fixed_desc.reserve(n * K); S.var_desc.reserve(n * K);
+  S.obs_counts.reserve(n); S.row_of_point.reserve(n);
+  DevBuf<float> tmp; tmp.reserve(3 * n);
+  copy_in(tmp.p, xyz, sizeof(float) * 3 * n, s);
+  hipLaunchKernelGGL(k_xyz_to_float4, dim3(nblk(n)), dim3(kBlock), 0, s, tmp.p, n, S.pts.p);
+  copy_in(S.nbr.p, neighbor_indices, sizeof(unsigned) * n * K, s);
+  S.has_fixed = fixed_descriptors != nullptr;
+  if (fixed_descriptors) copy_in(S.fixed_desc.p, fixed_descriptors, sizeof(float) * n * K, s);
+  else E3D_HIP(hipMemsetAsync(S.fixed_desc.p, 0, sizeof(float) * n * K, s));
+  E3D_HIP(hipMemsetAsync(S.var_desc.p, 0, sizeof(float) * n * K, s));
+  hipLaunchKernelGGL(k_fill_i32, dim3(nblk(n)), dim3(kBlock), 0, s, S.obs_counts.p, n, fixed_descriptors ? 99999 : 0);   // problem.cc:568-570
+  rsync(h);
+  for (auto& kv : h->images) kv.second.obs.erase(point_scale);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_set_variable_descriptors(e3d_reg_t* h, int point_scale, const float* descriptors, const int32_t* counts) {
+  E3D_TRY_ON(h)
+  if (!h || !descriptors || !counts) throw Error(E3D_ERR_INVALID, "null argument");
+  PointScale& S = get_scale(h, point_scale);
+  copy_in(S.var_desc.p, descriptors, sizeof(float) * S.n * h->prm.point_neighbor_count, h->stream);
+  copy_in(S.obs_counts.p, counts, sizeof(int) * S.n, h->stream);
+  rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+int e3d_reg_get_variable_descriptors(e3d_reg_t* h, int point_scale, float* descriptors, int32_t* counts) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  PointScale& S = get_scale(h, point_scale);
+  if (descriptors) copy_out(descriptors, S.var_desc.p, sizeof(float) * S.n * h->prm.point_neighbor_count, h->stream);
+  if (counts) copy_out(counts, S.obs_counts.p, sizeof(int) * S.n, h->stream);
+  rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_set_intrinsics(e3d_reg_t* h, int intrinsics_id, int camera_type, int width, int height, const float* parameters,
+                           int n_parameters, int min_image_scale, int n_levels) {
+  E3D_TRY_ON(h)
+  if (!h || !parameters) throw Error(E3D_ERR_INVALID, "null argument");
+  if (camera_type < 0 || camera_type >= kNumCameraModels)
+    throw Error(E3D_ERR_INVALID, "unknown camera model (E3D_CAMERA_* of e3d_hip.h)");
+  if (n_parameters != cam_param_count(camera_type)) throw Error(E3D_ERR_INVALID, fmt("camera model %d takes %d parameters, got %d", camera_type, cam_param_count(camera_type), n_parameters));
+  if (n_levels < 1 || n_levels > kRegMaxLevels || width < 2 || height < 2 || min_image_scale < 0) throw Error(E3D_ERR_INVALID, "bad pyramid description");
+  Intrin in;
+  in.type = camera_type; in.min_image_scale = min_image_scale; in.n_params = n_parameters;
+  in.width = width; in.height = height;
+  for (int i = 0; i < n_parameters; ++i) in.params[i] = parameters[i];
+  build_model_pyramid(h, in, n_levels);
+  h->intr[intrinsics_id] = in;                          // (a camera mask belongs to the previous description of this id and goes with it)
+  return 0;
+  E3D_CATCH()
+}
+
+/* Intrinsics::camera_mask (src/opt/intrinsics.h:104, loaded by Image::LoadImageData, image.cc:62-72): one u8 mask per pyramid level
+ * of the camera, shared by all its images; an observation is dropped where the image mask OR the camera mask is non-zero
+ * (visibility_estimator.cc:335-345,482-503).  level_masks[l] = width_l x height_l bytes (host or device) or NULL; level_masks == NULL
+ * removes the mask.  Call after e3d_reg_set_intrinsics. */
+int e3d_reg_set_camera_mask(e3d_reg_t* h, int intrinsics_id, const uint8_t* const* level_masks) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  auto it = h->intr.find(intrinsics_id);
+  if (it == h->intr.end()) throw Error(E3D_ERR_INDEX, "no such intrinsics");
+  Intrin& in = it->second;
+  if (!level_masks) { in.cam_mask.reset(); }
+  else {
+    auto masks = std::make_shared<std::vector<DevBuf<unsigned char>>>(in.levels.size());
+    for (size_t l = 0; l < in.levels.size(); ++l) {
+      if (!level_masks[l]) continue;
+      const size_t bytes = (size_t)in.levels[l].width * (size_t)in.levels[l].height;
+      (*masks)[l].reserve(bytes);
+      copy_in((*masks)[l].p, level_masks[l], bytes, h->stream);
+    }
+    rsync(h);
+    in.cam_mask = masks;
+  }
+  for (auto& kv : h->images)
+    if (kv.second.intrinsics_id == intrinsics_id)
+      for (auto& o : kv.second.obs) o.second.rows_valid = false;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_get_intrinsics_level(e3d_reg_t* h, int intrinsics_id, int level, int* width, int* height, float* parameters,
+                                 float* cutoff2) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  auto it = h->intr.find(intrinsics_id);
+  if (it == h->intr.end() || level < 0 || level >= (int)it->second.levels.size()) throw Error(E3D_ERR_INDEX, "no such intrinsics level");
+  const CamLevel& c = it->second.levels[level];
+  if (width) *width = c.width;
+  if (height) *height = c.height;
+  if (parameters) {
+    if (cam_unique_focal(c.model)) {
+      parameters[0] = c.fx; parameters[1] = c.cx; parameters[2] = c.cy;
+      for (int i = 3; i < it->second.n_params; ++i) parameters[i] = c.q[i - 3];
+    } else {
+      parameters[0] = c.fx; parameters[1] = c.fy; parameters[2] = c.cx; parameters[3] = c.cy;
+      for (int i = 4; i < it->second.n_params; ++i) parameters[i] = c.q[i - 4];
+    }
+  }
+  if (cutoff2) *cutoff2 = cam_is_fisheye(c.model) ? c.inner_cutoff2 : c.cutoff2;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_set_image(e3d_reg_t* h, int image_id, int intrinsics_id, const uint8_t* const* level_pixels,
+                      const uint8_t* const* level_masks) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null argument");
+  auto it = h->intr.find(intrinsics_id);
+  if (it == h->intr.end()) throw Error(E3D_ERR_INDEX, "intrinsics not set");
+  const Intrin& in = it->second;
+  if (!h->owns(image_id)) {                     // another rank's image: only its id, intrinsics and pose are kept here
+    ImageDev& im = h->images[image_id];
+    im.intrinsics_id = intrinsics_id;
+    im.pix.clear(); im.mask.clear(); im.has_mask.clear(); im.obs.clear();
+    im.depth_scale = -1;
+    return 0;
+  }
+  if (!level_pixels) throw Error(E3D_ERR_INVALID, "null argument");
+  ImageDev& im = h->images[image_id];
+  im.intrinsics_id = intrinsics_id;
+  const int L = (int)in.levels.size();
+  im.pix.resize(L); im.mask.resize(L); im.has_mask.assign(L, false);
+  for (int l = 0; l < L; ++l) {
+    const size_t bytes = (size_t)in.levels[l].width * in.levels[l].height;
+    if (!level_pixels[l]) throw Error(E3D_ERR_INVALID, "missing pyramid level");
+    im.pix[l].reserve(bytes);
+    copy_in(im.pix[l].p, level_pixels[l], bytes, h->stream);
+    if (level_masks && level_masks[l]) {
+      im.mask[l].reserve(bytes);
+      copy_in(im.mask[l].p, level_masks[l], bytes, h->stream);
+      im.has_mask[l] = true;
+    }
+  }
+  rsync(h);
+  im.obs.clear();
+  im.depth_scale = -1;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_set_image_pose(e3d_reg_t* h, int image_id, const float q[4], const float t[3]) {
+  E3D_TRY_ON(h)
+  if (!h || !q || !t) throw Error(E3D_ERR_INVALID, "null argument");
+  ImageDev& im = get_image(h, image_id);
+  SE3f T;
+  T.q.w = q[0]; T.q.x = q[1]; T.q.y = q[2]; T.q.z = q[3];
+  for (int i = 0; i < 3; ++i) T.t[i] = t[i];
+  set_pose(im, T);
+  for (auto& kv : im.obs) kv.second.rows_valid = false;
+  if (!h->frames.empty()) compose_rig_poses(h);
+  return 0;
+  E3D_CATCH()
+}
+
+/* opt::Rig: image_T_rig of every camera of a rig (camera 0 = reference, normally identity) */
+int e3d_reg_set_rig(e3d_reg_t* h, int rig_id, int n_cameras, const float* q, const float* t) {
+  E3D_TRY_ON(h)
+  if (!h || !q || !t || n_cameras < 1) throw Error(E3D_ERR_INVALID, "bad rig");
+  RigState r;
+  r.image_T_rig.resize(n_cameras);
+  for (int c = 0; c < n_cameras; ++c) {
+    SE3f T;
+    T.q.w = q[4 * c]; T.q.x = q[4 * c + 1]; T.q.y = q[4 * c + 2]; T.q.z = q[4 * c + 3];
+    for (int i = 0; i < 3; ++i) T.t[i] = t[3 * c + i];
+    r.image_T_rig[c] = T;
+  }
+  h->rigs[rig_id] = r;
+  if (!h->frames.empty()) compose_rig_poses(h);
+  return 0;
+  E3D_CATCH()
+}
+int e3d_reg_get_rig(e3d_reg_t* h, int rig_id, int camera_index, float q[4], float t[3]) {
+  E3D_TRY_ON(h)
+  if (!h || !q || !t) throw Error(E3D_ERR_INVALID, "null argument");
+  auto it = h->rigs.find(rig_id);
+  if (it == h->rigs.end() || camera_index < 0 || camera_index >= (int)it->second.image_T_rig.size()) throw Error(E3D_ERR_INDEX, "no such rig camera");
+  const SE3f& T = it->second.image_T_rig[camera_index];
+  q[0] = T.q.w; q[1] = T.q.x; q[2] = T.q.y; q[3] = T.q.z;
+  for (int i = 0; i < 3; ++i) t[i] = T.t[i];
+  return 0;
+  E3D_CATCH()
+}
+/* opt::RigImages: one frame of a rig = one image per camera, image_ids[0] is the reference image.  The poses of the other
+ * images become image_T_rig[camera] * image_T_global(reference). */
+int e3d_reg_add_rig_images(e3d_reg_t* h, int rig_id, const int* image_ids, int n_cameras) {
+  E3D_TRY_ON(h)
+  if (!h || !image_ids) throw Error(E3D_ERR_INVALID, "null argument");
+  auto it = h->rigs.find(rig_id);
+  if (it == h->rigs.end() || (int)it->second.image_T_rig.size() != n_cameras) throw Error(E3D_ERR_INVALID, "rig not set or camera count mismatch");
+  RigFrame f; f.rig_id = rig_id;
+  for (int c = 0; c < n_cameras; ++c) {
+    ImageDev& im = get_image(h, image_ids[c]);
+    if (im.rig_id >= 0) throw Error(E3D_ERR_INVALID, fmt("image %d already belongs to a rig frame", image_ids[c]));
+    f.image_ids.push_back(image_ids[c]);
+  }
+  for (int c = 0; c < n_cameras; ++c) {
+    ImageDev& im = h->images.at(image_ids[c]);
+    im.rig_id = rig_id; im.camera_index = c; im.ref_image_id = image_ids[0];
+  }
+  h->frames.push_back(f);
+  compose_rig_poses(h);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_get_image_pose(e3d_reg_t* h, int image_id, float q[4], float t[3]) {
+  E3D_TRY_ON(h)
+  if (!h || !q || !t) throw Error(E3D_ERR_INVALID, "null argument");
+  const ImageDev& im = get_image(h, image_id);
+  q[0] = im.pose_q.q.w; q[1] = im.pose_q.q.x; q[2] = im.pose_q.q.y; q[3] = im.pose_q.q.z;
+  for (int i = 0; i < 3; ++i) t[i] = im.pose_q.t[i];
+  return 0;
+  E3D_CATCH()
+}
+
+/* OcclusionGeometry::AddMesh / AddSplats (occlusion_geometry.cc:64-182): one more triangle mesh (vertices already in the
+ * global frame).  compute_edges != 0 also extracts the edges used for masking occlusion boundaries (meshes: yes, splat
+ * geometry: no). */
+int e3d_reg_add_occlusion_mesh(e3d_reg_t* h, const float* vertices, size_t n_vertices, const uint32_t* triangles, size_t n_triangles,
+                               int compute_edges) {
+  E3D_TRY_ON(h)
+  if (!h || !vertices || !triangles || !n_vertices || !n_triangles) throw Error(E3D_ERR_INVALID, "empty mesh");
+  if (n_triangles >= ((size_t)1 << 31) || n_vertices >= ((size_t)1 << 32)) throw Error(E3D_ERR_INVALID, "mesh too large");
+  hipStream_t s = h->stream;
+  std::unique_ptr<MeshDev> m(new MeshDev());
+  m->n_vertices = n_vertices; m->n_triangles = n_triangles;
+  DevBuf<float> tmp; tmp.reserve(3 * n_vertices);
+  copy_in(tmp.p, vertices, sizeof(float) * 3 * n_vertices, s);
+  m->vertices.reserve(n_vertices);
+  hipLaunchKernelGGL(k_xyz_to_float4, dim3(nblk(n_vertices)), dim3(kBlock), 0, s, tmp.p, n_vertices, m->vertices.p);
+  m->triangles.reserve(3 * n_triangles);
+  copy_in(m->triangles.p, triangles, sizeof(unsigned) * 3 * n_triangles, s);
+  rsync(h);
+  for (size_t i = 0; i < 3 * n_triangles; ++i) if (triangles[i] >= n_vertices) throw Error(E3D_ERR_INDEX, "triangle refers to a missing vertex");
+  if (compute_edges) {
+    const size_t ne = 3 * n_triangles;
+    DevBuf<unsigned long long> ka, kb;
+    DevBuf<unsigned> va, vb, cnt;
+    ka.reserve(ne); kb.reserve(ne); va.reserve(ne); vb.reserve(ne); cnt.reserve(1);
+    m->normals.reserve(n_triangles);
+    hipLaunchKernelGGL(k_face_normals, dim3(nblk(n_triangles)), dim3(kBlock), 0, s, m->vertices.p, m->triangles.p, n_triangles, m->normals.p,
+                       ka.p, va.p);
+    sort_pairs_u64_u32(ka.p, kb.p, va.p, vb.p, ne, 64, h->sort_temp, s);
+    m->edges.reserve(ne);
+    E3D_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(k_filter_edges, dim3(nblk(ne)), dim3(kBlock), 0, s, kb.p, vb.p, ne, m->vertices.p, m->normals.p, m->edges.p, cnt.p);
+    unsigned n_edges = 0;
+    copy_out(&n_edges, cnt.p, sizeof n_edges, s);
+    rsync(h);
+    m->n_edges = n_edges;
+  }
+  h->meshes.push_back(std::move(m));
+  for (auto& kv : h->images) kv.second.depth_scale = -1;
+  return (int)h->meshes.size();
+  E3D_CATCH()
+}
+int e3d_reg_clear_occlusion_meshes(e3d_reg_t* h) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  h->meshes.clear();
+  for (auto& kv : h->images) kv.second.depth_scale = -1;
+  return 0;
+  E3D_CATCH()
+}
+/* min_occlusion_depth / max_occlusion_depth (near / far plane of the mesh renderer) and mask_occlusion_boundaries of
+ * OcclusionGeometry::RenderDepthMap (occlusion_geometry.h:80-86); defaults 0.05, 100, true */
+int e3d_reg_set_occlusion_options(e3d_reg_t* h, float min_depth, float max_depth, int mask_occlusion_boundaries) {
+  E3D_TRY_ON(h)
+  if (!h || !(min_depth > 0) || !(max_depth > min_depth)) throw Error(E3D_ERR_INVALID, "bad occlusion depth range");
+  h->min_occlusion_depth = min_depth; h->max_occlusion_depth = max_depth; h->mask_occlusion_boundaries = mask_occlusion_boundaries != 0;
+  return 0;
+  E3D_CATCH()
+}
+int64_t e3d_reg_occlusion_edge_count(e3d_reg_t* h, int mesh_index) {
+  E3D_TRY_ON(h)
+  if (!h || mesh_index < 0 || mesh_index >= (int)h->meshes.size()) throw Error(E3D_ERR_INDEX, "no such mesh");
+  return (int64_t)h->meshes[mesh_index]->n_edges;
+  E3D_CATCH()
+}
+
+int e3d_reg_set_splat_points(e3d_reg_t* h, const float* xyz, size_t n) {
+  E3D_TRY_ON(h)
+  if (!h || (!xyz && n)) throw Error(E3D_ERR_INVALID, "null argument");
+  DevBuf<float> tmp; tmp.reserve(3 * n);
+  copy_in(tmp.p, xyz, sizeof(float) * 3 * n, h->stream);
+  h->splat.reserve(n);
+  // The splat points are only ever reduced to a depth map (a minimum: order free), so the library keeps them in Morton order of
+  // their positions: neighbouring threads of k_splat_bin then hit neighbouring pixels, and the one atomicMin per point lands in
+  // cache lines other lanes of the wave touch too (measured: 0.41 -> see DESIGN 10.3 ms per 10 M points of a 24 MP image with the
+  // points in random order before).  E3D_REG_SPLAT_ORDER=0 keeps the caller's order.
+  if (reg_switches().splat_order && n > 1 && n < ((size_t)1 << 32)) {
+    hipStream_t s = h->stream;
+    DevBuf<float> bbp, bbo;
+    bbp.reserve(6 * (size_t)kMaxBboxBlocks); bbo.reserve(6);
+    launch_bbox_aos(tmp.p, n, bbp.p, bbo.p, s);
+    float bb[6];
+    copy_out(bb, bbo.p, sizeof bb, s);
+    rsync(h);
+    float ext = 0.f;
+    for (int k = 0; k < 3; ++k) ext = std::max(ext, bb[3 + k] - bb[k]);
+    const float inv = (ext > 0.f && std::isfinite(ext)) ? 1023.f / ext : 0.f;
+    for (int k = 0; k < 2; ++k) { h->sp_keys[k].reserve(n); h->sp_vals[k].reserve(n); }
+    hipLaunchKernelGGL(k_morton_keys, dim3(nblk(n)), dim3(kBlock), 0, s, tmp.p, n, std::isfinite(bb[0]) ? bb[0] : 0.f, std::isfinite(bb[1]) ? bb[1] : 0.f,
+                       std::isfinite(bb[2]) ? bb[2] : 0.f, inv, h->sp_keys[0].p, h->sp_vals[0].p);
+    sort_pairs_u32_u32(h->sp_keys[0].p, h->sp_keys[1].p, h->sp_vals[0].p, h->sp_vals[1].p, n, 30, h->sort_temp, s);
+    hipLaunchKernelGGL(k_gather_xyz_to_float4, dim3(nblk(n)), dim3(kBlock), 0, s, tmp.p, h->sp_vals[1].p, n, h->splat.p);
+  } else {
+    hipLaunchKernelGGL(k_xyz_to_float4, dim3(nblk(n)), dim3(kBlock), 0, h->stream, tmp.p, n, h->splat.p);
+  }
+  rsync(h);
+  h->n_splat = n;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_render_depth(e3d_reg_t* h, int image_id, int image_scale, float* depth_out) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  render_depth(h, image_id, image_scale, depth_out);
+  return 0;
+  E3D_CATCH()
+}
+
+int64_t e3d_reg_observe(e3d_reg_t* h, int image_id, int point_scale, int image_scale, int border_size, const uint32_t* indices,
+                        size_t n_indices) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  return (int64_t)observe(h, image_id, point_scale, image_scale, border_size, indices, n_indices);
+  E3D_CATCH()
+}
+
+int e3d_reg_get_observations(e3d_reg_t* h, int image_id, int point_scale, uint32_t* idx, float* x, float* y, float* scale,
+                             uint8_t* flags) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  Obs& O = get_obs(get_image(h, image_id), point_scale);
+  if (idx) copy_out(idx, O.idx.p, sizeof(unsigned) * O.n, h->stream);
+  if (x) copy_out(x, O.x.p, sizeof(float) * O.n, h->stream);
+  if (y) copy_out(y, O.y.p, sizeof(float) * O.n, h->stream);
+  if (scale) copy_out(scale, O.s.p, sizeof(float) * O.n, h->stream);
+  if (flags) copy_out(flags, O.flags.p, O.n, h->stream);
+  rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_set_observations(e3d_reg_t* h, int image_id, int point_scale, size_t n, const uint32_t* idx, const float* x,
+                             const float* y, const float* scale) {
+  E3D_TRY_ON(h)
+  if (!h || (n && (!idx || !x || !y || !scale))) throw Error(E3D_ERR_INVALID, "null argument");
+  ImageDev& im = get_image(h, image_id);
+  PointScale& S = get_scale(h, point_scale);
+  Obs& O = im.obs[point_scale];
+  O.active = true;
+  O.n = n;
+  O.idx.reserve(n); O.x.reserve(n); O.y.reserve(n); O.s.reserve(n);
+  copy_in(O.idx.p, idx, sizeof(unsigned) * n, h->stream); copy_in(O.x.p, x, sizeof(float) * n, h->stream);
+  copy_in(O.y.p, y, sizeof(float) * n, h->stream); copy_in(O.s.p, scale, sizeof(float) * n, h->stream);
+  O.inten_valid = false;
+  finish_observations(h, S, O);
+  rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_pass1(e3d_reg_t* h, int image_id, int point_scale, float* intensities, float* j_intrinsics, float* j_pose) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  ImageDev& im = get_image(h, image_id);
+  PointScale& S = get_scale(h, point_scale);
+  Obs& O = get_obs(im, point_scale);
+  prepare_rows(h, im, S, O);
+  const int I = cam_param_count(image_model(h, im));
+  const int off_pose = 1 + I + (im.dependent() ? 6 : 0);
+  const size_t stride = 4 * (size_t)rows4(local_unknowns(h, im));
+  std::vector<float> rows(stride * O.n);
+  copy_out(rows.data(), O.rows.p, sizeof(float) * stride * O.n, h->stream);
+  rsync(h);
+  for (size_t i = 0; i < O.n; ++i) {
+    const float* r = rows.data() + stride * i;
+    if (intensities) intensities[i] = r[0];
+    if (j_intrinsics) for (int c = 0; c < I; ++c) j_intrinsics[(size_t)I * i + c] = r[1 + c];
+    if (j_pose) for (int c = 0; c < 6; ++c) j_pose[6 * i + c] = r[off_pose + c];
+  }
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_accumulate(e3d_reg_t* h, int image_id, int point_scale, double* H, double* b, double sums[2], int64_t counts[2]) {
+  E3D_TRY_ON(h)
+  if (!h || !H || !b || !sums || !counts) throw Error(E3D_ERR_INVALID, "null argument");
+  const int V = accumulate_enqueue(h, image_id, point_scale, nullptr, true);
+  const int slot = reg_slot(V);
+  std::vector<double> r(slot);
+  read_back(h, r.data(), h->red.p, sizeof(double) * slot);
+  h->pass1_ms += h->t_pass1->ms(); h->pass2_ms += h->t_pass2->ms();      // (the pass timers of the call just made: the stream is idle)
+  accumulate_unpack(V, r.data(), H, b, sums, counts);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_kernel_times(e3d_reg_t* h, double out[4], int reset) {
+  E3D_TRY_ON(h)
+  if (!h || !out) throw Error(E3D_ERR_INVALID, "null argument");
+  out[0] = h->pass1_ms; out[1] = h->pass2_ms; out[2] = h->pass_observations; out[3] = h->pass_calls;
+  if (reset) { h->pass1_ms = h->pass2_ms = h->pass_observations = h->pass_calls = 0; }
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_profile(e3d_reg_t* h, int enable, char* out, size_t capacity) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  if (out && capacity) {
+    std::string t;
+    for (const auto& kv : h->profile_ms) t += kv.first + "=" + fmt("%.4f", kv.second) + ";";
+    h->kflush();
+    for (const auto& kv : h->kgroups) t += "k:" + kv.first + "=" + fmt("%.4f,%lld,%.0f", kv.second.ms, kv.second.calls, kv.second.units) + ";";
+    std::snprintf(out, capacity, "%s", t.c_str());
+  }
+  if (enable != (h->profile_on ? 1 : 0)) { h->profile_ms.clear(); h->kflush(); h->kgroups.clear(); }
+  h->profile_on = enable != 0;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_cost(e3d_reg_t* h, int image_id, int point_scale, double sums[2], int64_t counts[2]) {
+  E3D_TRY_ON(h)
+  if (!h || !sums || !counts) throw Error(E3D_ERR_INVALID, "null argument");
+  h->red.reserve(4);
+  cost_enqueue(h, image_id, point_scale, h->red.p);
+  double r[4];
+  read_back(h, r, h->red.p, sizeof r);
+  sums[0] = r[0]; sums[1] = r[1]; counts[0] = (int64_t)r[2]; counts[1] = (int64_t)r[3];
+  return 0;
+  E3D_CATCH()
+}
+
+// ---- depth residuals -------------------------------------------------------------------------------------------------------------
+/* Problem::SetFixedDepthMaps for one image (problem.cc:593-595): one f32 depth map per pyramid level of the image's camera
+ * (level_depths[l]: width_l x height_l floats, host or device memory); level_depths == NULL removes them. */
+int e3d_reg_set_depth_maps(e3d_reg_t* h, int image_id, const float* const* level_depths) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  ImageDev& im = get_image(h, image_id);
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  im.depth_maps.clear();
+  if (!level_depths) return 0;
+  im.depth_maps.resize(in.levels.size());
+  for (size_t l = 0; l < in.levels.size(); ++l) {
+    if (!level_depths[l]) throw Error(E3D_ERR_INVALID, "e3d_reg_set_depth_maps: every pyramid level needs a depth map");
+    const size_t px = (size_t)in.levels[l].width * (size_t)in.levels[l].height;
+    im.depth_maps[l].reserve(px);
+    copy_in(im.depth_maps[l].p, level_depths[l], sizeof(float) * px, h->stream);
+  }
+  rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_depth_accumulate(e3d_reg_t* h, int image_id, int point_scale, double* H, double* b, double* sum, int64_t* count) {
+  E3D_TRY_ON(h)
+  if (!h || !H || !b || !sum || !count) throw Error(E3D_ERR_INVALID, "null argument");
+  depth_accumulate(h, image_id, point_scale, H, b, sum, count);
+  return 0;
+  E3D_CATCH()
+}
+int e3d_reg_depth_cost(e3d_reg_t* h, int image_id, int point_scale, double* sum, int64_t* count) {
+  E3D_TRY_ON(h)
+  if (!h || !sum || !count) throw Error(E3D_ERR_INVALID, "null argument");
+  depth_cost(h, image_id, point_scale, sum, count);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_color_begin(e3d_reg_t* h, int point_scale) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  color_begin(h, point_scale);
+  return 0;
+  E3D_CATCH()
+}
+int e3d_reg_color_accumulate(e3d_reg_t* h, int image_id, int point_scale) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  color_accumulate_enqueue(h, image_id, point_scale);
+  rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+int e3d_reg_color_finish(e3d_reg_t* h, int point_scale) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  color_finish(h, point_scale);
+  return 0;
+  E3D_CATCH()
+}
 
 int e3d_reg_set_shard(e3d_reg_t* h, int rank, int world_size, e3d_allreduce_fn allreduce, e3d_allreduce_device_fn allreduce_device,
                       void* user) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   if (world_size < 1 || rank < 0 || rank >= world_size) throw Error(E3D_ERR_INVALID, "bad rank / world size");
   if (world_size > 1 && (!allreduce || !allreduce_device)) throw Error(E3D_ERR_INVALID, "world_size > 1 needs both all-reduce callbacks");
   if (!h->images.empty()) throw Error(E3D_ERR_INVALID, "e3d_reg_set_shard must be called before images are set");
   h->rank = rank; h->world = world_size; h->allreduce = allreduce; h->allreduce_dev = allreduce_device; h->ar_user = user;
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_set_comm(e3d_reg_t* h, e3d_comm_t* comm) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   if (!h->images.empty()) throw Error(E3D_ERR_INVALID, "e3d_reg_set_comm must be called before images are set");
   if (comm && comm->device != h->device) throw Error(E3D_ERR_INVALID, "e3d_reg_set_comm: communicator and handle live on different devices");
@@ -4173,13 +4240,13 @@ int e3d_reg_set_comm(e3d_reg_t* h, e3d_comm_t* comm) {
   h->rank = comm ? comm->rank : 0; h->world = comm ? comm->world : 1;
   h->allreduce = nullptr; h->allreduce_dev = nullptr; h->ar_user = nullptr;
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_image_owner(e3d_reg_t* h, int image_id) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  return h->world <= 1 ? 0 : ((image_id % h->world) + h->world) % h->world;
-  R_CATCH()
+  return image_owner(h, image_id);
+  E3D_CATCH()
 }
 
 /* CreateMultiScalePointCloud, first part (multi_scale_point_cloud.cc:236-262): the radius range of every point over all
@@ -4187,7 +4254,7 @@ int e3d_reg_image_owner(e3d_reg_t* h, int image_id) {
  * current_image_scale) with occlusion, mask and saturation tests but no scale test, then the point radius that projects to
  * half a pixel.  min_radius starts at +inf, max_radius at -inf (points seen by no image keep those values). */
 int e3d_reg_point_radius_minmax(e3d_reg_t* h, const float* xyz, size_t n, float* min_radius, float* max_radius) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (n && (!xyz || !min_radius || !max_radius))) throw Error(E3D_ERR_INVALID, "null argument");
   hipStream_t s = h->stream;
   DevBuf<float> tmp, d_min, d_max;
@@ -4203,7 +4270,7 @@ int e3d_reg_point_radius_minmax(e3d_reg_t* h, const float* xyz, size_t n, float*
     ImageDev& im = kv.second;
     const Intrin& in = h->intr.at(im.intrinsics_id);
     const int scale = best_available_scale(h, in);
-    if (e3d_reg_render_depth(h, kv.first, scale, nullptr) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+    render_depth(h, kv.first, scale, nullptr);
     const int lvl = std::max(0, scale - in.min_image_scale);
     const CamLevel& cam = in.levels[lvl];
     const CamLevel& cam_min = in.levels[0];
@@ -4230,7 +4297,7 @@ int e3d_reg_point_radius_minmax(e3d_reg_t* h, const float* xyz, size_t n, float*
   rsync(h);
   E3D_HIP(hipGetLastError());
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 
 /* Problem::DeterminePointNeighbors (src/opt/problem.cc:706-786): the (candidates + 1) nearest neighbours of every point --
@@ -4239,7 +4306,7 @@ int e3d_reg_point_radius_minmax(e3d_reg_t* h, const float* xyz, size_t n, float*
  * point by point), keeping the first neighbor_count. */
 int e3d_determine_point_neighbors(const float* xyz, size_t n, const uint8_t* scan_indices, int scan_count, int limit_to_same_scan,
                                   int neighbor_count, int candidate_count, uint32_t* neighbor_indices) {
-  R_TRY
+  E3D_TRY
   if ((!xyz && n) || !neighbor_indices || neighbor_count < 1 || candidate_count < neighbor_count) throw Error(E3D_ERR_INVALID, "bad argument");
   if (limit_to_same_scan && (!scan_indices || scan_count < 1)) throw Error(E3D_ERR_INVALID, "scan indices required");
   const int k = candidate_count + 1;
@@ -4277,12 +4344,12 @@ int e3d_determine_point_neighbors(const float* xyz, size_t n, const uint8_t* sca
     run(std::vector<float>(xyz, xyz + 3 * n), nullptr, true);
   }
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 
 // ---- f4: GroundTruthCreator -------------------------------------------------------------------------------------------------
 int e3d_reg_set_scan_points(e3d_reg_t* h, const float* xyz, size_t n) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (n && !xyz)) throw Error(E3D_ERR_INVALID, "null argument");
   if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "more than 2^31-1 scan points");
   h->n_scan = n; h->scan_points_set = true; h->scan_colors_begun = false;
@@ -4296,13 +4363,13 @@ int e3d_reg_set_scan_points(e3d_reg_t* h, const float* xyz, size_t n) {
     rsync(h);
   }
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 static void scan_visibility(e3d_reg* h, int image_id, const uint8_t* mask, int excluded_flag, int mode, int min_count, int radius = 0) {
   ImageDev& im = get_image(h, image_id);
   const Intrin& in = h->intr.at(im.intrinsics_id);
   // RenderDepthMap(intrinsics, image, intrinsics.min_image_scale, ...) + intrinsics.model(0): the highest resolution
-  if (e3d_reg_render_depth(h, image_id, in.min_image_scale, nullptr) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+  render_depth(h, image_id, in.min_image_scale, nullptr);
   const CamLevel& cam = in.levels[0];
   const size_t px = (size_t)cam.width * cam.height;
   if (mask) { h->eval_mask.reserve(px); copy_in(h->eval_mask.p, mask, px, h->stream); }
@@ -4313,32 +4380,32 @@ static void scan_visibility(e3d_reg* h, int image_id, const uint8_t* mask, int e
                                                h->gt_depth.p, radius));
 }
 int e3d_reg_count_scan_observations(e3d_reg_t* h, int image_id, const uint8_t* mask, int excluded_flag) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   scan_visibility(h, image_id, mask, excluded_flag, 0, 0);
   rsync(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_get_scan_observation_counts(e3d_reg_t* h, int32_t* counts) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (!counts && h->n_scan)) throw Error(E3D_ERR_INVALID, "null argument");
   if (h->n_scan) copy_out(counts, h->scan_counts.p, sizeof(int) * h->n_scan, h->stream);
   rsync(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_set_scan_observation_counts(e3d_reg_t* h, const int32_t* counts) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (!counts && h->n_scan)) throw Error(E3D_ERR_INVALID, "null argument");
   if (h->n_scan) copy_in(h->scan_counts.p, counts, sizeof(int) * h->n_scan, h->stream);
   rsync(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_ground_truth_depth(e3d_reg_t* h, int image_id, const uint8_t* mask, int excluded_flag, int min_count, float* gt_depth,
                                float* occlusion_depth) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   ImageDev& im = get_image(h, image_id);
   const CamLevel& cam = h->intr.at(im.intrinsics_id).levels[0];
@@ -4350,7 +4417,7 @@ int e3d_reg_ground_truth_depth(e3d_reg_t* h, int image_id, const uint8_t* mask, 
   if (occlusion_depth) copy_out(occlusion_depth, im.depth.p, sizeof(float) * px, h->stream);
   rsync(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 
 /* CreateGroundTruthForImage, scan rendering part (ground_truth_creator.cc:149,175-187): which scan point ends up on top of every pixel
@@ -4358,7 +4425,7 @@ int e3d_reg_ground_truth_depth(e3d_reg_t* h, int image_id, const uint8_t* mask, 
  * the image keeps its own colour. */
 int e3d_reg_scan_rendering(e3d_reg_t* h, int image_id, const uint8_t* mask, int excluded_flag, int min_count, int point_radius,
                            uint32_t* winner) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || !winner) throw Error(E3D_ERR_INVALID, "null argument");
   if (point_radius < 0 || point_radius > 64) throw Error(E3D_ERR_INVALID, "scan_point_radius out of range [0, 64]");
   if (h->n_scan >= 0xFFFFFFFFull) throw Error(E3D_ERR_INVALID, "too many scan points for 32-bit indices");
@@ -4371,12 +4438,12 @@ int e3d_reg_scan_rendering(e3d_reg_t* h, int image_id, const uint8_t* mask, int 
   copy_out(winner, h->gt_depth.p, sizeof(unsigned) * px, h->stream);
   rsync(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 
 // ---- debug point clouds (Problem::DebugWriteColoredPointCloud, src/opt/problem.cc:642-704) ---------------------------------------
 int e3d_reg_scan_colors_begin(e3d_reg_t* h) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
   h->scan_color_acc.reserve(h->n_scan);
@@ -4384,20 +4451,20 @@ int e3d_reg_scan_colors_begin(e3d_reg_t* h) {
   rsync(h);
   h->scan_colors_begun = true;
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_scan_colors_add_image(e3d_reg_t* h, int image_id, const uint8_t* rgb, int width, int height) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || !rgb) throw Error(E3D_ERR_INVALID, "null argument");
   if (width < 2 || height < 2) throw Error(E3D_ERR_INVALID, "a colour image needs at least 2 x 2 pixels for a bilinear sample");
   if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
   if (!h->scan_colors_begun) throw Error(E3D_ERR_INVALID, "call e3d_reg_scan_colors_begin first");
   ImageDev& im = get_image(h, image_id);
-  if (!h->owns(image_id)) throw Error(E3D_ERR_INVALID, fmt("image %d belongs to rank %d", image_id, e3d_reg_image_owner(h, image_id)));
+  if (!h->owns(image_id)) throw Error(E3D_ERR_INVALID, fmt("image %d belongs to rank %d", image_id, image_owner(h, image_id)));
   if (h->n_scan == 0) return 0;
   const Intrin& in = h->intr.at(im.intrinsics_id);
   const int scale = best_available_scale(h, in);
-  if (e3d_reg_render_depth(h, image_id, scale, nullptr) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+  render_depth(h, image_id, scale, nullptr);
   const int lvl = std::max(0, scale - in.min_image_scale);
   const CamLevel& cam = in.levels[lvl];
   const size_t bytes = (size_t)width * height * 3;
@@ -4416,10 +4483,10 @@ int e3d_reg_scan_colors_add_image(e3d_reg_t* h, int image_id, const uint8_t* rgb
   rsync(h);                          // (the caller's pixels may go away after the call)
   E3D_HIP(hipGetLastError());
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_scan_colors_get_sums(e3d_reg_t* h, float* sums, int32_t* counts) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (h->n_scan && (!sums || !counts))) throw Error(E3D_ERR_INVALID, "null argument");
   if (!h->scan_colors_begun) throw Error(E3D_ERR_INVALID, "call e3d_reg_scan_colors_begin first");
   std::vector<float4> acc(h->n_scan);
@@ -4430,10 +4497,10 @@ int e3d_reg_scan_colors_get_sums(e3d_reg_t* h, float* sums, int32_t* counts) {
     memcpy(&counts[i], &acc[i].w, sizeof(int32_t));
   }
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_scan_colors_set_sums(e3d_reg_t* h, const float* sums, const int32_t* counts) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (h->n_scan && (!sums || !counts))) throw Error(E3D_ERR_INVALID, "null argument");
   if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
   std::vector<float4> acc(h->n_scan);
@@ -4446,10 +4513,10 @@ int e3d_reg_scan_colors_set_sums(e3d_reg_t* h, const float* sums, const int32_t*
   rsync(h);
   h->scan_colors_begun = true;
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_scan_colors_finish(e3d_reg_t* h, uint8_t* rgb) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (h->n_scan && !rgb)) throw Error(E3D_ERR_INVALID, "null argument");
   if (!h->scan_colors_begun) throw Error(E3D_ERR_INVALID, "call e3d_reg_scan_colors_begin first");
   if (h->n_scan) {
@@ -4463,56 +4530,33 @@ int e3d_reg_scan_colors_finish(e3d_reg_t* h, uint8_t* rgb) {
   rsync(h);
   E3D_HIP(hipGetLastError());
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 
 int e3d_reg_update_observations(e3d_reg_t* h, int border_size) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   update_observations(h, border_size);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 // Optimizer::set_cache_observations (optimizer.h)
 int e3d_reg_set_cache_observations(e3d_reg_t* h, int enabled) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   h->cache_observations = enabled != 0;
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
-// ObservationsCache::DetermineAndSaveObservedPointIndices (observations_cache.cc:104-158) without the files: the full
-// visibility test at image scale 0, whose observed point indices become the cached lists.
 int e3d_reg_determine_observed_indices(e3d_reg_t* h) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
-  const int old_scale = h->prm.current_image_scale;
-  const bool old_cache = h->cache_observations;
-  h->prm.current_image_scale = 0;
-  h->cache_observations = false;
-  try { update_observations(h, 1); } catch (...) { h->prm.current_image_scale = old_scale; h->cache_observations = old_cache; throw; }
-  h->prm.current_image_scale = old_scale;
-  h->cache_observations = old_cache;
-  for (auto& kv : h->images) {
-    if (!h->owns(kv.first)) continue;
-    ImageDev& im = kv.second;
-    for (auto& sc : h->scales) {
-      auto& slot = im.observed[sc.first];
-      slot.second = 0;
-      if (!has_obs(im, sc.first)) continue;
-      Obs& O = im.obs.at(sc.first);
-      slot.first.reserve(O.n);
-      if (O.n) E3D_HIP(hipMemcpyAsync(slot.first.p, O.idx.p, sizeof(unsigned) * O.n, hipMemcpyDeviceToDevice, h->stream));
-      slot.second = O.n;
-    }
-    im.has_observed = true;
-  }
-  rsync(h);
+  determine_observed_indices(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int64_t e3d_reg_get_observed_indices(e3d_reg_t* h, int image_id, int point_scale, uint64_t* indices) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   ImageDev& im = get_image(h, image_id);
   get_scale(h, point_scale);
@@ -4526,10 +4570,10 @@ int64_t e3d_reg_get_observed_indices(e3d_reg_t* h, int image_id, int point_scale
     for (size_t i = 0; i < n; ++i) indices[i] = tmp[i];
   }
   return (int64_t)n;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_set_observed_indices(e3d_reg_t* h, int image_id, int point_scale, const uint64_t* indices, size_t count) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || (count && !indices)) throw Error(E3D_ERR_INVALID, "null argument");
   ImageDev& im = get_image(h, image_id);
   PointScale& S = get_scale(h, point_scale);
@@ -4545,30 +4589,30 @@ int e3d_reg_set_observed_indices(e3d_reg_t* h, int image_id, int point_scale, co
   slot.second = count;
   im.has_observed = true;
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_color_update(e3d_reg_t* h) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
   color_update(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_compute_cost(e3d_reg_t* h, double* cost) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || !cost) throw Error(E3D_ERR_INVALID, "null argument");
   *cost = total_cost(h);
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 int e3d_reg_apply(e3d_reg_t* h, int print_progress, int* applied_update, float* lambda, float* max_change) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || !applied_update || !lambda || !max_change) throw Error(E3D_ERR_INVALID, "null argument");
   bool applied = false;
   apply_update(h, print_progress != 0, &applied, lambda, max_change);
   *applied_update = applied ? 1 : 0;
   return 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 
 // bool Optimizer::RunOnCurrentScale(...)  (src/opt/optimizer.cc:49-182); the observation source follows
@@ -4576,7 +4620,7 @@ int e3d_reg_apply(e3d_reg_t* h, int print_progress, int* applied_update, float* 
 int e3d_reg_run_on_current_scale(e3d_reg_t* h, int max_num_iterations, float max_change_convergence_threshold,
                                  int iterations_without_new_optimum_threshold, int print_progress, double* optimum_cost,
                                  int* iterations_done) {
-  R_TRYH
+  E3D_TRY_ON(h)
   if (!h || !optimum_cost) throw Error(E3D_ERR_INVALID, "null argument");
   const bool print = print_progress != 0;
   // never use the highest image scale (optimizer.cc:60-61)
@@ -4585,7 +4629,7 @@ int e3d_reg_run_on_current_scale(e3d_reg_t* h, int max_num_iterations, float max
   if (h->cache_observations) {       // ObservationsCache constructor (observations_cache.cc:39-50), "path does not exist" branch
     bool missing = false;
     for (auto& kv : h->images) missing = missing || (h->owns(kv.first) && !kv.second.has_observed);
-    if (missing && e3d_reg_determine_observed_indices(h) < 0) throw Error(E3D_ERR_INVALID, e3d_last_error());
+    if (missing) determine_observed_indices(h);
   }
   bool converged = false;
   float lambda = 64.0f;
@@ -4595,7 +4639,7 @@ int e3d_reg_run_on_current_scale(e3d_reg_t* h, int max_num_iterations, float max
   int it = 0;
   NormalSystem pending;                 // the next Apply's normal equations, when an iteration's cost came out of them
   bool have_pending = false;
-  static const bool fuse_cost = [] { const char* e = getenv("E3D_REG_FUSE_COST"); return !e || atoi(e) != 0; }();
+  const bool fuse_cost = reg_switches().fuse_cost;
   for (; it < max_num_iterations; ++it) {
     if (print) printf("Iteration %d\n", it + 1);
     bool applied = true;
@@ -4656,6 +4700,6 @@ int e3d_reg_run_on_current_scale(e3d_reg_t* h, int max_num_iterations, float max
   if (iterations_done) *iterations_done = it;
   if (print) fflush(stdout);
   return converged ? 1 : 0;
-  R_CATCH()
+  E3D_CATCH()
 }
 }  // extern "C"

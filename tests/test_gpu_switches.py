@@ -3,7 +3,7 @@ each setting runs in its own interpreter: the certificate search of several dire
 pair or one launch per pair (E3D_ICP_BATCH = 0 / 1; default 2: one launch per kernel and batch), the far lists of a batch keyed, sorted and searched in one launch each against pair by pair (E3D_NN_FAR_BATCH), the LM step's damped solves on host threads (E3D_LM_SOLVE_THREADS), the certificates' motion bound per query against the clouds' global one (E3D_NN_PERQUERY), the key kernel that settles queries with an empty 27-cell block against sorting them all (E3D_NN_PRUNE), certificates tested in every outer iteration against skipped while none holds (E3D_NN_CERT_SKIP) and against no certificates at all (E3D_NN_CERT=0: every query searched in every iteration), resident against compacted correspondence rows (E3D_ICP_RESIDENT), the speculative last LM step
 (E3D_LM_SPECULATE), the row update's per-block results written by the certificate kernel for the blocks it settles whole against the update
 computing them all (E3D_NN_FUSE_UPDATE = 0; E3D_NN_FUSE_GATE = 1: for every certified pair, not only the nearly settled ones), far-list queries that start the bounded search from a probe of their own half cell against sort + row kernel for all of them (E3D_NN_SEED = 0; E3D_NN_SEED_FRAC / _NEAR / _FRESH: from the first search on, other seed distances); the kNN estimator's single scan with sampled thresholds against the two-pass kernels (E3D_KNN_SINGLE), with
-and without the lists the 125-cell pass starts from (E3D_KNN_SEED), the wave-per-query form of that pass (E3D_KNN_WIDE_WAVE), the sampled thresholds from the block population against the distance histogram, and deliberately poor ones (E3D_KNN_EST, E3D_KNN_EST_SCALE), and the switches that change the pass's host-side numbers only (E3D_KNN_CELL_FACTOR, _LEVEL_STEP, _CAP_EXTRA, _WIDE, _DENSE_LOG2, _PINNED, _CAP1 with _REP_TARGET); (B): an iteration's cost taken from the next Apply's accumulation against the separate cost pass (E3D_REG_FUSE_COST = 0)."""
+and without the lists the 125-cell pass starts from (E3D_KNN_SEED), the wave-per-query form of that pass (E3D_KNN_WIDE_WAVE), the sampled thresholds from the block population against the distance histogram, and deliberately poor ones (E3D_KNN_EST, E3D_KNN_EST_SCALE), and the switches that change the pass's host-side numbers only (E3D_KNN_CELL_FACTOR, _LEVEL_STEP, _CAP_EXTRA, _WIDE, _DENSE_LOG2, _PINNED, _CAP1 with _REP_TARGET); (B): an iteration's cost taken from the next Apply's accumulation against the separate cost pass (E3D_REG_FUSE_COST = 0), and the registration's host-side switches that no other test sets (E3D_REG_PINNED = 0, E3D_REG_SPLAT_ORDER = 0, E3D_REG_MIN_FILTER = separable)."""
 import json
 import os
 import subprocess
@@ -239,6 +239,50 @@ def test_reg_cost_from_the_next_accumulation():
         assert f["pass2_launches"] <= p["pass2_launches"], (name, f["pass2_launches"], p["pass2_launches"])
         print("%s: %d iterations, cost launches %d (separate pass: %d), accumulations %d (%d)"
               % (name, f["iterations"], f["cost_launches"], p["cost_launches"], f["pass2_launches"], p["pass2_launches"]))
+
+
+REG_HOST_CODE = r"""
+import importlib, json, sys
+import numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+e3d = importlib.import_module("dataset-pipeline_amd")
+from reg_util import make_multi_image_scene, plane_depth_pyramid
+# the opencv_depth row of REG_CODE: splat render, listed and all-points observation passes, colour update, pass 2 on the matrix cores
+# (V = 14), the depth tables and both cost paths
+M = make_multi_image_scene(n_points=6000, n_images=3, seed=6, perturb=0.006, model=1)
+prm = e3d.default_reg_params(image_scale_count=M["n_levels"], point_neighbor_count=M["K"], variable_residuals_weight=1.0, depth_residuals_weight=0.5)
+G = e3d.RegProblem(prm)
+G.set_intrinsics(0, M["width"], M["height"], M["params"], 0, M["n_levels"], camera_type=M["model"])
+G.set_point_scale(0, M["pts"], M["point_radius"], M["nbr"], M["fixed_desc"]); G.set_splat_points(M["pts"])
+for i, im in enumerate(M["images"]):
+    G.set_image(i, 0, im["pyr"]); G.set_image_pose(i, im["q_init"], im["t_init"])
+    G.set_depth_maps(i, plane_depth_pyramid(M, im))
+G.profile(True)
+conv, cost, its = G.run_on_current_scale(5, 0.0, 15, False)
+G.profile(False)
+poses = [[float(v).hex() for v in np.concatenate([np.ravel(a) for a in G.get_image_pose(i)])] for i in range(3)]
+w, h, pg, _ = G.intrinsics_level(0, 0)
+print("RESULT" + json.dumps({"converged": conv, "iterations": its, "cost": float(cost).hex(), "poses": poses, "intrinsics": [float(v).hex() for v in pg],
+                             "calls": {k: v[1] for k, v in sorted(G.kernel_groups.items())}}))
+""" % (ROOT, os.path.join(ROOT, "tests"))
+
+
+@pytest.mark.timeout(600)
+def test_reg_host_switches_agree():
+    """The registration's host-side switches that change no arithmetic: results read back through pageable instead of pinned memory
+    (E3D_REG_PINNED = 0), the splat points in the caller's instead of Morton order (E3D_REG_SPLAT_ORDER = 0: the depth map is a minimum
+    over them) and the minimum filter of the splat depth in two launches (E3D_REG_MIN_FILTER = separable).  Convergence, iterations,
+    cost, poses and intrinsics bit for bit; the first two launch what the default launches, group by group (the separable filter
+    launches other depth.* kernels by design)."""
+    base = _run(REG_HOST_CODE, {})
+    assert base["iterations"] > 0 and base["calls"].get("accumulate.pass2", 0) > 0 and base["calls"].get("cost", 0) > 0, base
+    result = lambda r: {k: v for k, v in r.items() if k != "calls"}
+    for env, same_launches in (({"E3D_REG_PINNED": "0"}, True), ({"E3D_REG_SPLAT_ORDER": "0"}, True), ({"E3D_REG_MIN_FILTER": "separable"}, False)):
+        other = _run(REG_HOST_CODE, env)
+        print(env, "bit-equal results:", result(other) == result(base), "equal launch counts:", other["calls"] == base["calls"])
+        assert result(other) == result(base), (env, result(other), result(base))
+        if same_launches:
+            assert other["calls"] == base["calls"], (env, other["calls"], base["calls"])
 
 
 @pytest.mark.timeout(900)
