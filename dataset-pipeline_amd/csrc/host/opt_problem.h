@@ -467,9 +467,14 @@ class Problem {
     return std::max<int>(2, (int)(1 + std::ceil(std::log(area_factor) / std::log(4))));
   }
 
-  bool LoadMultiResPointCloud(const std::string& dir) {
+  // false without *fatal: nothing saved there yet (the caller computes and saves the cloud).  A saved cloud that cannot be used --
+  // other neighbour counts than the settings, a damaged file -- is fatal as in the reference (LOG(FATAL), problem.cc:62-160): it is
+  // neither loaded nor overwritten.
+  bool LoadMultiResPointCloud(const std::string& dir, bool* fatal) {
+    *fatal = false;
     std::ifstream f(dir + "/metadata.txt");
     if (!f) return false;
+    auto fail = [&](const std::string& what) { *fatal = true; return this->fail(what); };
     std::string name, version;
     f >> name >> version;
     if (version != "1") return fail("Unsupported multi-res point cloud format version: " + version);
@@ -867,9 +872,11 @@ class Problem {
 
   bool SetMultiResGeometry(const std::vector<PointCloud::Ptr>& scans, const std::string& multi_res_dir) {
     if (multi_res_dir.empty()) return fail("Please specify --multi_res_point_cloud_directory_path.");
-    if (LoadMultiResPointCloud(multi_res_dir)) {
+    bool unusable = false;
+    if (LoadMultiResPointCloud(multi_res_dir, &unusable)) {
       std::cout << "SetScanGeometryAndInitialize(): Loaded existing multi-res point cloud." << std::endl;
     } else {
+      if (unusable) return false;
       if (!ComputeMultiResPointCloud(scans)) return false;
       // saved for faster loading next time (and to keep it constant while camera poses change)
       if (!SaveMultiResPointCloud(multi_res_dir)) return false;

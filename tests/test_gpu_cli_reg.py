@@ -363,6 +363,60 @@ def test_image_registrator_computes_multires_cloud(tmp_path, e3d):
     assert "Loaded existing multi-res point cloud." in out2 and "Creating multi-res point cloud" not in out2
 
 
+def test_image_registrator_cli_neighbour_count_3(tmp_path, e3d):
+    """--point_neighbor_count 3 through the tool: it builds and saves the multi-resolution cloud with 3 neighbours per point, runs
+    every kernel at that count, and a second run on the saved cloud ends at the cost the Python binding reaches on the same cloud.
+    The saved cloud then does not fit the default count: fatal, as in the reference (problem.cc:93-97), and the cloud stays."""
+    from reg_util import pyramid_u8, texture
+    M = make_multi_image_scene(n_points=6000, n_images=3, seed=12, perturb=0.006, K=3)
+    names = ["dslr/img_%d.png" % i for i in range(3)]
+    d = _write_dataset(tmp_path, M, names)
+    shutil.rmtree(os.path.join(d, "cache"))
+    tex = texture(M["pts"][:, 0].astype(np.float64), M["pts"][:, 2].astype(np.float64)).clip(0, 255)
+    write_ply_xyz(os.path.join(d, "scan.ply"), M["pts"], rgb=np.repeat(np.rint(tex).astype(np.uint8)[:, None], 3, 1))
+    out = _run_tool(d, ["--point_neighbor_count", "3"])
+    assert "ComputeMultiResPointCloud(): Creating multi-res point cloud ..." in out and "Finished!" in out
+    meta = open(os.path.join(d, "out", "scale_1_state", "metadata.txt")).read()
+    assert "point_neighbor_count 3" in meta
+    cache_meta = open(os.path.join(d, "cache", "metadata.txt")).read()
+    assert "neighbor_count 3" in cache_meta.replace("neighbor_candidate_count", "candidates")
+    got = _read_cache(os.path.join(d, "cache"))
+    assert len(got) >= 1 and all(g["nbr"].shape == (len(g["pts"]), 3) and g["nbr"].max() < len(g["pts"]) for g in got)
+    # second run: loads the saved cloud (radii as written, 6 digits); the binding runs on exactly that cloud
+    shutil.rmtree(os.path.join(d, "out")); shutil.rmtree(os.path.join(d, "obs_cache"), ignore_errors=True)
+    out2 = _run_tool(d, ["--point_neighbor_count", "3"])
+    assert "Loaded existing multi-res point cloud." in out2 and "Creating multi-res point cloud" not in out2
+    G = e3d.RegProblem(e3d.default_reg_params(image_scale_count=3, point_neighbor_count=3))
+    G.set_intrinsics(0, M["width"], M["height"], M["params"], 0, 3)
+    for s_i, sc in enumerate(got):
+        nbr = sc["nbr"].astype(np.uint32)
+        G.set_point_scale(s_i, sc["pts"], sc["radius"], nbr, (sc["colors"][nbr] - sc["colors"][:, None]).astype(np.float32))
+    G.set_splat_points(M["pts"])
+    for i, im in enumerate(M["images"]):
+        G.set_image(i, 0, pyramid_u8(im["pyr"][0], 3)); G.set_image_pose(i, im["q_init"], im["t_init"])
+    for scale in (1, 0):
+        prm = G.params; prm.current_image_scale = scale; G.set_params(prm)
+        G.set_cache_observations(scale != 1)
+        cost = G.run_on_current_scale(4, 0.0, 15, False)[1]
+        meta = open(os.path.join(d, "out", "scale_%s_state" % ("0.5" if scale == 1 else "1"), "metadata.txt")).read()
+        assert "point_neighbor_count 3" in meta
+        assert np.isfinite(cost) and abs(float(meta.strip().split("optimum_cost ")[1]) - cost) <= 1e-4 * cost
+    st = _read_images_txt(os.path.join(d, "out", "scale_1_state", "images.txt"))
+    for i in range(3):
+        q, t = G.get_image_pose(i)
+        assert np.abs(st[i][0] - q).max() <= 2e-5 and np.abs(st[i][1] - t).max() <= 2e-5
+    # the saved cloud against another neighbour count
+    before = open(os.path.join(d, "cache", "neighbor_point_indices"), "rb").read()
+    cmd = [os.path.join(BIN, "ImageRegistrator"), "--scan_alignment_path", os.path.join(d, "scans.mlp"), "--multi_res_point_cloud_directory_path",
+           os.path.join(d, "cache"), "--image_base_path", os.path.join(d, "images"), "--state_path", os.path.join(d, "state"),
+           "--output_folder_path", os.path.join(d, "out5"), "--observations_cache_path", os.path.join(d, "obs_cache5"),
+           "--max_iterations", "2", "--max_initial_image_area_in_pixels", "3000", "--point_neighbor_count", "5"]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode != 0 and "neighbor_count from file does not fit to the point_neighbor_count setting" in r.stderr
+    assert cache_meta == open(os.path.join(d, "cache", "metadata.txt")).read()
+    assert before == open(os.path.join(d, "cache", "neighbor_point_indices"), "rb").read()
+
+
 @pytest.mark.parametrize("binary", [True, False])
 def test_image_registrator_cli_with_occlusion_mesh(tmp_path, e3d, binary):
     """--occlusion_mesh_path: the wall as a triangle mesh (PLY, binary or ASCII) replaces the scan-point splats as

@@ -1034,6 +1034,21 @@ for model in (1, 2, 0, 9, 4):                  # V = 14, 18 (folded tile), 10, 1
     P.update_observations(1)
     H, b, sums, counts = P.accumulate(0, 0)
     out["H%d" % model] = H; out["b%d" % model] = b; out["s%d" % model] = sums; out["c%d" % model] = counts
+import reg_lists
+for model in (1, 2):                           # the same on a list with gaps (tests/reg_lists.py): keys 101, 102
+    S = reg_lists.scene(5, model)
+    P = e3d.RegProblem(e3d.default_reg_params(image_scale_count=S["n_levels"], point_neighbor_count=S["K"]))
+    P.set_intrinsics(0, S["width"], S["height"], S["params"], 0, S["n_levels"], camera_type=model)
+    P.set_image(0, 0, S["pyr"]); P.set_image_pose(0, S["q"], S["t"])
+    P.set_point_scale(0, S["pts"], S["point_radius"], S["nbr"], S["fixed_desc"])
+    P.set_variable_descriptors(0, S["var_desc"], S["obs_counts"]); P.set_splat_points(S["pts"])
+    P.update_observations(1)
+    o = reg_lists.drop(P.get_observations(0, 0, P.observe(0, 0, 0, 1))[:4], 105)
+    P.set_observations(0, 0, *o)
+    H, b, sums, counts = P.accumulate(0, 0)
+    m = 100 + model
+    out["H%d" % m] = H; out["b%d" % m] = b; out["s%d" % m] = sums; out["c%d" % m] = counts
+    out["i%d" % m] = o[0]; out["f%d" % m] = P.get_observations(0, 0, len(o[0]))[4]
 np.savez(sys.argv[2], **out)
 '''
 
@@ -1067,6 +1082,20 @@ def test_pass2_variants_agree(tmp_path):
             worst = max(worst, eh, eb)
             assert eh <= 1e-7 and eb <= 1e-7, (model, variant, eh, eb)
     print("pass 2 variants: worst deviation", worst)
+    # the same on thinned lists (every tenth observation dropped: rows differ from point indices, four in ten flags are cleared,
+    # the last 64-lane chunk is partial), models 1 and 2
+    for m in (101, 102):
+        ref = res[""]
+        idx, flags = ref["i%d" % m], ref["f%d" % m]
+        assert not np.array_equal(idx, np.arange(len(idx))) and 0.3 <= flags.mean() <= 0.95 and len(idx) % 64 != 0
+        assert ref["c%d" % m][0] == flags.sum() and 0.25 * flags.sum() <= ref["c%d" % m][1] <= 0.75 * flags.sum()
+        for variant in ("tile32", "mfma32", "valu"):
+            g = res[variant]
+            assert np.array_equal(g["c%d" % m], ref["c%d" % m]) and np.array_equal(g["s%d" % m], ref["s%d" % m])
+            d = np.sqrt(np.diag(ref["H%d" % m]))
+            eh = (np.abs(g["H%d" % m] - ref["H%d" % m]) / np.outer(d, d)).max()
+            eb = (np.abs(g["b%d" % m] - ref["b%d" % m]) / d).max() / np.abs(ref["b%d" % m] / d).max()
+            assert eh <= 1e-7 and eb <= 1e-7, (m, variant, eh, eb)
 
 
 _PASS2_RUN_SNIPPET = r'''
