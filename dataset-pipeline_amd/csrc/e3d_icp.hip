@@ -36,10 +36,58 @@ static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 const char* last_error_cstr() { return g_last_error.c_str(); }
 
+// Every environment switch of this file, parsed once at first use; each field carries its default and its parse rule.  "on unless 0" is
+// env_default_on (off only if the value starts with '0'), "off unless 1" env_default_off (on only if it starts with '1'); numbers go
+// through atoi / atof unclamped unless the field says so.  nn_mode, resident and sequential_dsum are initial values: e3d_set_nn_mode and
+// the handle's setters change their copies.  (E3D_ROW_SPAN, E3D_NN_QUAD_LIMIT, E3D_NN_HALF_MIN, E3D_NN_SEED_PROBES: e3d_icp_kernels.hip.)
+struct IcpSwitches {
+  // ---- the grids ----
+  // E3D_NN_MODE: 0 auto (default), 1 per-query, 2 hash-table buckets, 3 dense rows, 4 dense rows + MFMA filter, 5 dense rows with the
+  // half-cell directory of the bounded search built whatever the density and used for every list (tests); outside 0..5: 0
+  int nn_mode = [] { const int v = env_int("E3D_NN_MODE", 0); return (v >= 0 && v <= 5) ? v : 0; }();
+  int half = env_int("E3D_NN_HALF", 1);                // 0 = no half-cell directory (A/B timing), 1 = for dense clouds (default), 2 = always (tests)
+  bool occupancy = env_default_on("E3D_NN_PRUNE");     // on unless 0: occupancy bits of the 27-cell blocks (sort_query_keys_pruned)
+  // E3D_DENSE_CELLS: max cells of a dense directory, strtoull (4 B each; default 2^33 = 32 GB of the 288 GB per cloud); hash table beyond
+  size_t dense_cells = [] { const char* e = getenv("E3D_DENSE_CELLS"); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 33; }();
+  // ---- the certificate search, for the three drivers (find_pair, find_pairs_batched, find_pairs_multi) ----
+  bool use_cert = env_default_on("E3D_NN_CERT");       // on unless 0; 0: every query is searched in every outer iteration
+  bool cert_skip = env_default_on("E3D_NN_CERT_SKIP"); // on unless 0; 0: the certificates are tested in every outer iteration (certify_now)
+  bool per_query = env_default_on("E3D_NN_PERQUERY");  // on unless 0; 0: the clouds' global motion bounds (rounds 2 - 4) instead of the bound per query
+  bool want_stats = env_default_off("E3D_NN_STATS");   // off unless 1: per-pair list lengths on stderr
+  bool nn_profile = env_default_off("E3D_NN_PROFILE"); // off unless 1: wall-clock split of the search (synchronises between the phases, pair by pair)
+  // fractions of the search radius (atof): the bounded search's margin, the near list's reach, what a query without a partner is searched
+  // beyond the radius and the clouds' motion below which it is (prepare_pair)
+  double margin_frac = env_double("E3D_NN_MARGIN", 0.08), near_frac = env_double("E3D_NN_NEAR", 0.4);
+  double np_frac = env_double("E3D_NN_NP_EXTRA", 0.5), np_gate = env_double("E3D_NN_NP_GATE", 0.2);
+  size_t prune_min_list = (size_t)env_double("E3D_NN_PRUNE_MIN", 262144.0);   // atof: shorter far lists are not pruned (sort_query_keys_pruned)
+  // E3D_NN_FAR_DIV, atoll: a far list below 1 / this of the pair's queries takes the bounded search (default 32; <= 0: always -- experiments)
+  long long far_div = [] { const char* e = getenv("E3D_NN_FAR_DIV"); return e ? atoll(e) : 32ll; }();
+  // find_pairs_multi alone (what they do: there)
+  bool fuse_update = env_default_on("E3D_NN_FUSE_UPDATE");                    // on unless 0
+  double fuse_gate = env_double("E3D_NN_FUSE_GATE", 0.003);                   // atof
+  bool far_batch = env_default_on("E3D_NN_FAR_BATCH");                        // on unless 0
+  bool seed_allowed = env_default_on("E3D_NN_SEED");                          // on unless 0
+  double seed_frac = env_double("E3D_NN_SEED_FRAC", 0.3), seed_near = env_double("E3D_NN_SEED_NEAR", 0.4);   // atof
+  bool seed_fresh = env_double("E3D_NN_SEED_FRESH", 0.0) != 0.0;              // atof, on if not zero
+  // ---- the outer iteration (align_meshes) ----
+  // E3D_ICP_BATCH: a value that starts with '0' switches batching off, whatever follows (find_pair, pair by pair); otherwise the mode is
+  // atoi of it, default 2: >= 2 one launch per kernel and batch (find_pairs_multi), else per kernel and pair (find_pairs_batched)
+  bool batching = env_default_on("E3D_ICP_BATCH");
+  int batch_mode = env_int("E3D_ICP_BATCH", 2);
+  bool resident = env_default_on("E3D_ICP_RESIDENT");                         // on unless 0 (e3d_icp_set_resident_rows)
+  bool sequential_dsum = env_default_off("E3D_ICP_SEQUENTIAL_DISTANCE_SUM");  // off unless 1 (e3d_icp_set_sequential_distance_sum)
+  // ---- the LM (lm_compute) ----
+  bool lm_profile = env_default_off("E3D_LM_PROFILE"); // off unless 1: wall-clock split of an outer iteration's LM on the host (stderr; diagnostics only)
+  bool lm_trace = getenv("E3D_LM_TRACE") != nullptr;   // on if set at all, even to 0 or the empty string: a line per LM step on stderr
+  // atoi, default 4: the tries' solves side by side on min(this, 9) host threads once the system has >= 30 unknowns (0 = on the caller's)
+  int solve_threads = env_int("E3D_LM_SOLVE_THREADS", 4);
+  bool speculate = env_default_on("E3D_LM_SPECULATE"); // on unless 0; 0: try 0 always takes the fused pass (lm_compute)
+  int spec_offset = env_int("E3D_LM_SPEC_OFFSET", 0);  // atoi: speculate this many LM steps later (measured and left at 0: lm_compute)
+};
+static const IcpSwitches& icp_switches() { static const IcpSwitches sw; return sw; }
+
 static int g_device = 0;
-// E3D_NN_MODE / e3d_set_nn_mode: 0 auto, 1 per-query, 2 hash-table buckets, 3 dense rows, 4 dense rows + MFMA filter,
-// 5 dense rows with the half-cell directory of the bounded search built whatever the density and used for every list (tests)
-static int g_nn_mode = [] { const char* e = getenv("E3D_NN_MODE"); const int v = e ? atoi(e) : 0; return (v >= 0 && v <= 5) ? v : 0; }();
+static int g_nn_mode = icp_switches().nn_mode;                 // e3d_set_nn_mode
 static std::atomic<unsigned long long> g_grid_generation{0};   // handles run on one host thread per GPU (--gpus N)
 
 // -------------------------------------------------------------------------------------------------
@@ -120,7 +168,6 @@ struct PairJob {
   double dsum = 0.0;
   bool dsum_f32 = false;    // dsum holds the reference's sequential f32 sum (e3d_icp_set_sequential_distance_sum)
   size_t corr_off = 0;
-  bool mine = true;
   PairState* resident = nullptr;   // the pair's rows are the resident ones of this state (else: compacted into cA / cB / cC)
   long long vrows = 0;             // resident: 64 * active groups, the rows an LM pass walks
 };
@@ -185,13 +232,10 @@ struct e3d_icp {
   int max_inner = 150;
   // the progress line's "avg. distance" from the reference's own sum: f32, sequential, in original source order (one device ->
   // host copy of n floats and a host loop per pair; off: f64 sum on the device, which does not stagnate for large clouds)
-  bool sequential_dsum = env_default_off("E3D_ICP_SEQUENTIAL_DISTANCE_SUM");
+  bool sequential_dsum = icp_switches().sequential_dsum;
   DevBuf<float> d2_by_orig;
   std::vector<float> h_d2_by_orig;
-  int nn_mode = 0;                              // 0 auto, 1 per-query kernel, 2 hash-table bucket kernel, 3 dense-directory row kernel, 4 row kernel with MFMA filter
-  // max cells of a dense directory (4 B each; default 2^33 = 32 GB of the 288 GB per cloud, E3D_DENSE_CELLS overrides);
-  // hash table beyond
-  size_t dense_cell_budget = [] { const char* e = getenv("E3D_DENSE_CELLS"); return e ? (size_t)strtoull(e, nullptr, 10) : (size_t)1 << 33; }();
+  int nn_mode = 0;                              // the NN kernel (IcpSwitches::nn_mode / e3d_set_nn_mode at the handle's creation)
   int rank = 0, world = 1;
   e3d_allreduce_fn allreduce = nullptr;
   void* allreduce_user = nullptr;
@@ -215,9 +259,8 @@ struct e3d_icp {
   PinBuf<double> h_total_d2;
   DevBuf<float4> cA, cB, cC;
   size_t corr_used = 0;
-  // e3d_icp_set_resident_rows / E3D_ICP_RESIDENT=0: compacted planes rewritten every outer iteration for every pair (the round-3
-  // data flow; A/B timing, tests)
-  bool resident_rows = env_default_on("E3D_ICP_RESIDENT");
+  // off: compacted planes rewritten every outer iteration for every pair (the round-3 data flow; A/B timing, tests)
+  bool resident_rows = icp_switches().resident;
   bool resident_now = false;                    // this outer iteration keeps resident rows for the pairs of the certificate path
   int lm_prev_end_step = -1;                    // LM step at which the previous outer iteration's LM ended with ten rejections (-1: none yet)
   std::unique_ptr<SolvePool> solve_pool;        // host threads of the LM step's damped solves (systems of >= 30 unknowns)
@@ -271,7 +314,6 @@ struct e3d_icp {
   PinBuf<unsigned> h_prune_count;
   size_t last_corr_total = 0;                   // correspondences of the previous outer iteration (sizes the planes)
   long long nn_global_bound_updates = 0;        // pose updates of a pair that fell back to the clouds' global motion bound (not near-rigid poses)
-  DevBuf<unsigned long long> nn_stats;
   DevBuf<float> lbe_scratch;
 
   std::vector<e3d_icp_pair_record> pair_records;
@@ -292,6 +334,17 @@ static Affine to_affine(const float* T) {
 
 static void sync(e3d_icp* h) { E3D_HIP(hipStreamSynchronize(h->stream)); }
 
+// the handle's cloud table as the pair jobs index it: the movable clouds, then (index = their number) the merged fixed cloud
+static Cloud& cloud_at(e3d_icp* h, int idx) { return idx == (int)h->clouds.size() ? *h->fixed : *h->clouds[idx]; }
+// this rank's share [j0, j0 + n) of a source cloud (cell order); world == 1 => the whole cloud
+struct Slice { size_t j0, n; };
+static Slice slice_of(const e3d_icp* h, const Cloud& src) {
+  const size_t j0 = (size_t)((unsigned __int128)src.n * (unsigned)h->rank / (unsigned)h->world);
+  const size_t j1 = (size_t)((unsigned __int128)src.n * (unsigned)(h->rank + 1) / (unsigned)h->world);
+  return {j0, j1 - j0};
+}
+static void release_rows(PairState& ps) { ps.pA.release(); ps.pB.release(); ps.pC.release(); ps.rows_valid = false; }
+
 static void upload_cloud(e3d_icp* h, Cloud& c, const float* xyz, const float* nrm, size_t n) {
   c.n = n;
   c.raw_xyz.reserve(3 * n);
@@ -307,12 +360,12 @@ static void ensure_bbox_scratch(e3d_icp* h) {
   h->h_bbox.reserve(6);
 }
 
-// E3D_NN_HALF: 0 = no half-cell directory (A/B timing), 1 = for dense clouds (default), 2 = always (tests)
-static int half_mode() { static const int v = [] { const char* e = getenv("E3D_NN_HALF"); return e ? atoi(e) : 1; }(); return v; }
+static void reserve_sort_buffers(e3d_icp* h, size_t n) { h->keys_a.reserve(n); h->keys_b.reserve(n); h->vals_a.reserve(n); h->vals_b.reserve(n); }
 
 // Build the static local-frame grid of a cloud for search radius d (global frame).
 static void build_grid(e3d_icp* h, Cloud& c, float d) {
   hipStream_t s = h->stream;
+  const IcpSwitches& sw = icp_switches();
   ensure_bbox_scratch(h);
   const size_t n = c.n;
   // local bbox
@@ -363,9 +416,9 @@ static void build_grid(e3d_icp* h, Cloud& c, float d) {
   c.cum_motion = 0.0; c.last_motion = 0.0; c.err_max = 0.0;
   unsigned n_cells = 0;
   if (n > 0) {
-    h->keys_a.reserve(n); h->keys_b.reserve(n); h->vals_a.reserve(n); h->vals_b.reserve(n);
+    reserve_sort_buffers(h, n);
     h->counter.reserve(1);
-    if (half_mode() != 0) {
+    if (sw.half != 0) {
       // sub-cell order inside every cell: sort by the 3-bit half-cell code first, then (stable) by the cell key
       unsigned* fk_a = reinterpret_cast<unsigned*>(h->keys_b.p);
       unsigned* fk_b = fk_a + n;
@@ -406,7 +459,7 @@ static void build_grid(e3d_icp* h, Cloud& c, float d) {
   // hash probes per cell group by one coalesced lookup.  288 GB of HBM make this the default; huge sparse grids
   // keep the hash table.
   c.has_dense = false;
-  if (n > 0 && prod + 2.0 <= (double)h->dense_cell_budget) {
+  if (n > 0 && prod + 2.0 <= (double)sw.dense_cells) {
     const size_t ncell = (size_t)prod;
     c.dense_start.reserve(ncell + 2);
     E3D_HIP(hipMemsetAsync(c.dense_start.p, 0, sizeof(unsigned) * (ncell + 2), s));
@@ -419,8 +472,8 @@ static void build_grid(e3d_icp* h, Cloud& c, float d) {
   // per cell of the bounding grid, twice the cell directory -- so it has to fit the same budget three times over (4 + 8 B per
   // cell), and a failed allocation only costs the directory: k_nn_bounded works on whole cells without it
   c.has_half = false;
-  if (c.has_dense && half_mode() != 0 && n > 0 && 3.0 * (prod + 2.0) <= (double)h->dense_cell_budget &&
-      ((double)n >= 4.0 * (double)std::max(n_cells, 1u) || half_mode() == 2 || h->nn_mode == 5)) {
+  if (c.has_dense && sw.half != 0 && n > 0 && 3.0 * (prod + 2.0) <= (double)sw.dense_cells &&
+      ((double)n >= 4.0 * (double)std::max(n_cells, 1u) || sw.half == 2 || h->nn_mode == 5)) {
     const size_t ncell = (size_t)prod;
     bool ok = true;
     try { c.half_prefix.reserve(ncell + 2); }
@@ -436,8 +489,7 @@ static void build_grid(e3d_icp* h, Cloud& c, float d) {
   // occupancy bits of the 27-cell blocks (E3D_NN_PRUNE=0: none): cells / 8 bytes, the unpadded bits of the build in the sort's key
   // buffer when it is large enough
   c.has_occ = false;
-  static const bool want_occ = env_default_on("E3D_NN_PRUNE");
-  if (c.has_dense && want_occ && n > 0) {
+  if (c.has_dense && sw.occupancy && n > 0) {
     const unsigned stride_w = (c.qrange.D[0] + 31u) / 32u;
     const size_t words = (size_t)c.qrange.D[2] * c.qrange.D[1] * stride_w;
     try {
@@ -581,8 +633,6 @@ static double pose_rounding_bound(const Cloud& c, const float* T) {
   return 2.5 * FLT_EPSILON * (std::sqrt(fro) * std::sqrt(R2) + std::sqrt(tt));
 }
 
-// E3D_NN_PERQUERY=0: the certificates use the clouds' global motion bounds (rounds 2 - 4) instead of the bound per query
-static bool per_query_motion() { static const bool on = env_default_on("E3D_NN_PERQUERY"); return on; }
 // largest entry of |L^T L - I|: the singular values of the pose's linear part lie within sqrt(1 -+ 3 dev).  Poses are re-composed in
 // f32 every outer iteration (Tn = R * T) and never re-orthonormalised, so dev grows by ~1e-7 per iteration: the bound per query is
 // scaled by what dev allows (accumulate_pair_motion) instead of being switched off at a fixed tolerance (at 4e-6 a
@@ -616,7 +666,7 @@ static bool relative_map(const float* Ts, const float* Tt, double M[12]) {
 static bool accumulate_pair_motion(PairState& ps, const Cloud& src, const Cloud& tgt, const float* Ts0, const float* Ts1, const float* Tt0, const float* Tt1, double glob) {
   double M0[12], M1[12];
   const double ds = std::max(pose_ortho_dev(Ts0), pose_ortho_dev(Ts1)), dt = std::max(pose_ortho_dev(Tt0), pose_ortho_dev(Tt1));
-  if (!per_query_motion()) { ps.mB += glob; return true; }
+  if (!icp_switches().per_query) { ps.mB += glob; return true; }
   if (!(ds <= kNearRigidDev) || !(dt <= kNearRigidDev) || !relative_map(Ts0, Tt0, M0) || !relative_map(Ts1, Tt1, M1)) {
     ps.mB += glob;
     return false;
@@ -648,7 +698,7 @@ static bool accumulate_pair_motion(PairState& ps, const Cloud& src, const Cloud&
 // the two roundings of a pair's accumulated bound, and the source centre's global position (rho is measured from it)
 static void pair_motion_bounds(const PairState& ps, const Cloud& src, const Cloud& tgt, MotionBound& lo, MotionBound& up) {
   const double err = 2.0 * (src.err_max + tgt.err_max);
-  if (per_query_motion()) {
+  if (icp_switches().per_query) {
     lo.a = round_down_f(ps.mA * (1.0 - 2e-6)); lo.b = round_down_f(ps.mB * (1.0 - 2e-6));
     up.a = round_up_f(ps.mA * (1.0 + 2e-6)); up.b = round_up_f((ps.mB * (1.0 + 2e-6) + err) * (1.0 + 1e-6));
     double cmax = 0;
@@ -701,11 +751,12 @@ static bool launch_rows(int mode, const Cloud& tgt, const float4* srcG, const un
   return true;
 }
 
+struct SortWatch { e3d_icp* h; hipStream_t s; SortWatch(e3d_icp* hh, hipStream_t st) : h(hh), s(st) { h->tm_sort.start(s); } ~SortWatch() { h->tm_sort.stop(s); } };   // tm_sort to the end of the scope
+
 static void sort_query_keys(e3d_icp* h, const Cloud& tgt, const float4* srcG, const unsigned* list, size_t n, const InvMap& im) {
   hipStream_t s = h->stream;
-  h->keys_a.reserve(n); h->keys_b.reserve(n); h->vals_a.reserve(n); h->vals_b.reserve(n);
-  h->tm_sort.start(s);
-  struct Stop { e3d_icp* h; hipStream_t s; ~Stop() { h->tm_sort.stop(s); } } stop_at_return{h, s};
+  reserve_sort_buffers(h, n);
+  SortWatch watch(h, s);
   if (tgt.key_bits <= 31) {   // 8-byte (key, index) pairs through the radix passes
     unsigned* ka = reinterpret_cast<unsigned*>(h->keys_a.p);
     unsigned* kb = reinterpret_cast<unsigned*>(h->keys_b.p);
@@ -719,25 +770,6 @@ static void sort_query_keys(e3d_icp* h, const Cloud& tgt, const float4* srcG, co
   }
 }
 
-// The certificate search's switches, read once for the three drivers (find_pair, find_pairs_batched, find_pairs_multi)
-struct NnSwitches {
-  bool use_cert = env_default_on("E3D_NN_CERT");       // 0: every query is searched in every outer iteration
-  bool want_stats = env_default_off("E3D_NN_STATS");
-  // fractions of the search radius: the bounded search's margin, the near list's reach, what a query without a partner is searched
-  // beyond the radius and the clouds' motion below which it is (prepare_pair)
-  double margin_frac = env_double("E3D_NN_MARGIN", 0.08), near_frac = env_double("E3D_NN_NEAR", 0.4);
-  double np_frac = env_double("E3D_NN_NP_EXTRA", 0.5), np_gate = env_double("E3D_NN_NP_GATE", 0.2);
-  size_t prune_min_list = (size_t)env_double("E3D_NN_PRUNE_MIN", 262144.0);   // shorter far lists are not pruned (sort_query_keys_pruned)
-  // find_pairs_multi alone (what they do: there)
-  bool fuse_update = env_default_on("E3D_NN_FUSE_UPDATE");
-  double fuse_gate = env_double("E3D_NN_FUSE_GATE", 0.003);
-  bool far_batch = env_default_on("E3D_NN_FAR_BATCH");
-  bool seed_allowed = env_default_on("E3D_NN_SEED");
-  double seed_frac = env_double("E3D_NN_SEED_FRAC", 0.3), seed_near = env_double("E3D_NN_SEED_NEAR", 0.4);
-  bool seed_fresh = env_double("E3D_NN_SEED_FRESH", 0.0) != 0.0;
-};
-static const NnSwitches& nn_switches() { static const NnSwitches sw; return sw; }
-
 // Is k_nn_certify worth a pass over this pair's queries?  While two scans are centimetres apart every certificate breaks with every
 // pose update (0.7 ms per outer iteration at 2 x 50 M points for nothing).  After a pass that settled less than 2 % of the queries
 // the pair is searched whole -- the state of the last search still tells which queries had no partner (from_state) -- until half
@@ -745,12 +777,7 @@ static const NnSwitches& nn_switches() { static const NnSwitches sw; return sw; 
 // at that pass.  A wrong guess costs searches, never a
 // result.  E3D_NN_CERT_SKIP=0: always test.
 static bool certify_now(const PairState& ps, const Cloud& src, const Cloud& tgt) {
-  static const bool allow = env_default_on("E3D_NN_CERT_SKIP");
-  return !allow || ps.settled_frac >= 0.02 || ps.matched_frac >= 0.5 || (src.last_motion + tgt.last_motion) < 0.5 * ps.certify_motion;
-}
-static void certify_ran(PairState& ps, const Cloud& src, const Cloud& tgt, size_t n, size_t unsettled) {
-  ps.settled_frac = n ? 1.0 - (double)unsettled / (double)n : 1.0;
-  ps.certify_motion = src.last_motion + tgt.last_motion;
+  return !icp_switches().cert_skip || ps.settled_frac >= 0.02 || ps.matched_frac >= 0.5 || (src.last_motion + tgt.last_motion) < 0.5 * ps.certify_motion;
 }
 
 // The certificate path's variant: the key kernel settles the queries whose 27-cell block holds no target point (k_query_keys_prune:
@@ -760,12 +787,11 @@ static void certify_ran(PairState& ps, const Cloud& src, const Cloud& tgt, size_
 // goes back to the plain key kernel (ps.prune; a fresh state starts over).  E3D_NN_PRUNE=0: never.
 static size_t sort_query_keys_pruned(e3d_icp* h, PairState& ps, const Cloud& tgt, const float4* srcG, const unsigned* list, size_t n, const InvMap& im,
                                      float r2, const CertParams& cert, float* match_d2, bool from_state) {
-  if (!tgt.has_occ || !ps.prune || n < nn_switches().prune_min_list) { sort_query_keys(h, tgt, srcG, list, n, im); return n; }
+  if (!tgt.has_occ || !ps.prune || n < icp_switches().prune_min_list) { sort_query_keys(h, tgt, srcG, list, n, im); return n; }
   hipStream_t s = h->stream;
-  h->keys_a.reserve(n); h->keys_b.reserve(n); h->vals_a.reserve(n); h->vals_b.reserve(n);
+  reserve_sort_buffers(h, n);
   h->prune_count.reserve(1); h->h_prune_count.reserve(1);
-  h->tm_sort.start(s);
-  struct Stop { e3d_icp* h; hipStream_t s; ~Stop() { h->tm_sort.stop(s); } } stop_at_return{h, s};
+  SortWatch watch(h, s);
   const bool k32 = tgt.key_bits <= 31;
   E3D_HIP(hipMemsetAsync(h->prune_count.p, 0, sizeof(unsigned), s));
   launch_query_keys_prune(k32, srcG, list, n, tgt.occ27.p, tgt.occ_stride, tgt.grid, im, tgt.qrange, r2, cert, h->keys_a.p, h->vals_a.p, h->prune_count.p,
@@ -780,16 +806,19 @@ static size_t sort_query_keys_pruned(e3d_icp* h, PairState& ps, const Cloud& tgt
   return kept;
 }
 
-// NN search + compaction for one directed pair; appends to the correspondence planes.
-// Multi-GPU: every rank holds all clouds and handles the slice [j0, j1) of the source cloud (cell order).
 // E3D_NN_PROFILE=1: wall-clock split of the search of one outer iteration (synchronises between the phases; diagnostics only)
 static double g_nn_prof[8];
-static bool nn_profile() { static const bool on = env_default_off("E3D_NN_PROFILE"); return on; }
 struct NnPhase {
   hipStream_t s; int slot; std::chrono::steady_clock::time_point t0;
-  NnPhase(hipStream_t st, int sl) : s(st), slot(sl) { if (nn_profile()) { (void)hipStreamSynchronize(s); t0 = std::chrono::steady_clock::now(); } }
-  ~NnPhase() { if (nn_profile()) { (void)hipStreamSynchronize(s); g_nn_prof[slot] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } }
+  NnPhase(hipStream_t st, int sl) : s(st), slot(sl) { if (icp_switches().nn_profile) { (void)hipStreamSynchronize(s); t0 = std::chrono::steady_clock::now(); } }
+  ~NnPhase() { if (icp_switches().nn_profile) { (void)hipStreamSynchronize(s); g_nn_prof[slot] += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); } }
 };
+static void print_nn_profile(size_t n_pairs) {
+  if (!icp_switches().nn_profile) return;
+  fprintf(stderr, "[nn profile] certify + bounded search %.1f ms, keys + sort %.1f ms, match scan + compaction (+ plane growth) %.1f ms, %zu pairs\n",
+          g_nn_prof[0], g_nn_prof[1], g_nn_prof[2], n_pairs);
+  for (double& v : g_nn_prof) v = 0;
+}
 
 // which search a directed pair takes: the certificate path (per-pair state, results in source order) needs the target's dense
 // directory; only that path keeps resident correspondence rows
@@ -799,10 +828,9 @@ static bool pair_is_dense(const e3d_icp* h, const Cloud& tgt) {
 static bool pair_uses_rows(const e3d_icp* h, const Cloud& tgt) {
   return pair_is_dense(h, tgt) && tgt.has_dense && (h->nn_mode == 0 || h->nn_mode == 3 || h->nn_mode == 5);
 }
-// the far list (queries without a near partner) goes through the bounded search instead of sort + k_nn_rows when it holds less than
-// 1 / E3D_NN_FAR_DIV of the pair's queries (default 32; 0: always the bounded search -- experiments)
+// the far list (queries without a near partner) goes through the bounded search instead of sort + k_nn_rows (IcpSwitches::far_div)
 static bool far_list_is_short(size_t n_far, size_t n) {
-  static const long long div = [] { const char* e = getenv("E3D_NN_FAR_DIV"); return e ? atoll(e) : 32ll; }();
+  const long long div = icp_switches().far_div;
   return n_far > 0 && (div <= 0 || n_far * (size_t)div < n);
 }
 static size_t resident_rows_cap(size_t n) { return div_up(n, 64) * 64; }
@@ -820,8 +848,15 @@ struct BatchItem {
   bool rows_reset = false;             // ensure_resident_rows reset the pair's rows in this outer iteration (find_pairs_multi)
 };
 
+// k_nn_certify has run: the lengths of the two todo lists it left (near, far), and what certify_now wants to know about the pass
+static void certify_ran(BatchItem& it, const unsigned* todo_len) {
+  it.n_near = todo_len[0]; it.n_far = todo_len[1];
+  it.ps->settled_frac = it.n ? 1.0 - (double)(it.n_near + it.n_far) / (double)it.n : 1.0;
+  it.ps->certify_motion = it.src->last_motion + it.tgt->last_motion;
+}
+
 static void prepare_pair(BatchItem& it, float d) {
-  const NnSwitches& sw = nn_switches();
+  const IcpSwitches& sw = icp_switches();
   const Cloud& src = *it.src; const Cloud& tgt = *it.tgt;
   const PairState& ps = *it.ps;
   it.im = make_invmap(tgt);
@@ -895,7 +930,7 @@ static void search_far_list(e3d_icp* h, BatchItem& it, const unsigned* list, flo
 }
 
 static void print_pair_stats(const BatchItem& it) {
-  if (!nn_switches().want_stats) return;
+  if (!icp_switches().want_stats) return;
   fprintf(stderr, "[nn %d->%d] queries %zu bounded %zu rows %zu cum %.3g (last %.3g) err %.3g\n", it.job->src, it.job->tgt, it.n, it.n_near, it.n_far,
           it.cum_pair, it.src->last_motion + it.tgt->last_motion, it.src->err_max + it.tgt->err_max);
 }
@@ -926,16 +961,34 @@ static RowFrames ensure_resident_rows(PairState& ps, const Cloud& src, const Clo
   return {sg, tg, !valid};
 }
 
-static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job, size_t j0, size_t j1,
-                      e3d_icp_iter_record& rec) {
+// Resident rows: bring a pair's planes up to date with its match list (the rows whose partner changed), count, list the active groups;
+// the totals (count, active groups, rewritten rows) and the distance sum stay on the device for the caller's read-back
+static void update_resident_rows(e3d_icp* h, BatchItem& it, const float* match_d2, unsigned long long* totals_out, double* d2_out, e3d_icp_iter_record& rec) {
   hipStream_t s = h->stream;
-  const size_t n = j1 - j0;
-  job.count = 0; job.dsum = 0.0; job.corr_off = h->corr_used;
+  const Cloud& src = *it.src; const Cloud& tgt = *it.tgt;
+  PairState& ps = *it.ps;
+  const RowFrames rf = ensure_resident_rows(ps, src, tgt, it.n, s);
+  h->tm_compact.start(s);
+  launch_corr_update(ps.match.p, ps.plane_match.p, match_d2, it.n, (rf.sg ? src.G4.p : src.L4.p) + it.j0, src.LN.p + it.j0, rf.sg, to_affine(src.T),
+                     rf.tg ? tgt.G4.p : tgt.L4.p, tgt.LN.p, rf.tg, to_affine(tgt.T), ps.pA.p, ps.pB.p, ps.pC.p, h->block_counts.p,
+                     h->block_d2.p, h->block_groups.p, s);
+  h->tm_compact.stop(s);
+  h->tm_scan.start(s);
+  launch_corr_totals(it.n, h->block_counts.p, h->block_d2.p, h->block_groups.p, h->chunk_sum.p, h->chunk_d2.p, h->chunk_groups.p,
+                     totals_out, d2_out, ps.glist.p, s);
+  h->tm_scan.stop(s);
+  rec.nn_update_launches++; rec.nn_kernel_launches += 4;
+}
+
+// NN search + compaction (or resident row update) for one directed pair: this rank's slice of the source cloud against the target
+// (it: who, as search_pairs filled it in; the certificate path adds the pair's state)
+static void find_pair(e3d_icp* h, BatchItem& it, float d, e3d_icp_iter_record& rec) {
+  hipStream_t s = h->stream;
+  PairJob& job = *it.job; Cloud& src = *it.src; Cloud& tgt = *it.tgt;
+  const size_t j0 = it.j0, n = it.n, nb = div_up(n, kBlock);
   if (n == 0 || tgt.n == 0) return;
   const float4* srcG = src.G4.p + j0;
-  const float4* srcLN = src.LN.p + j0;
   h->match_d2.reserve(n);
-  const size_t nb = div_up(n, kBlock);
   h->block_counts.reserve(nb); h->block_offsets.reserve(nb); h->block_d2.reserve(nb);
   h->d_total.reserve(3); h->d_total_d2.reserve(1); h->h_total.reserve(3); h->h_total_d2.reserve(1);
   if (!h->nn_timer) h->nn_timer.reset(new EventTimer());
@@ -943,18 +996,15 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
   // query.  All are exact and return identical results.  The default row kernel keeps a per-query certificate between the
   // outer iterations: a query whose partner of the last iteration is provably still its unique nearest neighbour is settled
   // by k_nn_certify (one gather), only the others are sorted and searched.
-  const bool dense = pair_is_dense(h, tgt);
-  const bool rows = pair_uses_rows(h, tgt);
-  PairState* rstate = nullptr;
+  const bool dense = pair_is_dense(h, tgt), rows = pair_uses_rows(h, tgt);
   const unsigned* order = nullptr;
-  int* match_pos = nullptr;
+  if (!rows) h->match_pos.reserve(n);
+  int* match_pos = h->match_pos.p;                         // (the certificate path: the pair's own list, ps.match)
   // the timer brackets the search kernels themselves (what rocprofv3 reports for them); keys + sort are part of t_nn_ms
   if (rows) {
     PairState& ps = pair_state_for(h, job.src, job.tgt, src, tgt, j0, n);
-    if (h->resident_now) rstate = &ps;
+    it.ps = &ps;
     match_pos = ps.match.p;
-    BatchItem it{};
-    it.job = &job; it.src = &src; it.tgt = &tgt; it.j0 = j0; it.n = n; it.ps = &ps;
     prepare_pair(it, d);
     if (it.certified) {
       NnPhase ph(s, 0);
@@ -970,16 +1020,13 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
       sync(h);
       { const double t = h->nn_timer_c->ms(); rec.t_nn_certify_ms += t; rec.t_nn_query_ms += t; }
       rec.nn_certify_launches++; rec.nn_certify_queries += (long long)n; rec.nn_kernel_launches++;
-      it.n_near = h->h_todo.p[0]; it.n_far = h->h_todo.p[1];
-      certify_ran(ps, src, tgt, n, it.n_near + it.n_far);
+      certify_ran(it, h->h_todo.p);
       search_bounded_lists(h, it, h->todo_near.p, h->todo_far.p, h->match_d2.p, d, rec);
     }
     search_far_list(h, it, it.certified ? h->todo_far.p : nullptr, h->match_d2.p, d, h->nn_timer.get(), rec);
     ps.fresh = false;
     print_pair_stats(it);
   } else if (dense) {
-    h->match_pos.reserve(n);
-    match_pos = h->match_pos.p;
     const InvMap im = make_invmap(tgt);
     sort_query_keys(h, tgt, srcG, nullptr, n, im);
     h->nn_timer->start(s);
@@ -995,8 +1042,6 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
     order = source_order ? nullptr : h->vals_b.p;
     rec.nn_search_launches++; rec.nn_search_queries += (long long)n; rec.nn_kernel_launches += 2; rec.nn_sort_calls++;
   } else {
-    h->match_pos.reserve(n);
-    match_pos = h->match_pos.p;
     rec.nn_search_launches++; rec.nn_search_queries += (long long)n; rec.nn_kernel_launches++;
     h->nn_timer->start(s);
     launch_nn_query(srcG, n, tgt.G4.p, tgt.table.p, tgt.grid, make_invmap(tgt), radius_sq(d), h->match_pos.p,
@@ -1005,29 +1050,17 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
   h->nn_timer->stop(s);
   NnPhase ph3(s, 2);                                                 // (its constructor waits for the search kernels)
   h->chunk_sum.reserve(div_up(nb, 256) + 1); h->chunk_d2.reserve(div_up(nb, 256) + 1);
-  if (rstate) {
-    // resident rows: bring the pair's planes up to date with the match list (rows whose partner changed), count, list the groups
-    PairState& ps = *rstate;
-    const RowFrames rf = ensure_resident_rows(ps, src, tgt, n, s);
-    const bool sg = rf.sg, tg = rf.tg;
+  const bool resident = rows && h->resident_now;
+  if (resident) {
     h->block_groups.reserve(nb); h->chunk_groups.reserve(2 * (div_up(nb, 256) + 1));
-    h->tm_compact.start(s);
-    launch_corr_update(ps.match.p, ps.plane_match.p, h->match_d2.p, n, (sg ? src.G4.p : src.L4.p) + j0, srcLN, sg, to_affine(src.T),
-                       tg ? tgt.G4.p : tgt.L4.p, tgt.LN.p, tg, to_affine(tgt.T), ps.pA.p, ps.pB.p, ps.pC.p, h->block_counts.p,
-                       h->block_d2.p, h->block_groups.p, s);
-    h->tm_compact.stop(s);
-    h->tm_scan.start(s);
-    launch_corr_totals(n, h->block_counts.p, h->block_d2.p, h->block_groups.p, h->chunk_sum.p, h->chunk_d2.p, h->chunk_groups.p,
-                       h->d_total.p, h->d_total_d2.p, ps.glist.p, s);
-    h->tm_scan.stop(s);
-    rec.nn_update_launches++; rec.nn_kernel_launches += 4;
+    update_resident_rows(h, it, h->match_d2.p, h->d_total.p, h->d_total_d2.p, rec);
     copy_out(h->h_total.p + 1, h->d_total.p + 1, 2 * sizeof(unsigned long long), s);
   } else {
-  h->tm_scan.start(s);
-  launch_match_scan(match_pos, h->match_d2.p, n, h->block_counts.p, h->block_offsets.p, h->block_d2.p,
-                    h->chunk_sum.p, h->chunk_d2.p, h->d_total.p, h->d_total_d2.p, s);
-  h->tm_scan.stop(s);
-  rec.nn_kernel_launches += 4;
+    h->tm_scan.start(s);
+    launch_match_scan(match_pos, h->match_d2.p, n, h->block_counts.p, h->block_offsets.p, h->block_d2.p,
+                      h->chunk_sum.p, h->chunk_d2.p, h->d_total.p, h->d_total_d2.p, s);
+    h->tm_scan.stop(s);
+    rec.nn_kernel_launches += 4;
   }
   copy_out(h->h_total.p, h->d_total.p, sizeof(unsigned long long), s);
   copy_out(h->h_total_d2.p, h->d_total_d2.p, sizeof(double), s);
@@ -1035,7 +1068,7 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
   { const double t = h->nn_timer->ms(); rec.t_nn_query_ms += t; rec.t_nn_search_ms += t; }
   job.count = (long long)h->h_total.p[0];
   job.dsum = h->h_total_d2.p[0];
-  if (rows) pair_state_for(h, job.src, job.tgt, src, tgt, j0, n).matched_frac = (double)job.count / (double)n;
+  if (rows) it.ps->matched_frac = (double)job.count / (double)n;
   if (h->sequential_dsum && !h->comm && h->world <= 1 && n == src.n) {
     h->d2_by_orig.reserve(n); h->h_d2_by_orig.resize(n);
     launch_match_d2_by_original(match_pos, h->match_d2.p, order, n, srcG, h->d2_by_orig.p, s);
@@ -1045,8 +1078,8 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
     for (size_t i = 0; i < n; ++i) { const float v = h->h_d2_by_orig[i]; if (v >= 0.f) distance_sum += v; }
     job.dsum = (double)distance_sum; job.dsum_f32 = true;
   }
-  if (rstate) {
-    job.resident = rstate;
+  if (resident) {
+    job.resident = it.ps;
     job.vrows = 64 * (long long)h->h_total.p[1];
     rec.corr_rows_rewritten += (long long)h->h_total.p[2];
     rec.corr_rows_walked += job.vrows;
@@ -1061,7 +1094,7 @@ static void find_pair(e3d_icp* h, Cloud& src, Cloud& tgt, float d, PairJob& job,
     h->cC.grow_keep(ncap, h->corr_used, s);
   }
   h->tm_compact.start(s);
-  launch_compact_corr(match_pos, order, n, h->block_offsets.p, srcG, srcLN,
+  launch_compact_corr(match_pos, order, n, h->block_offsets.p, srcG, src.LN.p + j0,
                       to_affine(src.T), tgt.G4.p, tgt.LN.p, to_affine(tgt.T), h->cA.p, h->cB.p, h->cC.p,
                       h->corr_used, s);   // the merged fixed cloud keeps T = identity (exact)
   h->tm_compact.stop(s);
@@ -1137,28 +1170,14 @@ static void find_pairs_batched(e3d_icp* h, std::vector<BatchItem>& items, float 
   for (size_t i = 0; i < B; ++i) {
     BatchItem& it = items[i];
     e3d_icp::PairSlot& sl = *h->slots[i];
-    Cloud& src = *it.src; Cloud& tgt = *it.tgt;
-    PairState& ps = *it.ps;
-    const size_t n = it.n;
     if (it.certified) {
-      it.n_near = h->h_todo_all.p[2 * i]; it.n_far = h->h_todo_all.p[2 * i + 1];
-      certify_ran(ps, src, tgt, n, it.n_near + it.n_far);
+      certify_ran(it, h->h_todo_all.p + 2 * i);
       search_bounded_lists(h, it, sl.todo_near.p, sl.todo_far.p, sl.match_d2.p, d, rec);
     }
     search_far_list(h, it, it.certified ? sl.todo_far.p : nullptr, sl.match_d2.p, d, nullptr, rec);
-    ps.fresh = false;
+    it.ps->fresh = false;
     print_pair_stats(it);
-    const RowFrames rf = ensure_resident_rows(ps, src, tgt, n, s);
-    h->tm_compact.start(s);
-    launch_corr_update(ps.match.p, ps.plane_match.p, sl.match_d2.p, n, (rf.sg ? src.G4.p : src.L4.p) + it.j0, src.LN.p + it.j0, rf.sg, to_affine(src.T),
-                       rf.tg ? tgt.G4.p : tgt.L4.p, tgt.LN.p, rf.tg, to_affine(tgt.T), ps.pA.p, ps.pB.p, ps.pC.p, h->block_counts.p,
-                       h->block_d2.p, h->block_groups.p, s);
-    h->tm_compact.stop(s);
-    h->tm_scan.start(s);
-    launch_corr_totals(n, h->block_counts.p, h->block_d2.p, h->block_groups.p, h->chunk_sum.p, h->chunk_d2.p, h->chunk_groups.p,
-                       h->d_totals_all.p + 3 * i, h->d_d2_all.p + i, ps.glist.p, s);
-    h->tm_scan.stop(s);
-    rec.nn_update_launches++; rec.nn_kernel_launches += 4;
+    update_resident_rows(h, it, sl.match_d2.p, h->d_totals_all.p + 3 * i, h->d_d2_all.p + i, rec);
   }
   read_back_batch(h, items, rec);
 }
@@ -1175,7 +1194,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
   hipStream_t s = h->stream;
   const size_t B = items.size();
   for (const BatchItem& it : items) if (!it.tgt->has_half || h->nn_mode == 5) return false;
-  const NnSwitches& sw = nn_switches();
+  const IcpSwitches& sw = icp_switches();
   while (h->slots.size() < B) h->slots.emplace_back(new e3d_icp::PairSlot());
   h->h_todo_all.reserve(2 * kPairBatch); h->d_todo_all.reserve(2 * kPairBatch);
   h->d_totals_all.reserve(3 * kPairBatch); h->d_d2_all.reserve(kPairBatch); h->h_totals_all.reserve(3 * kPairBatch); h->h_d2_all.reserve(kPairBatch);
@@ -1203,8 +1222,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
     P.match = ps.match.p; P.match2 = ps.match2.p; P.lbe = ps.lbe.p; P.match_d2 = sl.match_d2.p;
     P.todo_near = sl.todo_near.p; P.todo_far = sl.todo_far.p; P.counts = h->d_todo_all.p + 2 * i;
     P.n = (unsigned)n; P.none_near = it.none_near ? 1 : 0;
-    P.cum_up = it.cum_up;
-    P.near2 = it.near2;
+    P.cum_up = it.cum_up; P.near2 = it.near2;
     P.g = tgt.grid; P.im = it.im; P.qr = tgt.qrange; P.bp = it.bp;
     P.Psrc = (sg ? src.G4.p : src.L4.p) + it.j0; P.LNsrc = src.LN.p + it.j0; P.Ptgt = tg ? tgt.G4.p : tgt.L4.p; P.LNtgt = tgt.LN.p;
     P.src_global = sg ? 1 : 0; P.tgt_global = tg ? 1 : 0; P.Tsrc = to_affine(src.T); P.Ttgt = to_affine(tgt.T);
@@ -1247,22 +1265,21 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
   // ---- phase B: the bounded searches as list jobs of ONE launch, long far lists pair by pair, row update, totals ----------------
   unsigned job_blocks = 0;
   long long job_queries = 0;
+  auto add_job = [&](size_t i, const unsigned* list, size_t n_list) {
+    if (!n_list) return;
+    const int jb = T.n_jobs++;
+    T.job_pair[jb] = (int)i; T.job_list[jb] = list; T.job_n[jb] = (unsigned)n_list;
+    job_blocks += (unsigned)div_up(n_list, kBlock); T.job_end[jb] = job_blocks;
+    job_queries += (long long)n_list;
+  };
   for (size_t i = 0; i < B; ++i) {
     BatchItem& it = items[i];
     if (!it.certified) continue;
     e3d_icp::PairSlot& sl = *h->slots[i];
-    it.n_near = h->h_todo_all.p[2 * i]; it.n_far = h->h_todo_all.p[2 * i + 1];
-    certify_ran(*it.ps, *it.src, *it.tgt, it.n, it.n_near + it.n_far);
-    auto add_job = [&](const unsigned* list, size_t n_list) {
-      if (!n_list) return;
-      const int jb = T.n_jobs++;
-      T.job_pair[jb] = (int)i; T.job_list[jb] = list; T.job_n[jb] = (unsigned)n_list;
-      job_blocks += (unsigned)div_up(n_list, kBlock); T.job_end[jb] = job_blocks;
-      job_queries += (long long)n_list;
-    };
-    add_job(sl.todo_near.p, it.n_near);
+    certify_ran(it, h->h_todo_all.p + 2 * i);
+    add_job(i, sl.todo_near.p, it.n_near);
     if (far_list_is_short(it.n_far, it.n)) {                  // (few queries without a near partner: search_bounded_lists)
-      add_job(sl.todo_far.p, it.n_far);
+      add_job(i, sl.todo_far.p, it.n_far);
       it.n_near += it.n_far; it.n_far = 0;
     }
   }
@@ -1317,7 +1334,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
       T.far_end[i] = key_blocks;
     }
     T.key_shift = kb_max;
-    h->keys_a.reserve(far_total); h->keys_b.reserve(far_total); h->vals_a.reserve(far_total); h->vals_b.reserve(far_total);
+    reserve_sort_buffers(h, far_total);
     constexpr size_t kCounts = 1 + 2 * (size_t)kNnBatchPairs;
     h->prune_count.reserve(kCounts); h->h_prune_count.reserve(kCounts);
     E3D_HIP(hipMemcpyAsync(h->d_batch.p, h->h_batch.p, sizeof(NnBatchDev), hipMemcpyHostToDevice, s));
@@ -1339,13 +1356,8 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
       row_blocks += (unsigned)div_up((size_t)kept, kBlock);
       T.rows_end[i] = row_blocks;
       if (kept > 0) rec.nn_search_queries += (long long)kept;
-      if (seeded > 0) {                                     // the seeded queries: one more list job of the bounded search
-        const int jb = T.n_jobs++;
-        T.job_pair[jb] = (int)i; T.job_list[jb] = P.seed_list; T.job_n[jb] = seeded;
-        job_blocks += (unsigned)div_up((size_t)seeded, kBlock); T.job_end[jb] = job_blocks;
-        job_queries += (long long)seeded;
-        it.n_near += seeded; it.n_far -= std::min((size_t)seeded, it.n_far);
-      }
+      add_job(i, P.seed_list, seeded);                      // the seeded queries: one more list job of the bounded search
+      it.n_near += seeded; it.n_far -= std::min((size_t)seeded, it.n_far);
     }
     launch_bounded_jobs();
     if (kept_total > 0) {
@@ -1405,13 +1417,12 @@ static int lm_blocks_for(long long n, int n_sets = 1) {
 static bool sharded(const e3d_icp* h) { return h->comm != nullptr || h->world > 1 || h->allreduce != nullptr; }
 
 // E3D_LM_PROFILE=1: wall-clock split of an outer iteration's LM on the host (stderr; diagnostics only)
-static bool lm_profile() { static const bool on = [] { const char* e = getenv("E3D_LM_PROFILE"); return e && e[0] == '1'; }(); return on; }
 struct LmProf { double solve_ms = 0, eval_ms = 0, reduce_ms = 0, prepare_ms = 0, callback_ms = 0, callback_max = 0, wait_max = 0; int solves = 0, evals = 0; };
 static thread_local LmProf g_lm_prof;
 struct LmTick {
   double& acc; std::chrono::steady_clock::time_point t0;
-  explicit LmTick(double& a) : acc(a) { if (lm_profile()) t0 = std::chrono::steady_clock::now(); }
-  ~LmTick() { if (lm_profile()) acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
+  explicit LmTick(double& a) : acc(a) { if (icp_switches().lm_profile) t0 = std::chrono::steady_clock::now(); }
+  ~LmTick() { if (icp_switches().lm_profile) acc += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
 // sum of the per-set results (n doubles, already reduced over this rank's blocks) over the ranks: in place in HBM on the
@@ -1446,13 +1457,41 @@ static void reduce_host(e3d_icp* h, double* buf, size_t n) {
 }
 
 struct LmSystem {
-  int n_impl = 0, nv = 0;
+  int nv = 0;
   std::vector<PairJob*> sets;        // this rank's non-empty pairs, grouped by mode
-  std::vector<int> mode_begin, mode_blocks, mode_block_base;   // per mode 1..3
+  std::vector<int> mode_blocks, mode_block_base;   // per mode 1..3
   int total_blocks = 0;
-  std::vector<double> H, b;
-  double cost = 0;
 };
+
+// a pair's inner poses as the LM kernels read them (LmSet and LmPose hold the same four arrays)
+static void pack_pose(const SE3f& src, const SE3f& tgt, float* Rs, float* Rt, float* ts, float* tt) {
+  quat_to_matrix<float>(src.q.w, src.q.x, src.q.y, src.q.z, Rs);
+  quat_to_matrix<float>(tgt.q.w, tgt.q.x, tgt.q.y, tgt.q.z, Rt);
+  for (int k = 0; k < 3; ++k) { ts[k] = src.t[k]; tt[k] = tgt.t[k]; }
+}
+
+// What every LM pass ends with: the launch under the handle's stop-watch, the per-set reduction, the sums over the ranks (every rank
+// holds the same sets -- lm_prepare --, so the per-set blocks add up) and to the host.  Returns the kernels' time.
+template <class Launch>
+static float lm_run_pass(e3d_icp* h, int ns, e3d_icp_iter_record& rec, Launch launch) {
+  hipStream_t s = h->stream;
+  if (!h->lm_timer) h->lm_timer.reset(new EventTimer());
+  EventTimer& tm = *h->lm_timer;
+  tm.start(s);
+  launch();
+  tm.stop(s);
+  launch_lm_reduce(h->d_partial.p, h->d_sets.p, ns, kLmSlot, h->d_setsum.p, s);
+  reduce_setsums(h, ns);
+  const float ms = tm.ms();
+  rec.t_lm_kernel_ms += ms;
+  return ms;
+}
+
+// a set's 6 x 6 block (upper triangle, 21 sums in row order) and its six right-hand sides into the system at unknown `at`
+static void add_upper6(std::vector<double>& H, int nv, int at, const double* r) {
+  for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) H[(size_t)(at + a) * nv + at + c] += *r++;
+}
+static void add_b6(std::vector<double>& b, int at, const double* r) { for (int a = 0; a < 6; ++a) b[at + a] += r[a]; }
 
 // Evaluate cost (+ H, b when full) at the given inner poses.
 static void lm_evaluate(e3d_icp* h, LmSystem& L, const std::vector<SE3f>& poses, bool full, std::vector<double>& H,
@@ -1464,57 +1503,40 @@ static void lm_evaluate(e3d_icp* h, LmSystem& L, const std::vector<SE3f>& poses,
   H.assign((size_t)nv * nv, 0.0);
   b.assign((size_t)nv, 0.0);
   cost = 0.0;
-  if (ns > 0) {
-    for (int i = 0; i < ns; ++i) {
-      LmSet& S = h->h_sets.p[i];
-      const SE3f& ps = poses[L.sets[i]->impl_src];
-      const SE3f& pt = poses[L.sets[i]->impl_tgt];
-      quat_to_matrix<float>(ps.q.w, ps.q.x, ps.q.y, ps.q.z, S.Rs);
-      quat_to_matrix<float>(pt.q.w, pt.q.x, pt.q.y, pt.q.z, S.Rt);
-      for (int k = 0; k < 3; ++k) { S.ts[k] = ps.t[k]; S.tt[k] = pt.t[k]; }
-    }
-    E3D_HIP(hipMemcpyAsync(h->d_sets.p, h->h_sets.p, sizeof(LmSet) * ns, hipMemcpyHostToDevice, s));
-    if (!h->lm_timer) h->lm_timer.reset(new EventTimer());
-    EventTimer& tm = *h->lm_timer;
-    tm.start(s);
+  if (full) rec.full_passes++; else rec.cost_passes++;
+  if (ns == 0) return;
+  for (int i = 0; i < ns; ++i) {
+    LmSet& S = h->h_sets.p[i];
+    pack_pose(poses[L.sets[i]->impl_src], poses[L.sets[i]->impl_tgt], S.Rs, S.Rt, S.ts, S.tt);
+  }
+  E3D_HIP(hipMemcpyAsync(h->d_sets.p, h->h_sets.p, sizeof(LmSet) * ns, hipMemcpyHostToDevice, s));
+  const float ms = lm_run_pass(h, ns, rec, [&] {
     if (full) {
       for (int m = 1; m <= 3; ++m)
         launch_lm_pass(m, h->d_sets.p, h->d_block_set.p, L.mode_block_base[m], L.mode_blocks[m], h->d_partial.p, s);
     } else {
       launch_lm_pass(kModeCost, h->d_sets.p, h->d_block_set.p, 0, L.total_blocks, h->d_partial.p, s);
     }
-    tm.stop(s);
-    launch_lm_reduce(h->d_partial.p, h->d_sets.p, ns, kLmSlot, h->d_setsum.p, s);
-    reduce_setsums(h, ns);      // every rank holds the same sets (lm_prepare), so the per-set blocks add up across the ranks
-    rec.t_lm_kernel_ms += tm.ms();
-    if (full) { rec.full_passes++; rec.t_lm_full_kernel_ms += tm.ms(); } else rec.cost_passes++;
-    // scatter the per-set systems into H, b  (Accumulate, icp_point_to_plane_impl.h:82-113)
-    for (int i = 0; i < ns; ++i) {
-      const double* r = h->h_setsum.p + (size_t)kLmSlot * i;
-      cost += r[0];
-      if (!full) continue;
-      const PairJob& pj = *L.sets[i];
-      const int si = 6 * (pj.impl_src - 1), ti = 6 * (pj.impl_tgt - 1);
-      const LmSet& S = h->h_sets.p[i];
-      if (S.mode == kModeOne) {
-        const int vi = (S.side == 0) ? si : ti;
-        int k = 1;
-        for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) H[(size_t)(vi + a) * nv + vi + c] += r[k++];
-        for (int a = 0; a < 6; ++a) b[vi + a] += r[22 + a];
-      } else {
-        int k = 1;
-        for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) H[(size_t)(si + a) * nv + si + c] += r[k++];
-        for (int a = 0; a < 6; ++a) b[si + a] += r[22 + a];
-        k = 28;
-        for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) H[(size_t)(ti + a) * nv + ti + c] += r[k++];
-        for (int a = 0; a < 6; ++a) b[ti + a] += r[49 + a];
-        if (S.mode == kModeTwoCross)
-          for (int a = 0; a < 6; ++a) for (int c = 0; c < 6; ++c) H[(size_t)(si + a) * nv + ti + c] += r[55 + 6 * a + c];
-        // kModeTwo: the (src,tgt) block lies in the lower triangle, which the solver never reads [QUIRK]
-      }
+  });
+  if (full) rec.t_lm_full_kernel_ms += ms;
+  // scatter the per-set systems into H, b  (Accumulate, icp_point_to_plane_impl.h:82-113)
+  for (int i = 0; i < ns; ++i) {
+    const double* r = h->h_setsum.p + (size_t)kLmSlot * i;
+    cost += r[0];
+    if (!full) continue;
+    const PairJob& pj = *L.sets[i];
+    const int si = 6 * (pj.impl_src - 1), ti = 6 * (pj.impl_tgt - 1);
+    const LmSet& S = h->h_sets.p[i];
+    if (S.mode == kModeOne) {
+      const int vi = (S.side == 0) ? si : ti;
+      add_upper6(H, nv, vi, r + 1); add_b6(b, vi, r + 22);
+    } else {
+      add_upper6(H, nv, si, r + 1); add_b6(b, si, r + 22);
+      add_upper6(H, nv, ti, r + 28); add_b6(b, ti, r + 49);
+      if (S.mode == kModeTwoCross)
+        for (int a = 0; a < 6; ++a) for (int c = 0; c < 6; ++c) H[(size_t)(si + a) * nv + ti + c] += r[55 + 6 * a + c];
+      // kModeTwo: the (src,tgt) block lies in the lower triangle, which the solver never reads [QUIRK]
     }
-  } else {
-    if (full) rec.full_passes++; else rec.cost_passes++;
   }
 }
 
@@ -1526,38 +1548,26 @@ static void lm_evaluate_costs(e3d_icp* h, LmSystem& L, const std::vector<std::ve
   const int ns = (int)L.sets.size();
   const int np = (int)cand.size();
   costs.assign(np, 0.0);
-  if (ns > 0) {
-    h->h_poses.reserve((size_t)np * ns);
-    h->d_poses.reserve((size_t)kLmMaxPoses * ns);
-    for (int k = 0; k < np; ++k)
-      for (int i = 0; i < ns; ++i) {
-        LmPose& P = h->h_poses.p[(size_t)k * ns + i];
-        const SE3f& ps = cand[k][L.sets[i]->impl_src];
-        const SE3f& pt = cand[k][L.sets[i]->impl_tgt];
-        quat_to_matrix<float>(ps.q.w, ps.q.x, ps.q.y, ps.q.z, P.Rs);
-        quat_to_matrix<float>(pt.q.w, pt.q.x, pt.q.y, pt.q.z, P.Rt);
-        for (int c = 0; c < 3; ++c) { P.ts[c] = ps.t[c]; P.tt[c] = pt.t[c]; }
-      }
-    E3D_HIP(hipMemcpyAsync(h->d_poses.p, h->h_poses.p, sizeof(LmPose) * (size_t)np * ns, hipMemcpyHostToDevice, s));
-    if (!h->lm_timer) h->lm_timer.reset(new EventTimer());
-    EventTimer& tm = *h->lm_timer;
-    tm.start(s);
-    launch_lm_cost_multi(h->d_sets.p, h->d_poses.p, ns, np, h->d_block_set.p, L.total_blocks, h->d_partial.p, s);
-    tm.stop(s);
-    launch_lm_reduce(h->d_partial.p, h->d_sets.p, ns, kLmSlot, h->d_setsum.p, s);
-    reduce_setsums(h, ns);
-    rec.t_lm_kernel_ms += tm.ms();
-    for (int i = 0; i < ns; ++i)
-      for (int k = 0; k < np; ++k) costs[k] += h->h_setsum.p[(size_t)kLmSlot * i + k];
-  }
   rec.multi_cost_passes++;
+  if (ns == 0) return;
+  h->h_poses.reserve((size_t)np * ns);
+  h->d_poses.reserve((size_t)kLmMaxPoses * ns);
+  for (int k = 0; k < np; ++k)
+    for (int i = 0; i < ns; ++i) {
+      LmPose& P = h->h_poses.p[(size_t)k * ns + i];
+      pack_pose(cand[k][L.sets[i]->impl_src], cand[k][L.sets[i]->impl_tgt], P.Rs, P.Rt, P.ts, P.tt);
+    }
+  E3D_HIP(hipMemcpyAsync(h->d_poses.p, h->h_poses.p, sizeof(LmPose) * (size_t)np * ns, hipMemcpyHostToDevice, s));
+  lm_run_pass(h, ns, rec, [&] { launch_lm_cost_multi(h->d_sets.p, h->d_poses.p, ns, np, h->d_block_set.p, L.total_blocks, h->d_partial.p, s); });
+  for (int i = 0; i < ns; ++i)
+    for (int k = 0; k < np; ++k) costs[k] += h->h_setsum.p[(size_t)kLmSlot * i + k];
 }
 
-static void lm_prepare(e3d_icp* h, LmSystem& L, std::vector<PairJob>& jobs, int M) {
+static void lm_prepare(e3d_icp* h, LmSystem& L, std::vector<PairJob>& jobs) {
   // group the non-empty pairs (global counts: every rank builds the same list, a rank without correspondences of a pair
   // contributes an empty set) by full-pass mode; assign LM blocks
   L.sets.clear();
-  L.mode_begin.assign(5, 0); L.mode_blocks.assign(5, 0); L.mode_block_base.assign(5, 0);
+  L.mode_blocks.assign(5, 0); L.mode_block_base.assign(5, 0);
   std::vector<std::vector<PairJob*>> by_mode(4);
   for (PairJob& j : jobs) {
     if (j.gcount == 0) continue;
@@ -1573,7 +1583,6 @@ static void lm_prepare(e3d_icp* h, LmSystem& L, std::vector<PairJob>& jobs, int 
   h->d_sets.reserve(std::max(ns_total, 1));
   std::vector<int> block_set;
   for (int m = 1; m <= 3; ++m) {
-    L.mode_begin[m] = (int)L.sets.size();
     L.mode_block_base[m] = block;
     for (PairJob* j : by_mode[m]) {
       const int i = (int)L.sets.size();
@@ -1581,12 +1590,10 @@ static void lm_prepare(e3d_icp* h, LmSystem& L, std::vector<PairJob>& jobs, int 
       if (j->resident) {
         // resident rows: the pass walks the listed 64-row groups; local halves get the outer pose of this iteration
         const PairState& ps = *j->resident;
-        const Cloud& src = (j->src == M) ? *h->fixed : *h->clouds[j->src];
-        const Cloud& tgt = (j->tgt == M) ? *h->fixed : *h->clouds[j->tgt];
         S.A = ps.pA.p; S.B = ps.pB.p; S.C = ps.pC.p; S.glist = ps.glist.p; S.n = j->vrows;
         if ((size_t)j->vrows == resident_rows_cap(ps.n)) S.glist = nullptr;      // every group is listed: rows [0, n) as they lie
         S.outer = (ps.src_global ? 0 : 1) | (ps.tgt_global ? 0 : 2);
-        S.Tos = to_affine(src.T); S.Tot = to_affine(tgt.T);
+        S.Tos = to_affine(cloud_at(h, j->src).T); S.Tot = to_affine(cloud_at(h, j->tgt).T);
       } else {
         S.A = h->cA.p + j->corr_off; S.B = h->cB.p + j->corr_off; S.C = h->cC.p + j->corr_off; S.glist = nullptr; S.n = j->count;
         S.outer = 0;
@@ -1614,38 +1621,36 @@ static void lm_prepare(e3d_icp* h, LmSystem& L, std::vector<PairJob>& jobs, int 
 
 // PointToPlaneICPImpl::compute  (icp_point_to_plane_impl.h:115-293)
 static void lm_compute(e3d_icp* h, LmSystem& L, std::vector<SE3f>& poses, e3d_icp_iter_record& rec) {
+  const IcpSwitches& sw = icp_switches();
   const int nv = L.nv;
   std::vector<double> H, b, Hn, bn;
-  double cost = 0, new_cost = 0;
-  double lambda = 0.1;
+  double cost = 0, new_cost = 0, lambda = 0.1;
   lm_evaluate(h, L, poses, true, H, b, cost, rec);
-  rec.initial_cost = cost;
-  rec.final_cost = cost;
+  rec.initial_cost = rec.final_cost = cost;
+  // The ten tries of an LM step: try 0 at the current lambda, tries 1..9 with lambda doubled after every rejection (impl.h:216-283).
+  // model_gain is what the quadratic model promises for the try: cost(-x) ~ cost - (2 b.x - x.H x) (H: the upper triangle, as the
+  // solver reads it)
   struct SolveScratch { std::vector<double> Hl, x, W; std::vector<int> perm; };
-  std::vector<SolveScratch> scratch(10);
-  // what the quadratic model promises for a try: cost(-x) ~ cost - (2 b.x - x.H x) (H: the upper triangle, as the solver reads it)
-  std::vector<double> model_gain(10, 0.0), step_norm(10, 0.0);
-  auto candidate = [&](double lam, std::vector<SE3f>& out, SolveScratch& sc, int k_try) {
+  struct Try { double lam = 0, cost = 0, model_gain = 0, step_norm = 0; std::vector<SE3f> poses; SolveScratch sc; };
+  std::vector<Try> tries(10);
+  auto candidate = [&](Try& t, SolveScratch& sc) {
     sc.Hl = H;
     sc.x.resize((size_t)std::max(nv, 1));
-    for (int i = 0; i < nv; ++i) sc.Hl[(size_t)i * nv + i] += lam;         // additive damping (impl.h:223)
+    for (int i = 0; i < nv; ++i) sc.Hl[(size_t)i * nv + i] += t.lam;         // additive damping (impl.h:223)
     if (nv > 0) ldlt_solve_upper(sc.Hl.data(), nv, b.data(), sc.x.data(), sc.W, sc.perm);
-    {
-      double bx = 0, xHx = 0, xx = 0;
-      for (int i = 0; i < nv; ++i) {
-        bx += b[i] * sc.x[i]; xx += sc.x[i] * sc.x[i];
-        xHx += H[(size_t)i * nv + i] * sc.x[i] * sc.x[i];
-        for (int j = i + 1; j < nv; ++j) xHx += 2.0 * H[(size_t)i * nv + j] * sc.x[i] * sc.x[j];
-      }
-      model_gain[k_try] = 2.0 * bx - xHx; step_norm[k_try] = std::sqrt(xx);
+    double bx = 0, xHx = 0, xx = 0;
+    for (int i = 0; i < nv; ++i) {
+      bx += b[i] * sc.x[i]; xx += sc.x[i] * sc.x[i];
+      xHx += H[(size_t)i * nv + i] * sc.x[i] * sc.x[i];
+      for (int j = i + 1; j < nv; ++j) xHx += 2.0 * H[(size_t)i * nv + j] * sc.x[i] * sc.x[j];
     }
-    out.resize(poses.size());
-    out[0] = poses[0];
-    for (size_t ci = 1; ci < poses.size(); ++ci) out[ci] = se3_apply_update(&sc.x[6 * (ci - 1)], poses[ci]);   // impl.h:235
+    t.model_gain = 2.0 * bx - xHx; t.step_norm = std::sqrt(xx);
+    t.poses.resize(poses.size());
+    t.poses[0] = poses[0];
+    for (size_t ci = 1; ci < poses.size(); ++ci) t.poses[ci] = se3_apply_update(&sc.x[6 * (ci - 1)], poses[ci]);   // impl.h:235
   };
-  // the tries' solves side by side on the handle's host threads when the system is large (E3D_LM_SOLVE_THREADS: 0 = on the caller's)
-  static const int solve_threads = [] { const char* e = getenv("E3D_LM_SOLVE_THREADS"); return e ? atoi(e) : 4; }();
-  if (nv >= 30 && solve_threads > 0 && !h->solve_pool) h->solve_pool.reset(new SolvePool(std::min(solve_threads, 9)));
+  // the tries' solves side by side on the handle's host threads when the system is large (IcpSwitches::solve_threads)
+  if (nv >= 30 && sw.solve_threads > 0 && !h->solve_pool) h->solve_pool.reset(new SolvePool(std::min(sw.solve_threads, 9)));
   // Candidate poses are compared as f32 bit patterns: a pass at a pose that was already evaluated returns the cost it returned
   // then, bit for bit (same rows, same per-correspondence f32 code, same reduction tree), so it need not run.  At the end of an
   // outer iteration the update x is so small that exp(-x).cast<float>() * pose rounds back to the pose for most of the ten
@@ -1655,32 +1660,29 @@ static void lm_compute(e3d_icp* h, LmSystem& L, std::vector<SE3f>& poses, e3d_ic
     return a.size() == b.size() && std::memcmp(a.data(), b.data(), a.size() * sizeof(SE3f)) == 0;
   };
   static_assert(sizeof(SE3f) == 7 * sizeof(float), "SE3f is compared as raw floats");
-  // All ten tries of an LM step as (lambda, poses): try 0 at the current lambda, tries 1..9 with lambda doubled after every
-  // rejection (impl.h:216-283).  The costs of the tries in [first, 10) whose poses are new and distinct come from one multi-pose pass
-  // (one new pose: the plain cost pass); a try whose poses equal the current ones costs `cost`.
-  std::vector<std::vector<SE3f>> cand(10);
-  std::vector<double> lam(10), costs(10);
-  // lam[first..9] from lam_first; the poses of tries [first, last); returns lambda after ten rejections
+  // lam of tries [first, 10) from lam_first; the poses of tries [first, last); returns lambda after ten rejections
   auto tries_from = [&](int first, int last, double lam_first) {
     LmTick tick(g_lm_prof.solve_ms); g_lm_prof.solves += last - first;
     double l = lam_first;
-    for (int k = first; k < 10; ++k) { lam[k] = l; l = 2.f * l; }
+    for (int k = first; k < 10; ++k) { tries[k].lam = l; l = 2.f * l; }
     if (h->solve_pool && nv >= 30 && last - first > 1) {
-      const std::function<void(int)> one = [&](int i) { candidate(lam[first + i], cand[first + i], scratch[first + i], first + i); };
+      const std::function<void(int)> one = [&](int i) { candidate(tries[first + i], tries[first + i].sc); };
       h->solve_pool->parallel_for(last - first, one);
     } else {
-      for (int k = first; k < last; ++k) candidate(lam[k], cand[k], scratch[0], k);
+      for (int k = first; k < last; ++k) candidate(tries[k], tries[0].sc);
     }
     return l;
   };
+  // The costs of the tries in [first, 10): those whose poses are new and distinct come from one multi-pose pass (one new pose: the
+  // plain cost pass); a try whose poses equal the current ones costs `cost`.
   auto evaluate_tries = [&](int first) {
     std::vector<std::vector<SE3f>> distinct;
     std::vector<int> slot(10, -1);                         // -1: the pose equals the current one (cost known)
     std::vector<double> dcosts;
     for (int k = first; k < 10; ++k) {
-      if (same_poses(cand[k], poses)) continue;
-      for (size_t q = 0; q < distinct.size() && slot[k] < 0; ++q) if (same_poses(cand[k], distinct[q])) slot[k] = (int)q;
-      if (slot[k] < 0) { slot[k] = (int)distinct.size(); distinct.push_back(cand[k]); }
+      if (same_poses(tries[k].poses, poses)) continue;
+      for (size_t q = 0; q < distinct.size() && slot[k] < 0; ++q) if (same_poses(tries[k].poses, distinct[q])) slot[k] = (int)q;
+      if (slot[k] < 0) { slot[k] = (int)distinct.size(); distinct.push_back(tries[k].poses); }
     }
     if (distinct.size() == 1) {            // one new pose: the plain cost pass (HBM bound; same bits)
       std::vector<double> Hx, bx;
@@ -1688,32 +1690,33 @@ static void lm_compute(e3d_icp* h, LmSystem& L, std::vector<SE3f>& poses, e3d_ic
       lm_evaluate(h, L, distinct[0], false, Hx, bx, dcosts[0], rec);
     } else if (!distinct.empty()) { lm_evaluate_costs(h, L, distinct, dcosts, rec); rec.multi_cost_poses += (int)distinct.size(); }
     else rec.lm_passes_skipped++;
-    for (int k = first; k < 10; ++k) costs[k] = (slot[k] < 0) ? cost : dcosts[slot[k]];
-    {
-      static const bool lm_trace = getenv("E3D_LM_TRACE") != nullptr;
-      if (lm_trace) {                                   // how many clouds keep their f32 pose in each try (diagnostics)
-        fprintf(stderr, "[lm trace] tries %d..9, clouds with an unchanged pose of %zu:", first, poses.size());
-        for (int k = first; k < 10; ++k) {
-          int same = 0;
-          for (size_t ci = 0; ci < poses.size(); ++ci) if (std::memcmp(&cand[k][ci], &poses[ci], sizeof(SE3f)) == 0) ++same;
-          fprintf(stderr, " %d", same);
-        }
-        fprintf(stderr, "\n");
+    for (int k = first; k < 10; ++k) tries[k].cost = (slot[k] < 0) ? cost : dcosts[slot[k]];
+    if (sw.lm_trace) {                                   // how many clouds keep their f32 pose in each try (diagnostics)
+      fprintf(stderr, "[lm trace] tries %d..9, clouds with an unchanged pose of %zu:", first, poses.size());
+      for (int k = first; k < 10; ++k) {
+        int same = 0;
+        for (size_t ci = 0; ci < poses.size(); ++ci) if (std::memcmp(&tries[k].poses[ci], &poses[ci], sizeof(SE3f)) == 0) ++same;
+        fprintf(stderr, " %d", same);
       }
+      fprintf(stderr, "\n");
     }
+  };
+  // try k is accepted at cost_k: H and b at its poses are in Hn, bn
+  auto accept = [&](int k, double cost_k) {
+    poses = tries[k].poses; H.swap(Hn); b.swap(bn); cost = cost_k;
+    lambda = tries[k].lam;                                 // (try 0: the current lambda)
+    lambda = 0.5f * lambda;
   };
   // Try 0 is usually accepted, so its cost is evaluated together with the next step's H and b (one fused pass) -- except in the LM
   // step an alignment that has settled ends with: there all ten tries are rejected, and the fused pass's H and b are thrown away.
   // The step at which the previous outer iteration's LM ended is the prediction: from that step on, try 0 joins tries 1..9 in the
   // multi-pose cost pass (ten poses), and only an accepted try pays a fused pass at its pose.  Same costs bit for bit, same
   // sequential decisions; a wrong prediction costs one cost-only evaluation of try 0.  (E3D_LM_SPECULATE=0: always the fused pass.)
-  static const bool speculate = [] { const char* e = getenv("E3D_LM_SPECULATE"); return !(e && e[0] == '0'); }();
   // (Speculating one step LATER -- E3D_LM_SPEC_OFFSET=1 -- was measured too: once the model's gain is below the f32 noise of the
   // cost, relative 1e-7 and less (E3D_LM_TRACE prints both), a step is accepted or not like a coin is tossed and the LM ends at the
   // previous iteration's step in half of the cases; but the ten tries of such a step round to three to seven distinct poses, the
   // multi-pose pass is cheaper than a fused pass + nine poses, and speculating at the same step stays ahead: settling iterations of
   // the headline scene 99.7 -> 103.9 ms with the offset, 102.7 without speculation.)
-  static const int spec_offset = [] { const char* e = getenv("E3D_LM_SPEC_OFFSET"); return e ? atoi(e) : 0; }();
   const int predicted_end = h->lm_prev_end_step;
   h->lm_prev_end_step = -1;
   for (int it = 0; it < h->max_inner; ++it) {
@@ -1721,270 +1724,235 @@ static void lm_compute(e3d_icp* h, LmSystem& L, std::vector<SE3f>& poses, e3d_ic
     bool applied = false;
     const double trace_cost_before = cost;
     double trace_try0_cost = 0.0;
-    const bool batch_all = speculate && predicted_end >= 0 && it >= predicted_end + spec_offset;
+    const bool batch_all = sw.speculate && predicted_end >= 0 && it >= predicted_end + sw.spec_offset;
     int hit = -1;
     double lam_end = lambda;
     if (batch_all) {
       lam_end = tries_from(0, 10, lambda);
       evaluate_tries(0);
-      trace_try0_cost = costs[0];
-      for (int k = 0; k < 10; ++k) if (costs[k] < cost) { hit = k; break; }
+      trace_try0_cost = tries[0].cost;
+      for (int k = 0; k < 10; ++k) if (tries[k].cost < cost) { hit = k; break; }
     } else {
       lam_end = tries_from(0, 1, lambda);                  // only try 0 is needed yet: the other nine are solved if it is rejected
-      if (same_poses(cand[0], poses)) { new_cost = cost; rec.lm_passes_skipped++; }
-      else lm_evaluate(h, L, cand[0], true, Hn, bn, new_cost, rec);
+      if (same_poses(tries[0].poses, poses)) { new_cost = cost; rec.lm_passes_skipped++; }
+      else lm_evaluate(h, L, tries[0].poses, true, Hn, bn, new_cost, rec);
       trace_try0_cost = new_cost;
       if (new_cost < cost) {
-        poses = cand[0]; H.swap(Hn); b.swap(bn); cost = new_cost;
-        lambda = 0.5f * lambda;
+        accept(0, new_cost);
         applied = true;
       } else {
-        tries_from(1, 10, lam[1]);
+        tries_from(1, 10, tries[1].lam);
         evaluate_tries(1);
-        for (int k = 1; k < 10; ++k) if (costs[k] < cost) { hit = k; break; }
+        for (int k = 1; k < 10; ++k) if (tries[k].cost < cost) { hit = k; break; }
       }
     }
     if (!applied) {
       if (hit >= 0) {
         double c2;
-        lm_evaluate(h, L, cand[hit], true, Hn, bn, c2, rec);   // H, b at the accepted pose; c2 == costs[hit] bit for bit
-        poses = cand[hit]; H.swap(Hn); b.swap(bn); cost = c2;
-        lambda = 0.5f * lam[hit];
+        lm_evaluate(h, L, tries[hit].poses, true, Hn, bn, c2, rec);   // H, b at the accepted pose; c2 == tries[hit].cost bit for bit
+        accept(hit, c2);
         applied = true;
       } else {
         lambda = lam_end;   // ten rejections: lambda doubled ten times
       }
     }
     rec.final_cost = cost;
-    {
-      static const bool lm_trace = getenv("E3D_LM_TRACE") != nullptr;
-      if (lm_trace) fprintf(stderr, "[lm trace] inner %d batch_all %d hit %d applied %d predicted_end %d try0: model gain %.6e (of cost %.9e) step %.3e lambda %.3e cost after %.12e\n", it, (int)batch_all, hit, (int)applied, predicted_end, model_gain[0], trace_cost_before, step_norm[0], lam[0], trace_try0_cost);
-    }
+    if (sw.lm_trace) fprintf(stderr, "[lm trace] inner %d batch_all %d hit %d applied %d predicted_end %d try0: model gain %.6e (of cost %.9e) step %.3e lambda %.3e cost after %.12e\n", it, (int)batch_all, hit, (int)applied, predicted_end, tries[0].model_gain, trace_cost_before, tries[0].step_norm, tries[0].lam, trace_try0_cost);
     if (!applied) { h->lm_prev_end_step = it; break; }
   }
 }
 
-// PointToPlaneICP::AlignMeshes  (icp_point_to_plane.cc:169-342)
-static bool align_meshes(e3d_icp* h, float max_d, float thr, bool print, int iteration) {
-  e3d_icp_iter_record rec{};
-  rec.iteration = iteration;
-  hipStream_t s = h->stream;
-  EventTimer t_tr, t_nn, t_lm;
-  const int M = (int)h->clouds.size();
-  const bool has_fixed = (bool)h->fixed;
-  int n_impl = 0, fixed_vertex = -1;
+// ---- the phases of an outer iteration (align_meshes), in the order they run ----------------------------------------------------------
 
-  t_tr.start(s);
-  if (has_fixed) {
-    Cloud& f = *h->fixed;
-    fixed_vertex = n_impl++;
-    f.cloud_index = fixed_vertex;
-    if (!grid_usable(f, max_d)) build_grid(h, f, max_d);
-    // fixed cloud lives in the global frame: G4 = L4 (identity transform is exact), bbox recomputed
-    transform_cloud(h, f);
-  }
-  for (int i = 0; i < M; ++i) {
-    Cloud& c = *h->clouds[i];
+// Every cloud gets its grid (if the one it has is not usable), its global coordinates and its vertex of the LM system: the fixed cloud
+// first (it lives in the global frame: G4 = L4, the identity transform is exact).  Returns the number of vertices.
+static int index_clouds(e3d_icp* h, float max_d, int& fixed_vertex) {
+  int n_impl = 0;
+  auto index = [&](Cloud& c) {
     if (!grid_usable(c, max_d)) build_grid(h, c, max_d);
     transform_cloud(h, c);
     c.cloud_index = n_impl++;
-  }
-  t_tr.stop(s);
+  };
+  if (h->fixed) index(*h->fixed);
+  fixed_vertex = h->fixed ? h->fixed->cloud_index : -1;
+  for (auto& c : h->clouds) index(*c);
+  return n_impl;
+}
 
-  // pair list in the sequential order of the reference's ik loop (cc:208-309)
+// pair list in the sequential order of the reference's ik loop (cc:208-309)
+static std::vector<PairJob> list_pairs(e3d_icp* h, int fixed_vertex) {
+  const int M = (int)h->clouds.size();
   std::vector<PairJob> jobs;
   for (int ik = 0; ik < M * M; ++ik) {
     const int i = ik / M, k = ik % M;
     if (i != k && bbox_intersects(*h->clouds[i], *h->clouds[k]))
       jobs.push_back({i, k, h->clouds[i]->cloud_index, h->clouds[k]->cloud_index});
-    if (i == k && has_fixed && bbox_intersects(*h->fixed, *h->clouds[i])) {
+    if (i == k && h->fixed && bbox_intersects(*h->fixed, *h->clouds[i])) {
       jobs.push_back({i, M, h->clouds[i]->cloud_index, fixed_vertex});
       jobs.push_back({M, i, fixed_vertex, h->clouds[i]->cloud_index});
     }
   }
-  t_nn.start(s);
-  h->corr_used = 0;
-  {
-    // correspondences <= queries: size the planes once (no hipMalloc/hipFree inside the iteration loop)
-    // Pairs of the certificate path keep RESIDENT rows (one row per query, 48 B + 4 B, for as long as the grids live) when all of
-    // them fit beside what is already allocated; otherwise every pair goes through the compacted planes as before.
-    size_t qtot = 0, rows_new = 0;
-    auto slice_len = [&](const Cloud& src) {
-      return (size_t)((unsigned __int128)src.n * (unsigned)(h->rank + 1) / (unsigned)h->world) -
-             (size_t)((unsigned __int128)src.n * (unsigned)h->rank / (unsigned)h->world);
-    };
-    bool resident = h->resident_rows;
-    for (const PairJob& j : jobs) {
-      const Cloud& src = (j.src == M) ? *h->fixed : *h->clouds[j.src];
-      const Cloud& tgt = (j.tgt == M) ? *h->fixed : *h->clouds[j.tgt];
-      const size_t nq = slice_len(src);
-      if (!pair_uses_rows(h, tgt) || nq == 0 || tgt.n == 0) continue;
-      auto it = h->pair_state.find(std::make_pair(j.src, j.tgt));
-      if (it == h->pair_state.end() || it->second->pA.cap < resident_rows_cap(nq)) rows_new += resident_bytes(nq);
-    }
-    // rows of pairs that have left the job list (their bounding boxes no longer intersect) go back first
-    for (auto& kv : h->pair_state) {
-      bool listed = false;
-      for (const PairJob& j : jobs) if (j.src == kv.first.first && j.tgt == kv.first.second) { listed = true; break; }
-      if (!listed) { PairState& ps = *kv.second; ps.pA.release(); ps.pB.release(); ps.pC.release(); ps.rows_valid = false; }
-    }
-    auto release_rows = [&]() {
-      for (auto& kv : h->pair_state) { PairState& ps = *kv.second; ps.pA.release(); ps.pB.release(); ps.pC.release(); ps.rows_valid = false; }
-    };
-    if (resident && rows_new > 0) {
-      // beside the rows: the batch scratch (12 B per query of a batch, at most 64 M queries) and what the search allocates on
-      // first use (sort buffers, block counts: ~40 B per query of the largest pair)
-      size_t free_b = 0, total_b = 0, q_max = 0;
-      (void)hipMemGetInfo(&free_b, &total_b);
-      for (const PairJob& j : jobs) q_max = std::max(q_max, slice_len((j.src == M) ? *h->fixed : *h->clouds[j.src]));
-      const double extra = 12.0 * (double)std::min<size_t>(q_max * kPairBatch, kBatchQueries) + 40.0 * (double)q_max;
-      if ((double)rows_new + extra > 0.8 * (double)free_b) resident = false;
-    }
-    if (resident) {
-      // The rows are allocated HERE, all of them, so that running out of memory is noticed before any pair has been searched: on
-      // failure every pair takes the compacted planes this iteration (the old data flow), exactly as when the estimate says no.
-      try {
-        for (const PairJob& j : jobs) {
-          const Cloud& src = (j.src == M) ? *h->fixed : *h->clouds[j.src];
-          const Cloud& tgt = (j.tgt == M) ? *h->fixed : *h->clouds[j.tgt];
-          const size_t nq = slice_len(src);
-          if (!pair_uses_rows(h, tgt) || nq == 0 || tgt.n == 0) continue;
-          const size_t j0 = (size_t)((unsigned __int128)src.n * (unsigned)h->rank / (unsigned)h->world);
-          PairState& ps = pair_state_for(h, j.src, j.tgt, src, tgt, j0, nq);
-          const size_t cap = resident_rows_cap(nq);
-          if (ps.pA.cap < cap || ps.pB.cap < cap || ps.pC.cap < cap) {
-            ps.rows_valid = false;
-            ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap);
-          }
-          ps.plane_match.reserve(nq); ps.glist.reserve(div_up(nq, 64));
-        }
-      } catch (const Error&) {
-        (void)hipGetLastError();
-        release_rows();
-        resident = false;
-      }
-    }
-    if (!resident) release_rows();
-    h->resident_now = resident;
-    for (const PairJob& j : jobs) {
-      const Cloud& src = (j.src == M) ? *h->fixed : *h->clouds[j.src];
-      const Cloud& tgt = (j.tgt == M) ? *h->fixed : *h->clouds[j.tgt];
-      if (resident && pair_uses_rows(h, tgt)) continue;           // no compacted rows for this pair
-      qtot += slice_len(src);
-    }
-    // two directed pairs: one slot per query (no reallocation ever); many pairs: most queries of a pair find no partner, so
-    // start from last iteration's total (+ 12 %) or a quarter of the queries and let find_pair grow the planes if needed
-    size_t want = qtot;
-    if (jobs.size() > 2 && qtot > h->cA.cap) {
-      // one slot per query as well if HBM has room for it (growing 100 GB planes means hipMalloc + copy + hipFree of that size:
-      // seconds per outer iteration while the correspondence count still climbs); otherwise start small and grow
-      size_t free_b = 0, total_b = 0;
-      (void)hipMemGetInfo(&free_b, &total_b);
-      const double need = 48.0 * (double)(qtot - h->cA.cap);
-      if (need > 0.75 * (double)free_b)
-        want = std::min(qtot, std::max(h->last_corr_total + h->last_corr_total / 8 + (size_t)(1 << 20), qtot / 4));
-    }
-    if (want > h->cA.cap) { h->cA.reserve(want); h->cB.reserve(want); h->cC.reserve(want); }
+  return jobs;
+}
+
+// Where this outer iteration's correspondences live (h->resident_now).  Pairs of the certificate path keep RESIDENT rows (one row per
+// query, 48 B + 4 B, for as long as the grids live) when all of them fit beside what is already allocated; otherwise every pair goes
+// through the compacted planes cA / cB / cC, sized here (correspondences <= queries: no hipMalloc / hipFree inside the batch loop).
+static void plan_rows(e3d_icp* h, const std::vector<PairJob>& jobs) {
+  auto wants_rows = [&](const PairJob& j, size_t nq) { const Cloud& tgt = cloud_at(h, j.tgt); return pair_uses_rows(h, tgt) && nq != 0 && tgt.n != 0; };
+  auto release_all = [&] { for (auto& kv : h->pair_state) release_rows(*kv.second); };
+  bool resident = h->resident_rows;
+  size_t rows_new = 0, q_max = 0;
+  for (const PairJob& j : jobs) {
+    const size_t nq = slice_of(h, cloud_at(h, j.src)).n;
+    q_max = std::max(q_max, nq);
+    if (!wants_rows(j, nq)) continue;
+    auto it = h->pair_state.find(std::make_pair(j.src, j.tgt));
+    if (it == h->pair_state.end() || it->second->pA.cap < resident_rows_cap(nq)) rows_new += resident_bytes(nq);
   }
-  {
-    // Pairs of the certificate search with resident rows run in batches of up to kPairBatch (two host round trips per batch);
-    // every other pair (sparse targets, forced kernel modes, compacted rows, the sequential distance sum) one by one.
-    std::vector<BatchItem> batch;
-    size_t batch_queries = 0;                               // (kBatchQueries bounds a batch's scratch)
-    // E3D_ICP_BATCH: 2 (default) one launch per kernel and batch (find_pairs_multi), 1 one launch per kernel and pair with the host
-    // round trips batched (find_pairs_batched), 0 pair by pair (find_pair)
-    // (a value that starts with '0' switches batching off, whatever follows)
-    static const char* const batch_env = getenv("E3D_ICP_BATCH");
-    static const bool batching = !(batch_env && batch_env[0] == '0');
-    static const int batch_mode = batch_env ? atoi(batch_env) : 2;
-    auto flush = [&]() {
-      if (batch.empty()) return;
-      if (!(batch_mode >= 2 && find_pairs_multi(h, batch, max_d, rec))) find_pairs_batched(h, batch, max_d, rec);
-      batch.clear(); batch_queries = 0;
-    };
-    for (size_t p = 0; p < jobs.size(); ++p) {
-      PairJob& j = jobs[p];
-      Cloud& src = (j.src == M) ? *h->fixed : *h->clouds[j.src];
-      Cloud& tgt = (j.tgt == M) ? *h->fixed : *h->clouds[j.tgt];
-      // this rank's slice of the source cloud (cell order); world == 1 => the whole cloud
-      const size_t j0 = (size_t)((unsigned __int128)src.n * (unsigned)h->rank / (unsigned)h->world);
-      const size_t j1 = (size_t)((unsigned __int128)src.n * (unsigned)(h->rank + 1) / (unsigned)h->world);
-      const bool whole = !h->comm && h->world <= 1 && (j1 - j0) == src.n;
-      if (batching && !nn_profile() && h->resident_now && pair_uses_rows(h, tgt) && j1 > j0 && tgt.n > 0 && !(h->sequential_dsum && whole)) {
-        j.count = 0; j.dsum = 0.0; j.corr_off = h->corr_used;
-        BatchItem it{};
-        it.job = &j; it.src = &src; it.tgt = &tgt; it.j0 = j0; it.n = j1 - j0;
-        it.ps = &pair_state_for(h, j.src, j.tgt, src, tgt, j0, j1 - j0);
-        if (batch_queries + it.n > kBatchQueries) flush();
-        batch.push_back(it);
-        batch_queries += it.n;
-        if (batch.size() == kPairBatch) flush();
-        continue;
+  // rows of pairs that have left the job list (their bounding boxes no longer intersect) go back first
+  for (auto& kv : h->pair_state) {
+    bool listed = false;
+    for (const PairJob& j : jobs) if (j.src == kv.first.first && j.tgt == kv.first.second) { listed = true; break; }
+    if (!listed) release_rows(*kv.second);
+  }
+  if (resident && rows_new > 0) {
+    // beside the rows: the batch scratch (12 B per query of a batch, at most 64 M queries) and what the search allocates on
+    // first use (sort buffers, block counts: ~40 B per query of the largest pair)
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const double extra = 12.0 * (double)std::min<size_t>(q_max * kPairBatch, kBatchQueries) + 40.0 * (double)q_max;
+    if ((double)rows_new + extra > 0.8 * (double)free_b) resident = false;
+  }
+  if (resident) {
+    // The rows are allocated HERE, all of them, so that running out of memory is noticed before any pair has been searched: on
+    // failure every pair takes the compacted planes this iteration (the old data flow), exactly as when the estimate says no.
+    try {
+      for (const PairJob& j : jobs) {
+        const Cloud& src = cloud_at(h, j.src);
+        const Slice sl = slice_of(h, src);
+        if (!wants_rows(j, sl.n)) continue;
+        PairState& ps = pair_state_for(h, j.src, j.tgt, src, cloud_at(h, j.tgt), sl.j0, sl.n);
+        const size_t cap = resident_rows_cap(sl.n);
+        if (ps.pA.cap < cap || ps.pB.cap < cap || ps.pC.cap < cap) {
+          ps.rows_valid = false;
+          ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap);
+        }
+        ps.plane_match.reserve(sl.n); ps.glist.reserve(div_up(sl.n, 64));
       }
-      flush();                                              // (keeps the pairs' order on the stream)
-      find_pair(h, src, tgt, max_d, j, j0, j1, rec);
-      rec.queries += (long long)(j1 - j0);
-      rec.correspondences += j.count;
+    } catch (const Error&) {
+      (void)hipGetLastError();
+      release_all();
+      resident = false;
+    }
+  }
+  if (!resident) release_all();
+  h->resident_now = resident;
+  size_t qtot = 0;                                             // queries of the pairs without resident rows
+  for (const PairJob& j : jobs)
+    if (!(resident && pair_uses_rows(h, cloud_at(h, j.tgt)))) qtot += slice_of(h, cloud_at(h, j.src)).n;
+  // two directed pairs: one slot per query (no reallocation ever); many pairs: most queries of a pair find no partner, so
+  // start from last iteration's total (+ 12 %) or a quarter of the queries and let find_pair grow the planes if needed
+  size_t want = qtot;
+  if (jobs.size() > 2 && qtot > h->cA.cap) {
+    // one slot per query as well if HBM has room for it (growing 100 GB planes means hipMalloc + copy + hipFree of that size:
+    // seconds per outer iteration while the correspondence count still climbs); otherwise start small and grow
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    const double need = 48.0 * (double)(qtot - h->cA.cap);
+    if (need > 0.75 * (double)free_b)
+      want = std::min(qtot, std::max(h->last_corr_total + h->last_corr_total / 8 + (size_t)(1 << 20), qtot / 4));
+  }
+  if (want > h->cA.cap) { h->cA.reserve(want); h->cB.reserve(want); h->cC.reserve(want); }
+}
+
+// The searches.  Pairs of the certificate search with resident rows run in batches of up to kPairBatch (two host round trips per
+// batch); every other pair (sparse targets, forced kernel modes, compacted rows, the sequential distance sum, E3D_NN_PROFILE) one by
+// one, behind a flush that keeps the pairs' order on the stream.
+static void search_pairs(e3d_icp* h, std::vector<PairJob>& jobs, float max_d, e3d_icp_iter_record& rec) {
+  const IcpSwitches& sw = icp_switches();
+  std::vector<BatchItem> batch;
+  size_t batch_queries = 0;                               // (kBatchQueries bounds a batch's scratch)
+  auto flush = [&]() {
+    if (batch.empty()) return;
+    if (!(sw.batch_mode >= 2 && find_pairs_multi(h, batch, max_d, rec))) find_pairs_batched(h, batch, max_d, rec);
+    batch.clear(); batch_queries = 0;
+  };
+  for (PairJob& j : jobs) {
+    Cloud& src = cloud_at(h, j.src); Cloud& tgt = cloud_at(h, j.tgt);
+    const Slice sl = slice_of(h, src);
+    const bool whole = !h->comm && h->world <= 1 && sl.n == src.n;
+    j.count = 0; j.dsum = 0.0; j.corr_off = h->corr_used;
+    BatchItem it{};
+    it.job = &j; it.src = &src; it.tgt = &tgt; it.j0 = sl.j0; it.n = sl.n;
+    if (sw.batching && !sw.nn_profile && h->resident_now && pair_uses_rows(h, tgt) && sl.n > 0 && tgt.n > 0 && !(h->sequential_dsum && whole)) {
+      it.ps = &pair_state_for(h, j.src, j.tgt, src, tgt, sl.j0, sl.n);
+      if (batch_queries + it.n > kBatchQueries) flush();
+      batch.push_back(it);
+      batch_queries += it.n;
+      if (batch.size() == kPairBatch) flush();
+      continue;
     }
     flush();
+    find_pair(h, it, max_d, rec);
+    rec.queries += (long long)sl.n;
+    rec.correspondences += j.count;
   }
-  t_nn.stop(s);
-  if (nn_profile()) {
-    fprintf(stderr, "[nn profile] certify + bounded search %.1f ms, keys + sort %.1f ms, match scan + compaction (+ plane growth) %.1f ms, %zu pairs\n",
-            g_nn_prof[0], g_nn_prof[1], g_nn_prof[2], jobs.size());
-    for (double& v : g_nn_prof) v = 0;
-  }
+  flush();
   h->last_corr_total = h->corr_used;
-  // global per-pair counts (what the reference prints); local counts stay in j.count for the LM sets
-  std::vector<long long> gcount(jobs.size());
-  std::vector<double> gdsum(jobs.size());
-  for (size_t p = 0; p < jobs.size(); ++p) { gcount[p] = jobs[p].count; gdsum[p] = jobs[p].dsum; }
-  if (sharded(h) && !jobs.empty()) {
-    std::vector<double> buf(2 * jobs.size(), 0.0);
-    for (size_t p = 0; p < jobs.size(); ++p) { buf[2 * p] = (double)jobs[p].count; buf[2 * p + 1] = jobs[p].dsum; }
-    reduce_host(h, buf.data(), buf.size());
-    for (size_t p = 0; p < jobs.size(); ++p) { gcount[p] = (long long)buf[2 * p]; gdsum[p] = buf[2 * p + 1]; }
-  }
-  for (size_t p = 0; p < jobs.size(); ++p) jobs[p].gcount = gcount[p];
+}
+
+// The pairs' counts over all ranks (what the reference prints, and what decides which pairs enter the LM system; the local counts
+// stay in j.count for the LM sets), the pair records and the progress lines.
+static void publish_pair_counts(e3d_icp* h, std::vector<PairJob>& jobs, int fixed_vertex, int iteration, bool print) {
+  std::vector<double> buf(2 * jobs.size(), 0.0);           // (count, distance sum) per pair: counts are exact in f64
+  for (size_t p = 0; p < jobs.size(); ++p) { buf[2 * p] = (double)jobs[p].count; buf[2 * p + 1] = jobs[p].dsum; }
+  reduce_host(h, buf.data(), buf.size());                  // (nothing to do on a handle that is not sharded)
   for (size_t p = 0; p < jobs.size(); ++p) {
-    const PairJob& j = jobs[p];
+    PairJob& j = jobs[p];
+    const long long gcount = j.gcount = (long long)buf[2 * p];
+    const double gdsum = buf[2 * p + 1];
     const int psrc = (j.impl_src == fixed_vertex) ? -1 : j.impl_src;
     const int ptgt = (j.impl_tgt == fixed_vertex) ? -1 : j.impl_tgt;
-    h->pair_records.push_back({iteration, psrc, ptgt, (int64_t)gcount[p], gdsum[p]});
-    if (print && h->rank == 0) {
-      char avg[64] = "";
-      if (gcount[p] > 0) {
-        const float a = jobs[p].dsum_f32 ? (float)gdsum[p] / (float)(size_t)gcount[p]        // float / size_t, as the reference divides
-                                         : (float)(gdsum[p] / (double)gcount[p]);
-        snprintf(avg, sizeof avg, " (avg. distance: %g)", (double)a);
-      }
-      if (psrc >= 0 && ptgt >= 0) printf("  found correspondences from %d to %d: %lld%s\n", j.impl_src, j.impl_tgt, gcount[p], avg);
-      else if (ptgt < 0) printf("  found correspondences from %d to fixed clouds: %lld%s\n", j.impl_src, gcount[p], avg);
-      else printf("  found correspondences from fixed clouds to %d: %lld%s\n", j.impl_tgt, gcount[p], avg);
+    h->pair_records.push_back({iteration, psrc, ptgt, (int64_t)gcount, gdsum});
+    if (!(print && h->rank == 0)) continue;
+    char avg[64] = "";
+    if (gcount > 0) {
+      const float a = j.dsum_f32 ? (float)gdsum / (float)(size_t)gcount        // float / size_t, as the reference divides
+                                 : (float)(gdsum / (double)gcount);
+      snprintf(avg, sizeof avg, " (avg. distance: %g)", (double)a);
     }
+    if (psrc >= 0 && ptgt >= 0) printf("  found correspondences from %d to %d: %lld%s\n", j.impl_src, j.impl_tgt, gcount, avg);
+    else if (ptgt < 0) printf("  found correspondences from %d to fixed clouds: %lld%s\n", j.impl_src, gcount, avg);
+    else printf("  found correspondences from fixed clouds to %d: %lld%s\n", j.impl_tgt, gcount, avg);
   }
+}
 
-  // impl.setMaxIterations(150); impl.compute()  (cc:312-316)
-  t_lm.start(s);
+// impl.setMaxIterations(150); impl.compute()  (cc:312-316): the inner poses of the n_impl vertices
+static std::vector<SE3f> solve_poses(e3d_icp* h, std::vector<PairJob>& jobs, int n_impl, e3d_icp_iter_record& rec) {
   std::vector<SE3f> poses((size_t)n_impl);
   LmSystem L;
-  L.n_impl = n_impl;
   L.nv = 6 * (n_impl - 1);
-  { LmTick tick(g_lm_prof.prepare_ms); lm_prepare(h, L, jobs, M); }
+  { LmTick tick(g_lm_prof.prepare_ms); lm_prepare(h, L, jobs); }
   if (n_impl >= 1) lm_compute(h, L, poses, rec);
-  t_lm.stop(s);
-  if (lm_profile()) {
-    fprintf(stderr, "[lm profile] it %d: prepare %.2f ms, %d solves %.2f ms, %d evaluations %.2f ms (of which waiting for the sums + reduction %.2f ms: longest wait %.2f ms; "
-            "all-reduce callback %.2f ms, longest %.2f ms)\n", iteration, g_lm_prof.prepare_ms, g_lm_prof.solves, g_lm_prof.solve_ms, g_lm_prof.evals, g_lm_prof.eval_ms,
-            g_lm_prof.reduce_ms, g_lm_prof.wait_max, g_lm_prof.callback_ms, g_lm_prof.callback_max);
-    g_lm_prof = LmProf{};
-  }
+  return poses;
+}
+static void print_lm_profile(int iteration) {
+  if (!icp_switches().lm_profile) return;
+  fprintf(stderr, "[lm profile] it %d: prepare %.2f ms, %d solves %.2f ms, %d evaluations %.2f ms (of which waiting for the sums + reduction %.2f ms: longest wait %.2f ms; "
+          "all-reduce callback %.2f ms, longest %.2f ms)\n", iteration, g_lm_prof.prepare_ms, g_lm_prof.solves, g_lm_prof.solve_ms, g_lm_prof.evals, g_lm_prof.eval_ms,
+          g_lm_prof.reduce_ms, g_lm_prof.wait_max, g_lm_prof.callback_ms, g_lm_prof.callback_max);
+  g_lm_prof = LmProf{};
+}
 
-  // pose write-back (cc:318-341): new = Affine3f(pose.matrix()) * global_T_cloud
+// pose write-back (cc:318-341): new = Affine3f(pose.matrix()) * global_T_cloud, composed in f32; the clouds' and the pairs' motion
+// certificates of the NN search follow the poses.  Returns whether no cloud moved by more than thr.
+static bool write_back_poses(e3d_icp* h, const std::vector<SE3f>& poses, float thr, bool print) {
+  const int M = (int)h->clouds.size();
   bool converged = true;
   std::vector<float> T_before((size_t)12 * (size_t)(M + 1));
   for (int i = 0; i < M; ++i) std::memcpy(&T_before[12 * (size_t)i], h->clouds[i]->T, sizeof(float) * 12);
-  if (has_fixed) std::memcpy(&T_before[12 * (size_t)M], h->fixed->T, sizeof(float) * 12);
+  if (h->fixed) std::memcpy(&T_before[12 * (size_t)M], h->fixed->T, sizeof(float) * 12);
   for (int i = 0; i < M; ++i) {
     Cloud& c = *h->clouds[i];
     const SE3f& p = poses[c.cloud_index];
@@ -2009,14 +1977,18 @@ static bool align_meshes(e3d_icp* h, float max_d, float thr, bool print, int ite
   // the pairs' own motion accumulators (every pair that keeps a state, whether it was searched in this iteration or not)
   for (auto& kv : h->pair_state) {
     const int si = kv.first.first, ti = kv.first.second;
-    if (si < 0 || ti < 0 || si > M || ti > M || (si == M && !has_fixed) || (ti == M && !has_fixed)) continue;
-    const Cloud& src = (si == M) ? *h->fixed : *h->clouds[si];
-    const Cloud& tgt = (ti == M) ? *h->fixed : *h->clouds[ti];
+    if (si < 0 || ti < 0 || si > M || ti > M || (si == M && !h->fixed) || (ti == M && !h->fixed)) continue;
+    const Cloud& src = cloud_at(h, si); const Cloud& tgt = cloud_at(h, ti);
     const double glob = ((si == M) ? 0.0 : src.last_motion) + ((ti == M) ? 0.0 : tgt.last_motion);
     if (!accumulate_pair_motion(*kv.second, src, tgt, &T_before[12 * (size_t)si], src.T, &T_before[12 * (size_t)ti], tgt.T, glob)) ++h->nn_global_bound_updates;
   }
-  if (nn_switches().want_stats && h->nn_global_bound_updates)
+  if (icp_switches().want_stats && h->nn_global_bound_updates)
     fprintf(stderr, "[nn] %lld pose updates of a pair went into the clouds' global motion bound (a pose that is not near-rigid)\n", h->nn_global_bound_updates);
+  return converged;
+}
+
+// the record's timers: the three phases' stop-watches and what the NN kernels' lazy ones collected
+static void close_timers(e3d_icp* h, EventTimer& t_tr, EventTimer& t_nn, EventTimer& t_lm, e3d_icp_iter_record& rec) {
   rec.t_transform_ms = t_tr.ms();
   rec.t_nn_ms = t_nn.ms();
   rec.t_nn_sort_ms = h->tm_sort.take(); rec.t_nn_scan_ms = h->tm_scan.take(); rec.t_nn_compact_ms = h->tm_compact.take();
@@ -2024,6 +1996,36 @@ static bool align_meshes(e3d_icp* h, float max_d, float thr, bool print, int ite
   { const double tc = h->tm_certify.take(); rec.t_nn_certify_ms += tc; rec.t_nn_query_ms += tc; }
   { const double ts = h->tm_search.take(); rec.t_nn_search_ms += ts; rec.t_nn_query_ms += ts; }
   rec.t_lm_ms = t_lm.ms();
+}
+
+// PointToPlaneICP::AlignMeshes  (icp_point_to_plane.cc:169-342)
+static bool align_meshes(e3d_icp* h, float max_d, float thr, bool print, int iteration) {
+  e3d_icp_iter_record rec{};
+  rec.iteration = iteration;
+  hipStream_t s = h->stream;
+  EventTimer t_tr, t_nn, t_lm;
+  int fixed_vertex = -1;
+
+  t_tr.start(s);
+  const int n_impl = index_clouds(h, max_d, fixed_vertex);
+  t_tr.stop(s);
+
+  std::vector<PairJob> jobs = list_pairs(h, fixed_vertex);
+  t_nn.start(s);
+  h->corr_used = 0;
+  plan_rows(h, jobs);                        // (sets h->resident_now: before the first search)
+  search_pairs(h, jobs, max_d, rec);
+  t_nn.stop(s);
+  print_nn_profile(jobs.size());
+  publish_pair_counts(h, jobs, fixed_vertex, iteration, print);
+
+  t_lm.start(s);
+  const std::vector<SE3f> poses = solve_poses(h, jobs, n_impl, rec);
+  t_lm.stop(s);
+  print_lm_profile(iteration);
+
+  const bool converged = write_back_poses(h, poses, thr, print);
+  close_timers(h, t_tr, t_nn, t_lm, rec);
   h->iter_records.push_back(rec);
   return converged;
 }
@@ -2198,11 +2200,11 @@ int64_t e3d_find_correspondences(const float* sxyz, size_t ns, const float* txyz
   if (ns > 0) {
     if (nt > 0) {
       h->match_pos.reserve(ns); h->match_d2.reserve(ns);
-      const int mode = g_nn_mode;
-      const bool dense = mode >= 2 || (mode == 0 && (double)tgt.n >= 4.0 * (double)std::max(tgt.n_cells, 1u));
+      const int mode = h->nn_mode;
+      const bool dense = pair_is_dense(h.get(), tgt);
       const unsigned* order = nullptr;
       if (dense) {
-        h->keys_a.reserve(ns); h->keys_b.reserve(ns); h->vals_a.reserve(ns); h->vals_b.reserve(ns);
+        reserve_sort_buffers(h.get(), ns);
         const InvMap im = make_invmap(tgt);
         launch_query_keys(src.G4.p, ns, tgt.grid, im, tgt.qrange, h->keys_a.p, h->vals_a.p, s);
         sort_pairs_u64_u32(h->keys_a.p, h->keys_b.p, h->vals_a.p, h->vals_b.p, ns, tgt.key_bits, h->sort_temp, s);
@@ -2306,12 +2308,9 @@ int e3d_icp_pair_system(const float* sxyz, const float* snrm, const float* txyz,
   sync(h.get());
   std::memset(H, 0, sizeof(double) * 144); std::memset(b, 0, sizeof(double) * 12);
   *cost = r[0];
-  int k = 1;
-  for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) { H[12 * a + c] = r[k]; H[12 * c + a] = r[k]; ++k; }
-  for (int a = 0; a < 6; ++a) b[a] = r[22 + a];
-  k = 28;
-  for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) { H[12 * (6 + a) + 6 + c] = r[k]; H[12 * (6 + c) + 6 + a] = r[k]; ++k; }
-  for (int a = 0; a < 6; ++a) b[6 + a] = r[49 + a];
+  auto sym6 = [&](int at, const double* u) { for (int a = 0; a < 6; ++a) for (int c = a; c < 6; ++c) H[12 * (at + a) + at + c] = H[12 * (at + c) + at + a] = *u++; };
+  sym6(0, r + 1); sym6(6, r + 28);
+  for (int a = 0; a < 6; ++a) { b[a] = r[22 + a]; b[6 + a] = r[49 + a]; }
   for (int a = 0; a < 6; ++a) for (int c = 0; c < 6; ++c) { H[12 * a + 6 + c] = r[55 + 6 * a + c]; H[12 * (6 + c) + a] = r[55 + 6 * a + c]; }
   return 0;
   E3D_CATCH()
