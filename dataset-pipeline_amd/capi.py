@@ -95,6 +95,7 @@ SIGNATURES = {
     "e3d_reg_get_variable_descriptors": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "e3d_reg_set_camera_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "e3d_reg_set_depth_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "e3d_reg_set_rig_depth_residuals": (C.c_int, [C.c_void_p, C.c_int]),
     "e3d_reg_depth_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_depth_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "e3d_reg_set_intrinsics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int]),
@@ -669,9 +670,14 @@ class RegProblem:
         arr = (C.c_void_p * len(keep))(*[l.ctypes.data for l in keep])
         self._chk(lib().e3d_reg_set_depth_maps(self._h, image_id, arr), "e3d_reg_set_depth_maps")
 
+    def set_rig_depth_residuals(self, enable=True):
+        """Depth residuals of the non-reference images of a rig (an error by default, as the reference aborts on them); kept by set_params."""
+        self._chk(lib().e3d_reg_set_rig_depth_residuals(self._h, int(bool(enable))), "e3d_reg_set_rig_depth_residuals")
+
     def depth_accumulate(self, image_id, point_scale):
-        """(H, b, sum of robust residuals, count) of the depth residuals of one (image, point scale); V = I + 6."""
-        V = self._nparams[self._image_intr[image_id]] + 6
+        """(H, b, sum of robust residuals, count) of the depth residuals of one (image, point scale); V = I + 6, or I + 12 for a
+        non-reference rig image (local_unknowns)."""
+        V = self.local_unknowns(image_id)
         H = np.zeros((V, V), np.float64); b = np.zeros(V, np.float64)
         sm = C.c_double(0); cn = C.c_int64(0)
         self._chk(lib().e3d_reg_depth_accumulate(self._h, image_id, point_scale, C.c_void_p(H.ctypes.data), C.c_void_p(b.ctypes.data),

@@ -1194,19 +1194,26 @@ __device__ __forceinline__ void load_row(const float4* __restrict__ rows, size_t
 }
 
 // ==== depth residuals (off by default: parameters.h:55, "not used in ETH3D pipeline" :165) ==================================================
-// ComputePointIntensityAndJacobians, depth part (intrinsics_and_pose_optimizer.cc:1150-1214), images that are not dependent rig images
-// (the reference aborts for those, :1199-1207).  Row of one observation: [residual, J_intrinsics(I), J_pose(6), 0-padding] as
-// rows4(I + 6) float4.  The projection terms are those of k_reg_pass1 with the depth pyramid's interpolation derivative, scaled by
-// -1 / depth^2, in place of the image's; the pose block loses (-1 / z^2) times the z row of d(camera point) / d(pose).
+// ComputePointIntensityAndJacobians, depth part (intrinsics_and_pose_optimizer.cc:1150-1214).  Row of one observation: [residual,
+// J_intrinsics(I), J_pose(6), 0-padding] as rows4(I + 6) float4.  The projection terms are those of k_reg_pass1 with the depth
+// pyramid's interpolation derivative, scaled by -1 / depth^2, in place of the image's; the pose block loses (-1 / z^2) times the z
+// row of d(camera point) / d(pose).
+// RIG: a non-reference image of a rig frame (the reference aborts for those, :1199-1207, its two "TODO" terms; opt-in here,
+// e3d_reg_set_rig_depth_residuals).  Row = [residual, J_intrinsics(I), J_extrinsics(6), J_rigpose(6)] as rows4(I + 12) float4, the
+// layout of k_reg_pass1<M, true>.  P / quat are the composed pose image_T_rig * rig_T_global, T the camera-space point, G = rig_T_global
+// * point, R = image_T_rig's rotation; both updates act on the left (:1107-1147), so d(T) / d(extrinsics) = [I | -[T]x] and
+// d(T) / d(rig pose) = R [I | -[G]x].  With a' = a - (-1 / z^2) e_z (the projection terms minus the derivative of the point's own
+// inverse depth): J_extrinsics = a' [I | -[T]x] -- the pose block above at the composed pose -- and J_rigpose = a' R [I | -[G]x].
 struct DepthPyramid { const float* map[kRegMaxLevels]; };
 
-template <int M>
+template <int M, bool RIG>
 __global__ __launch_bounds__(kBlock) void k_reg_depth_rows(const float4* __restrict__ pts, float point_radius, Pose P, float4 quat /* w x y z */,
                                                            Pyramid Y, DepthPyramid D, const unsigned* __restrict__ o_idx,
                                                            const float* __restrict__ o_x, const float* __restrict__ o_y,
-                                                           const float* __restrict__ o_s, size_t n_obs, float4* __restrict__ rows) {
+                                                           const float* __restrict__ o_s, size_t n_obs, RigLink L,
+                                                           float4* __restrict__ rows) {
   constexpr int I = cam_param_count(M);
-  constexpr int R4 = rows4(I + 6);
+  constexpr int R4 = rows4(I + (RIG ? 12 : 6));
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n_obs) return;
   const float4 p = pts[o_idx[i]];
@@ -1273,6 +1280,26 @@ __global__ __launch_bounds__(kBlock) void k_reg_depth_rows(const float4* __restr
     v -= j_point_inv * C2[c];
     row[1 + I + c] = v;
   }
+  if constexpr (RIG) {
+    // ar = (a - j_point_inv e_z)^T R, then the pose block of k_reg_pass1<M, true> with it
+    const float az = a[2] - j_point_inv;
+    float ar[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) ar[c] = a[0] * L.R_image_rig[c] + (a[1] * L.R_image_rig[3 + c] + az * L.R_image_rig[6 + c]);
+    // Sophus SO3 action: p + w * uv + v x uv, uv = 2 (v x p); then + translation
+    const float gx = L.q_rig_global[1], gy = L.q_rig_global[2], gz = L.q_rig_global[3], gw = L.q_rig_global[0];
+    float hx = gy * p.z - gz * p.y, hy = gz * p.x - gx * p.z, hz = gx * p.y - gy * p.x;
+    hx = hx + hx; hy = hy + hy; hz = hz + hz;
+    const float kx = gy * hz - gz * hy, ky = gz * hx - gx * hz, kz = gx * hy - gy * hx;
+    const float G0 = ((p.x + gw * hx) + kx) + L.t_rig_global[0];
+    const float G1 = ((p.y + gw * hy) + ky) + L.t_rig_global[1];
+    const float G2 = ((p.z + gw * hz) + kz) + L.t_rig_global[2];
+    const float D0[6] = {1, 0, 0, 0, G2, -1 * G1};
+    const float D1[6] = {0, 1, 0, -1 * G2, 0, G0};
+    const float D2[6] = {0, 0, 1, G1, -1 * G0, 0};
+#pragma unroll
+    for (int c = 0; c < 6; ++c) row[1 + I + 6 + c] = ar[0] * D0[c] + (ar[1] * D1[c] + ar[2] * D2[c]);
+  }
 #pragma unroll
   for (int r = 0; r < R4; ++r) rows[R4 * i + r] = make_float4(row[4 * r], row[4 * r + 1], row[4 * r + 2], row[4 * r + 3]);
 }
@@ -1331,7 +1358,9 @@ __global__ __launch_bounds__(kBlock) void k_reg_depth_acc(const float4* __restri
   }
 }
 
-// CostCalculator, depth part (cost_calculator.cc:221-245): partial[2 b] = sum of the robust residuals, partial[2 b + 1] = count
+// CostCalculator, depth part (cost_calculator.cc:221-245): partial[2 b] = sum of the robust residuals, partial[2 b + 1] = count.
+// The same kernel serves the non-reference images of a rig: P and quat are the image's own image_T_global, which compose_rig_poses
+// keeps at image_T_rig * rig_T_global for them, and the residual depends on nothing else.
 __global__ __launch_bounds__(kBlock) void k_reg_depth_cost(const float4* __restrict__ pts, Pose P, float4 quat, Pyramid Y, DepthPyramid D,
                                                            const unsigned* __restrict__ o_idx, const float* __restrict__ o_x,
                                                            const float* __restrict__ o_y, const float* __restrict__ o_s, size_t n_obs,
@@ -2392,6 +2421,7 @@ struct e3d_reg {
   float min_occlusion_depth = 0.05f, max_occlusion_depth = 100.f;     // opt::Parameters defaults (parameters.h:60-61)
   bool mask_occlusion_boundaries = true;
   bool cache_observations = false;        // Optimizer::cache_observations_ (optimizer.h)
+  bool rig_depth_residuals = false;       // e3d_reg_set_rig_depth_residuals: depth residuals of the non-reference rig images
   DevBuf<float4> scan_pts;                // f4: evaluation scan points + their observation counts
   DevBuf<int> scan_counts;
   DevBuf<unsigned char> eval_mask;
@@ -3174,15 +3204,16 @@ static DepthPyramid make_depth_pyramid(e3d_reg* h, const ImageDev& im, int image
   const Intrin& in = h->intr.at(im.intrinsics_id);
   if (im.depth_maps.size() != in.levels.size())
     throw Error(E3D_ERR_INVALID, fmt("depth residuals are enabled but image %d has no depth maps (e3d_reg_set_depth_maps)", image_id));
-  if (im.dependent())     // intrinsics_and_pose_optimizer.cc:1199-1207: LOG(FATAL) << "Not implemented yet"
-    throw Error(E3D_ERR_INVALID, "depth residuals for the non-reference images of a rig are not implemented (nor are they in the reference)");
+  if (im.dependent() && !h->rig_depth_residuals)     // intrinsics_and_pose_optimizer.cc:1199-1207: LOG(FATAL) << "Not implemented yet"
+    throw Error(E3D_ERR_INVALID, "depth residuals for the non-reference images of a rig are not implemented in the reference; e3d_reg_set_rig_depth_residuals enables them");
   DepthPyramid D{};
   for (size_t l = 0; l < in.levels.size(); ++l) D.map[l] = im.depth_maps[l].p;
   return D;
 }
 
 // The depth residuals of one (image, point scale): normal equations of the V = I + 6 local unknowns [intrinsics, pose] (row-major V x V,
-// upper triangle), b, the sum of the robust residuals and their count (intrinsics_and_pose_optimizer.cc:747-757, 1150-1214, 1219-1296)
+// upper triangle), b, the sum of the robust residuals and their count (intrinsics_and_pose_optimizer.cc:747-757, 1150-1214, 1219-1296).
+// A non-reference rig image (e3d_reg_set_rig_depth_residuals): V = I + 12, [intrinsics, rig extrinsics, rig pose] as in accumulate.
 static void depth_accumulate(e3d_reg* h, int image_id, int point_scale, double* H, double* b, double* sum, int64_t* count) {
   hipStream_t s = h->stream;
   ImageDev& im = get_image(h, image_id);
@@ -3190,21 +3221,30 @@ static void depth_accumulate(e3d_reg* h, int image_id, int point_scale, double* 
   Obs& O = get_obs(im, point_scale);
   const DepthPyramid D = make_depth_pyramid(h, im, image_id);
   const int model = image_model(h, im);
-  const int V = h->intr.at(im.intrinsics_id).n_params + 6, slot = reg_slot(V);
+  const int V = local_unknowns(h, im), slot = reg_slot(V);
   O.drows.reserve((size_t)rows4(V) * std::max<size_t>(O.n, 1));
   const float4 quat = make_float4(im.pose_q.q.w, im.pose_q.q.x, im.pose_q.q.y, im.pose_q.q.z);
-  if (O.n)
-    E3D_CAM_SWITCH(model, hipLaunchKernelGGL(k_reg_depth_rows<M>, dim3(nblk(O.n)), dim3(kBlock), 0, s, S.pts.p, S.radius, im.pose, quat,
-                                             make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p, O.s.p, O.n, O.drows.p));
+  if (O.n) {
+    const RigLink L = rig_link(h, im);
+    if (im.dependent()) {
+      E3D_CAM_SWITCH(model, hipLaunchKernelGGL((k_reg_depth_rows<M, true>), dim3(nblk(O.n)), dim3(kBlock), 0, s, S.pts.p, S.radius, im.pose, quat,
+                                               make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p, O.s.p, O.n, L, O.drows.p));
+    } else {
+      E3D_CAM_SWITCH(model, hipLaunchKernelGGL((k_reg_depth_rows<M, false>), dim3(nblk(O.n)), dim3(kBlock), 0, s, S.pts.p, S.radius, im.pose, quat,
+                                               make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p, O.s.p, O.n, L, O.drows.p));
+    }
+  }
   const int nb = partial_blocks(O.n, 1024);
   h->partial.reserve((size_t)nb * slot); h->red.reserve(slot);
   const int rt = h->prm.depth_robust_weighting_type;
   const float rp = h->prm.depth_robust_weighting_parameter, dw = h->prm.depth_residuals_weight;
 #define E3D_DEPTH(V_, R0_, R1_, B_) \
   hipLaunchKernelGGL((k_reg_depth_acc<V_, R0_, R1_, B_>), dim3(nb), dim3(kBlock), 0, s, O.drows.p, O.n, rt, rp, dw, h->partial.p)
-  switch (V) {     // (the sizes of the camera models without a rig)
+  switch (V) {     // (the sizes of the camera models without a rig, then those of the non-reference rig images)
     E3D_ROWS_CASE(9, E3D_DEPTH) E3D_ROWS_CASE(10, E3D_DEPTH) E3D_ROWS_CASE(11, E3D_DEPTH) E3D_ROWS_CASE(13, E3D_DEPTH)
     E3D_ROWS_CASE(14, E3D_DEPTH) E3D_ROWS_CASE(18, E3D_DEPTH)
+    E3D_ROWS_CASE(15, E3D_DEPTH) E3D_ROWS_CASE(16, E3D_DEPTH) E3D_ROWS_CASE(17, E3D_DEPTH) E3D_ROWS_CASE(19, E3D_DEPTH)
+    E3D_ROWS_CASE(20, E3D_DEPTH) E3D_ROWS_CASE(24, E3D_DEPTH)
     default: throw Error(E3D_ERR_INVALID, "unsupported local system size");
   }
 #undef E3D_DEPTH
@@ -3405,7 +3445,8 @@ static void reduce_sums(e3d_reg* h, double sums[3], int64_t counts[3]) {
   for (int i = 0; i < 3; ++i) { sums[i] = buf[i]; counts[i] = (int64_t)buf[3 + i]; }
 }
 
-// depth residuals are in use: every image needs its depth maps, and none may be a dependent rig image (as in the reference)
+// depth residuals are in use: every image needs its depth maps, and -- as in the reference -- none may be a non-reference rig image
+// unless e3d_reg_set_rig_depth_residuals allowed them (make_depth_pyramid throws for the first image that breaks either rule)
 static bool depth_in_use(const e3d_reg* h) { return h->prm.depth_residuals_weight > 0; }
 
 // The colour costs of many (image, point scale) pairs: enqueued back to back, read with ONE copy and added in the order of the
@@ -3551,14 +3592,15 @@ static void accumulate_system(e3d_reg* h, NormalSystem& N) {
     accumulate_unpack(Vl, all.data() + j.off, Hl.data(), bl.data(), s2, c2);
     N.sums[0] += s2[0]; N.sums[1] += s2[1]; N.counts[0] += c2[0]; N.counts[1] += c2[1];
     // the local [intrinsics(I), (rig extrinsics(6),) pose(6)] block
-    scatter_block(N.Hb, Vl, Hl.data(), bl.data(), [&](int l) { return l < I ? ii + l : ((dep && l < I + 6) ? ri + (l - I) : pi + (l - (Vl - 6))); });
+    const auto index_of = [&](int l) { return l < I ? ii + l : ((dep && l < I + 6) ? ri + (l - I) : pi + (l - (Vl - 6))); };
+    scatter_block(N.Hb, Vl, Hl.data(), bl.data(), index_of);
     if (depth_in_use(h)) {
-      // depth residuals of every observation (intrinsics_and_pose_optimizer.cc:747-757); [intrinsics(I), pose(6)] block
-      std::vector<double> Hd((size_t)(I + 6) * (I + 6)), bd(I + 6);
+      // depth residuals of every observation (intrinsics_and_pose_optimizer.cc:747-757): a block of the same local unknowns
+      std::vector<double> Hd((size_t)Vl * Vl), bd(Vl);
       double sd; int64_t cd;
       depth_accumulate(h, j.image_id, j.scale, Hd.data(), bd.data(), &sd, &cd);
       N.sums[2] += sd; N.counts[2] += cd;
-      scatter_block(N.Hb, I + 6, Hd.data(), bd.data(), [&](int l) { return l < I ? ii + l : pi + (l - I); });
+      scatter_block(N.Hb, Vl, Hd.data(), bd.data(), index_of);
     }
   }
   rsync(h);
@@ -4178,6 +4220,16 @@ int e3d_reg_set_depth_maps(e3d_reg_t* h, int image_id, const float* const* level
     copy_in(im.depth_maps[l].p, level_depths[l], sizeof(float) * px, h->stream);
   }
   rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+/* Opt-in: depth residuals of the non-reference images of a rig (the two Jacobian terms the reference leaves as TODO and aborts on,
+ * intrinsics_and_pose_optimizer.cc:1199-1207).  A property of the handle, not of e3d_reg_params: e3d_reg_set_params keeps it. */
+int e3d_reg_set_rig_depth_residuals(e3d_reg_t* h, int enable) {
+  E3D_TRY_ON(h)
+  if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  h->rig_depth_residuals = enable != 0;
   return 0;
   E3D_CATCH()
 }

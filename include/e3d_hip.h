@@ -385,12 +385,18 @@ int e3d_reg_set_camera_mask(e3d_reg_t* reg, int intrinsics_id, const uint8_t* co
  * residual = 1 / (depth map interpolated at the observation) - 1 / (depth of the point in the image frame), one per observation,
  * weighted by e3d_reg_params.depth_residuals_weight with its own robust weighting.  Off by default and unused by the reference's
  * tools (no tool loads depth maps; its alignment test does, test_alignment.cc:469-500).  As in the reference the non-reference
- * images of a rig are not supported with depth residuals (:1199-1207 aborts) -- here that is an error return.
+ * images of a rig are not supported with depth residuals by default (:1199-1207 aborts) -- here that is an error return.
+ *   e3d_reg_set_rig_depth_residuals(enable != 0) lifts that for this handle (default 0; e3d_reg_set_params keeps it): the two Jacobian
+ *     terms the reference leaves open are supplied (d z / d extrinsics = row 2 of [I | -[T]x], d z / d rig pose = row 2 of
+ *     R_image_rig [I | -[G]x], T = image_T_global * point, G = rig_T_global * point), and every call below accepts such images.
  *   e3d_reg_set_depth_maps: Problem::SetFixedDepthMaps for one image, one f32 map per pyramid level of its camera (caller-built
  *     pyramid, like the test's cv::resize INTER_AREA chain); NULL removes them.  Required for every image once the weight is > 0.
  *   e3d_reg_depth_accumulate / e3d_reg_depth_cost: the depth part of AccumulateHAndBForImage / ComputeResidualsForImage for one
- *     (image, point scale); e3d_reg_apply, e3d_reg_compute_cost and e3d_reg_run_on_current_scale include them by themselves. */
+ *     (image, point scale); e3d_reg_apply, e3d_reg_compute_cost and e3d_reg_run_on_current_scale include them by themselves.
+ *     H is the V x V upper triangle (row-major) and b has V entries, V = the image's local unknowns as in e3d_reg_accumulate:
+ *     I + 6 [intrinsics, pose], or I + 12 [intrinsics, rig extrinsics, rig pose] for a non-reference rig image. */
 int e3d_reg_set_depth_maps(e3d_reg_t* reg, int image_id, const float* const* level_depths);
+int e3d_reg_set_rig_depth_residuals(e3d_reg_t* reg, int enable);
 int e3d_reg_depth_accumulate(e3d_reg_t* reg, int image_id, int point_scale, double* H, double* b, double* sum, int64_t* count);
 int e3d_reg_depth_cost(e3d_reg_t* reg, int image_id, int point_scale, double* sum, int64_t* count);
 /* queries one level of the pyramid the library built: size, parameters (n_parameters floats) and the radius cut-off
