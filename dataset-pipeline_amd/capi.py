@@ -130,6 +130,8 @@ SIGNATURES = {
     "e3d_reg_scan_colors_finish": (C.c_int, [C.c_void_p, C.c_void_p]),
     "e3d_reg_ground_truth_depth": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "e3d_reg_scan_rendering": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "e3d_reg_mask_transfer_source": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "e3d_reg_mask_transfer_target": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_set_cache_observations": (C.c_int, [C.c_void_p, C.c_int]),
     "e3d_reg_determine_observed_indices": (C.c_int, [C.c_void_p]),
     "e3d_reg_get_observed_indices": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -782,6 +784,39 @@ class RegProblem:
         self._chk(lib().e3d_reg_scan_rendering(self._h, image_id, C.c_void_p(m.ctypes.data) if m is not None else None, excluded_flag,
                                                min_count, point_radius, C.c_void_p(win.ctypes.data)), "e3d_reg_scan_rendering")
         return win
+
+    # ---- MaskTransfer (DatasetInspector "Label transfer", gui_main_window.cc:868-1054) ----------------------------------------------
+    def _level0_shape(self, image_id):
+        if image_id not in self._image_intr:
+            raise E3DError("image %d not set" % image_id)
+        w, h, _, _ = self.intrinsics_level(self._image_intr[image_id], 0)
+        return h, w
+
+    def _mask_ptr(self, mask, shape, keep, what):
+        if tuple(mask.shape) != tuple(shape):
+            raise E3DError("%s has shape %s, the image's camera is %s (height, width)" % (what, tuple(mask.shape), tuple(shape)))
+        return _ptr(mask, np.uint8, keep)
+
+    def mask_transfer_source(self, image_id, mask, transfer_eval_obs=False):
+        """Source half of the label transfer: mask is the (height, width) uint8 level-0 mask of image_id (0 / 1 / 2; numpy or a torch
+        tensor, host or device).  Labels the scan points (set_scan_points) and returns how many carry a label."""
+        image_id = int(image_id)
+        keep = []
+        p = self._mask_ptr(mask, self._level0_shape(image_id), keep, "mask")
+        return int(self._chk(lib().e3d_reg_mask_transfer_source(self._h, image_id, p, int(bool(transfer_eval_obs))), "e3d_reg_mask_transfer_source"))
+
+    def mask_transfer_target(self, image_id, existing=None, return_stats=False):
+        """Target half (any number of times after one mask_transfer_source): -> the merged (height, width) uint8 mask of image_id, and
+        with return_stats also (pixels set by the point pass, non-zero pixels after the fill-in, pixels that differ from `existing`)."""
+        image_id = int(image_id)
+        keep = []
+        shape = self._level0_shape(image_id)
+        e = self._mask_ptr(existing, shape, keep, "existing") if existing is not None else None
+        out = np.zeros(shape, np.uint8)
+        stats = np.zeros(3, np.int64)
+        self._chk(lib().e3d_reg_mask_transfer_target(self._h, image_id, e, C.c_void_p(out.ctypes.data), C.c_void_p(stats.ctypes.data)),
+                  "e3d_reg_mask_transfer_target")
+        return (out, tuple(int(v) for v in stats)) if return_stats else out
 
     def set_cache_observations(self, enabled):
         """Optimizer::set_cache_observations: update_observations re-projects the cached point index lists."""

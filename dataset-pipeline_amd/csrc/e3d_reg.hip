@@ -1046,6 +1046,168 @@ __global__ __launch_bounds__(kBlock) void k_scan_visibility(const float4* __rest
   }
 }
 
+// ==== MaskTransfer: DatasetInspector's "Label transfer" (src/dataset_inspector/gui_main_window.cc:868-1054) ========================
+// A mask drawn in one image carried to another through the scan points.  The reference is one serial loop over the cloud that
+// writes target_mask(target pixel) = source_mask(source pixel) for every point visible in both images, later points over earlier
+// ones, then fills holes with a 5 x 5 vote and merges the result into the target's mask.  Here: per point the label it carries
+// (k_mask_label_points, once per source), per target the highest labelled point index per pixel (k_mask_scatter, atomicMax of
+// index + 1 as in the scan rendering above -- integer max, so the result is the serial loop's whatever the launch order), then one
+// pass over the target's pixels (k_mask_fill).
+//
+// Visibility of a point in an image (:909-921, :931-943): z > 0, the rounded pixel inside the image at the highest resolution,
+// occlusion + threshold >= z; returns the pixel's index or -1.  Unlike the visibility test above, the reference also asks for
+// pxy + 0.5f >= 0 here: (int) truncates towards zero, so a position in (-1.5, -0.5) would otherwise land in column / row 0.
+template <int M>
+__device__ __forceinline__ long long mask_visible_pixel(const float4 p, const Pose& P, const CamLevel& cam, const float* __restrict__ occlusion,
+                                                        float occlusion_threshold) {
+  float X, Yc, Z;
+  rt(P, p.x, p.y, p.z, X, Yc, Z);
+  if (!(Z > 0.f)) return -1;
+  float ixf, iyf;
+  cam_normalized_to_image<M>(cam, X / Z, Yc / Z, ixf, iyf);
+  const float rx = ixf + 0.5f, ry = iyf + 0.5f;
+  if (!(rx >= 0.f && ry >= 0.f)) return -1;
+  const int ix = f2i(rx), iy = f2i(ry);
+  if (!(ix >= 0 && iy >= 0 && ix < cam.width && iy < cam.height)) return -1;
+  const size_t px = (size_t)iy * cam.width + ix;
+  if (!(occlusion[px] + occlusion_threshold >= Z)) return -1;
+  return (long long)px;
+}
+
+// the block's number of set flags added to *counter: one atomic per block (every thread of the block calls it)
+__device__ __forceinline__ void block_count_add(bool flag, unsigned long long* __restrict__ counter, unsigned* sc) {
+  const unsigned long long b = __ballot(flag);
+  if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = (unsigned)__popcll(b);
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned c = 0;
+    for (int w = 0; w < kBlock / kWave; ++w) c += sc[w];
+    if (c) atomicAdd(counter, (unsigned long long)c);
+  }
+  __syncthreads();
+}
+
+// bad[0] += number of mask bytes other than 0 / 1 / 2 (image.cc:87-97 aborts on them)
+__global__ __launch_bounds__(kBlock) void k_mask_check_values(const unsigned char* __restrict__ mask, size_t n, unsigned long long* __restrict__ bad) {
+  __shared__ unsigned sc[kBlock / kWave];
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  block_count_add(i < n && mask[i] > 2, bad, sc);
+}
+
+// Source half: labels[i] = the source mask's value at the point's pixel if the point is visible there and the value is not 0 nor --
+// without transfer_eval_obs -- kEvalObs (2); else 0.  labelled[0] += number of non-zero labels.
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_mask_label_points(const float4* __restrict__ pts, size_t n, Pose P, CamLevel cam,
+                                                              const float* __restrict__ occlusion, float occlusion_threshold,
+                                                              const unsigned char* __restrict__ mask, int transfer_eval_obs,
+                                                              unsigned char* __restrict__ labels, unsigned long long* __restrict__ labelled) {
+  __shared__ unsigned sc[kBlock / kWave];
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  unsigned char v = 0;
+  if (i < n) {
+    const long long px = mask_visible_pixel<M>(pts[i], P, cam, occlusion, occlusion_threshold);
+    if (px >= 0) {
+      v = mask[px];
+      if (v > 2 || (v == 2 && !transfer_eval_obs)) v = 0;       // (values above 2 are refused by the caller; never a label)
+    }
+    labels[i] = v;
+  }
+  block_count_add(v != 0, labelled, sc);
+}
+
+// Target half, point pass: winner[pixel] = max (index + 1) over the labelled points visible in the target; 0 = no point.  The label
+// is read first: most points of a real dataset carry none and leave without fetching their position.
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_mask_scatter(const float4* __restrict__ pts, const unsigned char* __restrict__ labels, size_t n,
+                                                         Pose P, CamLevel cam, const float* __restrict__ occlusion, float occlusion_threshold,
+                                                         unsigned* __restrict__ winner) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n || labels[i] == 0) return;
+  const long long px = mask_visible_pixel<M>(pts[i], P, cam, occlusion, occlusion_threshold);
+  if (px >= 0) atomicMax(&winner[px], (unsigned)i + 1u);
+}
+
+// Target half, per pixel: the winner's label; the numbers of kObs (1) and kEvalObs (2) labels in the 5 x 5 window around it, clipped
+// at the image borders (:997-1023; the reference's integral images are its way to count, any exact count gives the same mask);
+// obs >= 3 -> kObs, then with transfer_eval_obs eval_obs >= 3 -> kEvalObs (:1025-1030; so a kEvalObs pixel with >= 3 kObs but
+// fewer than 3 kEvalObs pixels around it BECOMES kObs -- the reference's behaviour, kept); merge (:1034-1047): the new value
+// replaces the existing one where it is not 0 and the existing one is not kEvalObs.  The window counts come from the point pass
+// alone (all labels of the tile and its 2-pixel apron are staged in LDS before any pixel is decided), so the fill is not recursive.
+// counters: [0] pixels set by the point pass, [1] non-zero pixels after the fill-in, [2] pixels of the merged mask that differ from
+// the existing one (from 0 without one), [3] existing values other than 0 / 1 / 2.
+// One block: 64 x 16 pixels, one wave per 4 rows, 4 pixels (one column of those rows) per thread: the 5-tap row sums of the 8 tile
+// rows a thread's pixels see are formed once (kObs count in the low half-word, kEvalObs count in the high one) and shared by them.
+constexpr int kMaskTileW = kWave, kMaskRows = 4, kMaskTileH = (kBlock / kWave) * kMaskRows, kMaskApron = 2;
+__global__ __launch_bounds__(kBlock) void k_mask_fill(const unsigned* __restrict__ winner, const unsigned char* __restrict__ labels, int width,
+                                                      int height, int transfer_eval_obs, const unsigned char* __restrict__ existing,
+                                                      unsigned char* __restrict__ out, unsigned long long* __restrict__ counters) {
+  constexpr int LW = kMaskTileW + 2 * kMaskApron, LH = kMaskTileH + 2 * kMaskApron, kWin = 2 * kMaskApron + 1;
+  __shared__ unsigned char tile[LH][LW];
+  __shared__ unsigned sc[kBlock / kWave][4];
+  const int x0 = (int)blockIdx.x * kMaskTileW, y0 = (int)blockIdx.y * kMaskTileH;
+  for (int k = threadIdx.x; k < LW * LH; k += kBlock) {
+    const int ly = k / LW, lx = k - ly * LW;
+    const int x = x0 + lx - kMaskApron, y = y0 + ly - kMaskApron;
+    unsigned char v = 0;                        // outside the image: no label -- the window is clipped, not clamped
+    if (x >= 0 && y >= 0 && x < width && y < height) {
+      const unsigned w = winner[(size_t)y * width + x];
+      if (w) v = labels[w - 1];
+    }
+    tile[ly][lx] = v;
+  }
+  __syncthreads();
+  const int tx = threadIdx.x % kWave, wave = threadIdx.x / kWave;
+  const int x = x0 + tx, ly0 = wave * kMaskRows;              // the thread's pixels: column x, rows y0 + ly0 .. + kMaskRows - 1
+  unsigned row_sum[kMaskRows + kWin - 1];
+#pragma unroll
+  for (int k = 0; k < kMaskRows + kWin - 1; ++k) {
+    unsigned s = 0;
+#pragma unroll
+    for (int dx = 0; dx < kWin; ++dx) {
+      const unsigned char t = tile[ly0 + k][tx + dx];
+      s += (t == 1 ? 1u : 0u) + (t == 2 ? 0x10000u : 0u);
+    }
+    row_sum[k] = s;
+  }
+  constexpr unsigned kFillInThreshold = 3;      // (int)(0.10f * 25 + 0.5f)
+  unsigned count[4] = {0, 0, 0, 0};             // (wave-uniform) set by the point pass, non-zero after the fill-in, changed, bad existing value
+#pragma unroll
+  for (int j = 0; j < kMaskRows; ++j) {
+    const int y = y0 + ly0 + j;
+    const bool inside = x < width && y < height;
+    bool set_by_points = false, non_zero = false, changed = false, bad = false;
+    if (inside) {
+      unsigned s = 0;
+#pragma unroll
+      for (int k = 0; k < kWin; ++k) s += row_sum[j + k];
+      const unsigned obs = s & 0xFFFFu, eval_obs = s >> 16;
+      unsigned char v = tile[ly0 + j + kMaskApron][tx + kMaskApron];
+      set_by_points = v != 0;
+      if (obs >= kFillInThreshold) v = 1;
+      if (transfer_eval_obs && eval_obs >= kFillInThreshold) v = 2;
+      non_zero = v != 0;
+      const size_t px = (size_t)y * width + x;
+      const unsigned char e = existing ? existing[px] : (unsigned char)0;
+      bad = e > 2;
+      const unsigned char m = (v != 0 && e != 2) ? v : e;
+      changed = m != e;
+      out[px] = m;
+    }
+    count[0] += (unsigned)__popcll(__ballot(set_by_points));
+    count[1] += (unsigned)__popcll(__ballot(non_zero));
+    count[2] += (unsigned)__popcll(__ballot(changed));
+    count[3] += (unsigned)__popcll(__ballot(bad));
+  }
+  if (tx == 0)
+    for (int c = 0; c < 4; ++c) sc[wave][c] = count[c];
+  __syncthreads();
+  if (threadIdx.x < 4) {                        // one atomic per block and counter
+    unsigned c = 0;
+    for (int w = 0; w < kBlock / kWave; ++w) c += sc[w][threadIdx.x];
+    if (c) atomicAdd(counters + threadIdx.x, (unsigned long long)c);
+  }
+}
+
 // ==== a22 ===============================================================================================================================
 __global__ __launch_bounds__(kBlock) void k_obs_mark(const unsigned* __restrict__ o_idx, size_t n_obs, int* __restrict__ row_of_point) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -2432,6 +2594,12 @@ struct e3d_reg {
   DevBuf<float4> scan_color_acc;
   DevBuf<unsigned char> scan_color_image, scan_color_rgb;
   bool scan_colors_begun = false;
+  // mask transfer (e3d_reg_mask_transfer_*): the label every scan point carries from the last source call (kept between target calls),
+  // the masks of the running call, {labelled points | the four counters of k_mask_fill, bad source values}
+  DevBuf<unsigned char> mask_labels, mask_in, mask_result;
+  DevBuf<unsigned long long> mask_counters;
+  bool mask_labels_ready = false;
+  int mask_transfer_eval_obs = 0;
   // scratch
   DevBuf<int> valid;
   DevBuf<float> tx, ty, ts;
@@ -4404,7 +4572,7 @@ int e3d_reg_set_scan_points(e3d_reg_t* h, const float* xyz, size_t n) {
   E3D_TRY_ON(h)
   if (!h || (n && !xyz)) throw Error(E3D_ERR_INVALID, "null argument");
   if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "more than 2^31-1 scan points");
-  h->n_scan = n; h->scan_points_set = true; h->scan_colors_begun = false;
+  h->n_scan = n; h->scan_points_set = true; h->scan_colors_begun = false; h->mask_labels_ready = false;
   h->scan_pts.reserve(n); h->scan_counts.reserve(n);
   if (n) {
     DevBuf<float> raw;
@@ -4489,6 +4657,79 @@ int e3d_reg_scan_rendering(e3d_reg_t* h, int image_id, const uint8_t* mask, int 
   scan_visibility(h, image_id, mask, excluded_flag, 2, min_count, point_radius);
   copy_out(winner, h->gt_depth.p, sizeof(unsigned) * px, h->stream);
   rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+// ---- MaskTransfer (MainWindow::TransferLabels, src/dataset_inspector/gui_main_window.cc:868-1054) ---------------------------------
+// the image of a mask transfer call, checked: known, owned by this rank
+static ImageDev& mask_transfer_image(e3d_reg* h, int image_id) {
+  ImageDev& im = get_image(h, image_id);
+  if (!h->owns(image_id)) throw Error(E3D_ERR_INVALID, fmt("image %d belongs to rank %d", image_id, image_owner(h, image_id)));
+  return im;
+}
+int64_t e3d_reg_mask_transfer_source(e3d_reg_t* h, int source_image_id, const uint8_t* source_mask, int transfer_eval_obs) {
+  E3D_TRY_ON(h)
+  if (!h || !source_mask) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
+  ImageDev& im = mask_transfer_image(h, source_image_id);
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  const size_t px = (size_t)cam.width * cam.height, n = h->n_scan;
+  h->mask_labels_ready = false;
+  h->mask_in.reserve(px); h->mask_labels.reserve(n); h->mask_counters.reserve(5);
+  copy_in(h->mask_in.p, source_mask, px, h->stream);
+  E3D_HIP(hipMemsetAsync(h->mask_counters.p, 0, sizeof(unsigned long long) * 5, h->stream));
+  hipLaunchKernelGGL(k_mask_check_values, dim3(nblk(px)), dim3(kBlock), 0, h->stream, h->mask_in.p, px, h->mask_counters.p + 4);
+  if (n) {
+    // RenderDepthMap(source_intrinsics, *source_image, source_intrinsics.min_image_scale, ...) + intrinsics.model(0) (:877-881)
+    render_depth(h, source_image_id, in.min_image_scale, nullptr);
+    KT kt(h, "mask.label_points", (double)n);
+    E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_mask_label_points<M>, dim3(nblk(n)), dim3(kBlock), 0, h->stream, h->scan_pts.p, n, im.pose, cam,
+                                               im.depth.p, h->prm.occlusion_depth_threshold, h->mask_in.p, transfer_eval_obs ? 1 : 0,
+                                               h->mask_labels.p, h->mask_counters.p));
+  }
+  unsigned long long counters[5];
+  read_back(h, counters, h->mask_counters.p, sizeof counters);
+  E3D_HIP(hipGetLastError());
+  if (counters[4]) throw Error(E3D_ERR_INVALID, fmt("the source mask holds %llu values other than 0, 1, 2", counters[4]));
+  h->mask_labels_ready = true;
+  h->mask_transfer_eval_obs = transfer_eval_obs ? 1 : 0;
+  return (int64_t)counters[0];
+  E3D_CATCH()
+}
+int e3d_reg_mask_transfer_target(e3d_reg_t* h, int target_image_id, const uint8_t* existing_mask, uint8_t* mask_out, int64_t* stats) {
+  E3D_TRY_ON(h)
+  if (!h || !mask_out) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
+  if (!h->mask_labels_ready) throw Error(E3D_ERR_INVALID, "call e3d_reg_mask_transfer_source first");
+  ImageDev& im = mask_transfer_image(h, target_image_id);
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  const size_t px = (size_t)cam.width * cam.height, n = h->n_scan;
+  h->gt_depth.reserve(px); h->mask_result.reserve(px);
+  if (existing_mask) { h->mask_in.reserve(px); copy_in(h->mask_in.p, existing_mask, px, h->stream); }
+  E3D_HIP(hipMemsetAsync(h->mask_counters.p, 0, sizeof(unsigned long long) * 5, h->stream));
+  E3D_HIP(hipMemsetAsync(h->gt_depth.p, 0, sizeof(unsigned) * px, h->stream));       // the winners, blank for every target (:901-903)
+  if (n) {
+    render_depth(h, target_image_id, in.min_image_scale, nullptr);                     // (:882-886)
+    KT kt(h, "mask.scatter", (double)n);
+    E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_mask_scatter<M>, dim3(nblk(n)), dim3(kBlock), 0, h->stream, h->scan_pts.p, h->mask_labels.p, n,
+                                               im.pose, cam, im.depth.p, h->prm.occlusion_depth_threshold, h->gt_depth.p));
+  }
+  {
+    KT kt(h, "mask.fill", (double)px);
+    const dim3 grid((unsigned)div_up(cam.width, kMaskTileW), (unsigned)div_up(cam.height, kMaskTileH));
+    hipLaunchKernelGGL(k_mask_fill, grid, dim3(kBlock), 0, h->stream, h->gt_depth.p, h->mask_labels.p, cam.width, cam.height,
+                       h->mask_transfer_eval_obs, existing_mask ? h->mask_in.p : nullptr, h->mask_result.p, h->mask_counters.p);
+  }
+  unsigned long long counters[5];
+  read_back(h, counters, h->mask_counters.p, sizeof counters);
+  E3D_HIP(hipGetLastError());
+  if (counters[3]) throw Error(E3D_ERR_INVALID, fmt("the existing mask holds %llu values other than 0, 1, 2", counters[3]));
+  copy_out(mask_out, h->mask_result.p, px, h->stream);
+  rsync(h);
+  if (stats) for (int k = 0; k < 3; ++k) stats[k] = (int64_t)counters[k];
   return 0;
   E3D_CATCH()
 }

@@ -154,6 +154,34 @@ inline bool load_pnm(const std::vector<uint8_t>& f, GrayImage* out, std::string*
   return true;
 }
 
+// an 8-bit PNG of `channels` = 1 (grey, colour type 0) or 3 (R G B, colour type 2) samples per pixel: filter 0 on every row, one IDAT chunk
+inline bool encode_png(const uint8_t* pixels, int width, int height, int channels, std::vector<uint8_t>* out) {
+  std::vector<uint8_t>& bytes = *out;
+  const size_t stride = (size_t)width * channels;
+  std::vector<uint8_t> raw((stride + 1) * (size_t)height);
+  for (int y = 0; y < height; ++y) { raw[(stride + 1) * y] = 0; memcpy(&raw[(stride + 1) * y + 1], pixels + stride * y, stride); }
+  uLongf clen = compressBound((uLong)raw.size());
+  std::vector<uint8_t> comp(clen);
+  if (compress2(comp.data(), &clen, raw.data(), (uLong)raw.size(), 1) != Z_OK) return false;
+  auto be = [&](uint32_t v) { for (int s2 = 24; s2 >= 0; s2 -= 8) bytes.push_back((uint8_t)(v >> s2)); };
+  auto chunk = [&](const char* type, const uint8_t* d, size_t n) {
+    be((uint32_t)n);
+    const size_t start = bytes.size();
+    bytes.insert(bytes.end(), type, type + 4);
+    bytes.insert(bytes.end(), d, d + n);
+    be((uint32_t)crc32(0L, &bytes[start], (uInt)(n + 4)));
+  };
+  const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
+  bytes.insert(bytes.end(), sig, sig + 8);
+  uint8_t ihdr[13];
+  for (int s2 = 0; s2 < 4; ++s2) { ihdr[s2] = (uint8_t)(width >> (24 - 8 * s2)); ihdr[4 + s2] = (uint8_t)(height >> (24 - 8 * s2)); }
+  ihdr[8] = 8; ihdr[9] = channels == 3 ? 2 : 0; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
+  chunk("IHDR", ihdr, 13);
+  chunk("IDAT", comp.data(), clen);
+  chunk("IEND", nullptr, 0);
+  return true;
+}
+
 }  // namespace img_detail
 
 // cv::imread(path, IMREAD_GRAYSCALE): empty image on failure (the caller reports it)
@@ -202,28 +230,7 @@ inline bool imwrite_color(const std::string& path, const ColorImage& img, std::s
     if (img.width > 65535 || img.height > 65535) { if (error) *error = "imwrite: image too large for JPEG"; return false; }
     bytes = encode_jpeg_rgb(img.rgb.data(), img.width, img.height, 95);
   } else if (ext == "png") {
-    const size_t stride = (size_t)img.width * 3;
-    std::vector<uint8_t> raw((stride + 1) * (size_t)img.height);
-    for (int y = 0; y < img.height; ++y) { raw[(stride + 1) * y] = 0; memcpy(&raw[(stride + 1) * y + 1], &img.rgb[stride * y], stride); }
-    uLongf clen = compressBound((uLong)raw.size());
-    std::vector<uint8_t> comp(clen);
-    if (compress2(comp.data(), &clen, raw.data(), (uLong)raw.size(), 1) != Z_OK) { if (error) *error = "imwrite: deflate failed"; return false; }
-    auto be = [&](uint32_t v) { for (int s2 = 24; s2 >= 0; s2 -= 8) bytes.push_back((uint8_t)(v >> s2)); };
-    auto chunk = [&](const char* type, const uint8_t* d, size_t n) {
-      be((uint32_t)n);
-      const size_t start = bytes.size();
-      bytes.insert(bytes.end(), type, type + 4);
-      bytes.insert(bytes.end(), d, d + n);
-      be((uint32_t)crc32(0L, &bytes[start], (uInt)(n + 4)));
-    };
-    const uint8_t sig[8] = {137, 80, 78, 71, 13, 10, 26, 10};
-    bytes.insert(bytes.end(), sig, sig + 8);
-    uint8_t ihdr[13];
-    for (int s2 = 0; s2 < 4; ++s2) { ihdr[s2] = (uint8_t)(img.width >> (24 - 8 * s2)); ihdr[4 + s2] = (uint8_t)(img.height >> (24 - 8 * s2)); }
-    ihdr[8] = 8; ihdr[9] = 2; ihdr[10] = 0; ihdr[11] = 0; ihdr[12] = 0;
-    chunk("IHDR", ihdr, 13);
-    chunk("IDAT", comp.data(), clen);
-    chunk("IEND", nullptr, 0);
+    if (!img_detail::encode_png(img.rgb.data(), img.width, img.height, 3, &bytes)) { if (error) *error = "imwrite: deflate failed"; return false; }
   } else if (ext == "ppm" || ext == "pnm") {
     char head[64];
     const int n = snprintf(head, sizeof head, "P6\n%d %d\n255\n", img.width, img.height);
@@ -233,6 +240,23 @@ inline bool imwrite_color(const std::string& path, const ColorImage& img, std::s
     if (error) *error = "imwrite: unsupported file extension ." + ext;
     return false;
   }
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) { if (error) *error = "cannot write " + path; return false; }
+  const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+  fclose(f);
+  if (!ok && error) *error = "cannot write " + path;
+  return ok;
+}
+
+// cv::imwrite(path.png, mask) for a single-channel 8-bit image: a grey PNG (colour type 0) that imread_gray reads back value for value
+inline bool imwrite_gray(const std::string& path, const GrayImage& img, std::string* error = nullptr) {
+  std::vector<uint8_t> bytes;
+  if (img.empty() || img.data.size() != (size_t)img.width * img.height) { if (error) *error = "imwrite: empty image"; return false; }
+  const size_t dot = path.find_last_of('.');
+  std::string ext;
+  if (dot != std::string::npos) for (size_t i = dot + 1; i < path.size(); ++i) ext += (char)tolower(path[i]);
+  if (ext != "png") { if (error) *error = "imwrite: grey images are written as .png only, not ." + ext; return false; }
+  if (!img_detail::encode_png(img.data.data(), img.width, img.height, 1, &bytes)) { if (error) *error = "imwrite: deflate failed"; return false; }
   FILE* f = fopen(path.c_str(), "wb");
   if (!f) { if (error) *error = "cannot write " + path; return false; }
   const bool ok = fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();

@@ -521,6 +521,36 @@ int e3d_reg_scan_colors_add_image(e3d_reg_t* reg, int image_id, const uint8_t* r
 int e3d_reg_scan_colors_get_sums(e3d_reg_t* reg, float* sums, int32_t* counts);
 int e3d_reg_scan_colors_set_sums(e3d_reg_t* reg, const float* sums, const int32_t* counts);
 int e3d_reg_scan_colors_finish(e3d_reg_t* reg, uint8_t* rgb);
+/* DatasetInspector "Label transfer" (src/dataset_inspector/gui_main_window.cc:476-559, the work in TransferLabels, :868-1054): a mask
+ * drawn in one image carried to other images through the scan points of e3d_reg_set_scan_points.  Both images are taken at their
+ * highest available resolution (intrinsics.model(0), mask_[0], occlusion depth at intrinsics.min_image_scale).  A point is visible
+ * in an image if z > 0, pxy = NormalizedToImage(x / z, y / z) has pxy.x + 0.5f >= 0 and pxy.y + 0.5f >= 0, the pixel
+ * ((int)(pxy.x + 0.5f), (int)(pxy.y + 0.5f)) lies inside the image and occlusion(iy, ix) + occlusion_depth_threshold >= z.
+ *   e3d_reg_mask_transfer_source, the source half: occlusion depth of the source image, then per scan point the label it carries:
+ *     the source mask's value v at its pixel if the point is visible there, v != 0 and -- when transfer_eval_obs is 0 -- v != 2
+ *     (opt::MaskType::kEvalObs), else 0 (:906-926).  source_mask: width x height bytes of the source camera's level 0, values
+ *     0 / 1 / 2 only; host or device.  Returns the number of labelled points.  The labels stay on the device until the next source
+ *     call or e3d_reg_set_scan_points.
+ *   e3d_reg_mask_transfer_target, the target half, any number of times after one source call:
+ *     point pass (:931-951) on a blank mask: every labelled point visible in the target writes its label to its target pixel in
+ *       cloud order, so per pixel the labelled point with the HIGHEST index decides;
+ *     fill-in (:957-1032): per pixel the numbers of kObs (1) and kEvalObs (2) pixels of the point pass in the 5 x 5 window around it,
+ *       clipped at the image borders; kObs count >= 3 -> kObs, then, with transfer_eval_obs, kEvalObs count >= 3 -> kEvalObs.  (So a
+ *       pixel the point pass set to kEvalObs becomes kObs when its window holds >= 3 kObs but fewer than 3 kEvalObs pixels: the
+ *       reference's behaviour, kept.)  The counts are taken before any pixel is filled.
+ *     merge (:1034-1047): mask_out = existing_mask with the new value written wherever it is not 0 and the existing value is not
+ *       kEvalObs; without existing_mask the new mask itself.
+ *     existing_mask (optional, the target's current level-0 mask) and mask_out (required) are width x height bytes of the TARGET
+ *     camera's level 0; host or device.  stats (optional, 3 x int64): pixels set by the point pass, non-zero pixels after the
+ *     fill-in, pixels of mask_out that differ from existing_mask (from 0 without one).  The masks the handle holds for the image
+ *     (e3d_reg_set_image) are neither read nor changed.
+ * Source and target may be the same image and may have different cameras.  Poses, cameras, occlusion geometry, the occlusion depth
+ * threshold and the min / max occlusion depths are used as e3d_reg_count_scan_observations uses them.
+ * Errors (negative return, e3d_last_error): null handle, source_mask or mask_out; no scan points set; target before source; unknown
+ * image (E3D_ERR_INDEX); an image of another rank; a mask value other than 0 / 1 / 2 in either mask (a source call that fails leaves
+ * no labels).  No scan points (n = 0) is not an error: 0 labels, mask_out = existing_mask or zeros. */
+int64_t e3d_reg_mask_transfer_source(e3d_reg_t* reg, int source_image_id, const uint8_t* source_mask, int transfer_eval_obs);
+int e3d_reg_mask_transfer_target(e3d_reg_t* reg, int target_image_id, const uint8_t* existing_mask, uint8_t* mask_out, int64_t* stats);
 /* Observations cache (src/opt/observations_cache.{h,cc}; Optimizer::set_cache_observations, optimizer.h).  When enabled, the
  * observation update re-projects a fixed per-image list of point indices with the current state and applies only the
  * scale-fit and border tests (VisibilityEstimator::AppendObservationsForIndexedPointsVisibleInImage,
