@@ -932,7 +932,9 @@ __device__ __forceinline__ bool obs_eval_one(const float4 p, const Pose& P, cons
   const float radius_pixels = sqrtf(dx * dx + dy * dy);
   const float observation_scale = q.image_scale + e3d_log2f(2 * radius_pixels);
   const int lo = max(Y.min_image_scale, q.current_image_scale);
-  if (!(observation_scale >= lo && f2i(observation_scale) < q.image_scale_count - 1)) return false;
+  // (a float comparison, not the reference's truncated one: the same decision for every finite scale >= lo >= 0, and it keeps out
+  // +inf -- the radius twin of a point just inside the cut-off radius projects to infinity -- which f2i turns into INT_MIN)
+  if (!(observation_scale >= lo && observation_scale < (float)(q.image_scale_count - 1))) return false;
   const int small_scale = f2i(observation_scale) + 1;
   int li = small_scale - Y.min_image_scale;
   if (li < 0) li = 0;
@@ -4259,6 +4261,8 @@ int64_t e3d_reg_observe(e3d_reg_t* h, int image_id, int point_scale, int image_s
                         size_t n_indices) {
   E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  // (0 is legal -- the multi-resolution radius code uses it; a negative border would let a position outside the level pass the border test)
+  if (border_size < 0) throw Error(E3D_ERR_INVALID, "negative border size");
   return (int64_t)observe(h, image_id, point_scale, image_scale, border_size, indices, n_indices);
   E3D_CATCH()
 }
@@ -4829,6 +4833,7 @@ int e3d_reg_scan_colors_finish(e3d_reg_t* h, uint8_t* rgb) {
 int e3d_reg_update_observations(e3d_reg_t* h, int border_size) {
   E3D_TRY_ON(h)
   if (!h) throw Error(E3D_ERR_INVALID, "null handle");
+  if (border_size < 0) throw Error(E3D_ERR_INVALID, "negative border size");
   update_observations(h, border_size);
   return 0;
   E3D_CATCH()

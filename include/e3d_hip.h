@@ -451,7 +451,8 @@ int e3d_reg_profile(e3d_reg_t* reg, int enable, char* out, size_t capacity);
 int e3d_reg_render_depth(e3d_reg_t* reg, int image_id, int image_scale, float* depth_out);
 /* Creates the observations of a point scale in an image (indices == NULL: every point, with occlusion, mask and
  * over-saturation tests against the last rendered depth map of this image and scale; indices != NULL: the given
- * visibility list without those tests) in point order, and their all-neighbours-observed flags.  Returns the count. */
+ * visibility list without those tests) in point order, and their all-neighbours-observed flags.  Returns the count.
+ * border_size >= 0 (E3D_ERR_INVALID otherwise, here and in e3d_reg_update_observations). */
 int64_t e3d_reg_observe(e3d_reg_t* reg, int image_id, int point_scale, int image_scale, int border_size,
                         const uint32_t* indices, size_t n_indices);
 int e3d_reg_get_observations(e3d_reg_t* reg, int image_id, int point_scale, uint32_t* point_index, float* x, float* y,

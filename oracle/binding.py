@@ -20,15 +20,24 @@ def variant():
 
 
 def build(force=False):
-    """Compile the oracle with gcc (Makefile in this directory)."""
+    """Compile the oracle with gcc (Makefile in this directory).  Several processes may get here at once with a library that is
+    older than its sources (the ranks of a multi-process test started before anything loaded the oracle): one of them builds under
+    an exclusive lock, the others wait and find it up to date.  The Makefile moves a finished library into place, so a reader
+    never meets a half-written one either."""
     glibc = variant() == "glibc"
     so = os.path.join(_HERE, "libe3d_oracle_glibc.so" if glibc else "libe3d_oracle.so")
-    if force or not os.path.exists(so) or any(
-        os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(so)
-        for f in os.listdir(_HERE) if f.endswith((".c", ".h", ".cc"))
-    ):
-        subprocess.check_call(["make", "-C", _HERE, "-s"] + (["glibc"] if glibc else []))
-    build_ref()
+
+    def stale():
+        return force or not os.path.exists(so) or any(
+            os.path.getmtime(os.path.join(_HERE, f)) > os.path.getmtime(so)
+            for f in os.listdir(_HERE) if f.endswith((".c", ".h", ".cc")))
+    if stale() or os.path.exists("/root/reference/src/opt/robust_weighting.h"):
+        import fcntl
+        with open(os.path.join(_HERE, ".build.lock"), "w") as lock:
+            fcntl.flock(lock, fcntl.LOCK_EX)
+            if stale():
+                subprocess.check_call(["make", "-C", _HERE, "-s"] + (["glibc"] if glibc else []))
+            build_ref()
     return so
 
 

@@ -202,7 +202,9 @@ size_t oracle_reg_observe(const float* pts, size_t n_pts, float point_radius, co
     const float radius_pixels = sqrtf(dx * dx + dy * dy);
     const float observation_scale = image_scale + om_log2f(2 * radius_pixels);
     const int lo = min_image_scale > current_image_scale ? min_image_scale : current_image_scale;
-    if (!(observation_scale >= lo && f2i(observation_scale) < image_scale_count - 1)) continue;
+    /* a float comparison, not the reference's truncated one: the same decision for every finite scale >= lo >= 0, and it keeps
+     * out +inf (the radius twin of a point just inside the cut-off radius projects to infinity), which f2i turns into INT_MIN */
+    if (!(observation_scale >= lo && observation_scale < (float)(image_scale_count - 1))) continue;
     const int small_scale = f2i(observation_scale) + 1;
     int li = small_scale - min_image_scale; if (li < 0) li = 0;
     if (li >= n_levels) continue;   /* cannot happen for consistent inputs (image_scale_count bounds it) */

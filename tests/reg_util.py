@@ -1,4 +1,6 @@
 """Shared helpers for the path-(B) tests: image pyramids and a small synthetic registration scene."""
+import functools
+
 import numpy as np
 
 
@@ -198,6 +200,162 @@ def make_reg_scene(n_points=6000, width=320, height=240, n_levels=4, K=5, seed=0
     obs_counts = rng.randint(0, 4, n_points).astype(np.int32)
     return dict(pts=pts, nbr=nbr, K=K, pyr=pyr, R=R, q=q, t=t, params=params, width=width, height=height, n_levels=n_levels,
                 fixed_desc=fixed_desc, var_desc=var_desc, obs_counts=obs_counts, point_radius=0.012, model=model)
+
+
+def pad_to_levels(levels_arrays, camera_levels):
+    """The level sizes of a loaded image (csrc/host/opt_problem.h, InitializeImages): the camera pyramid rounds up (ScaledBy,
+    int(0.5 w + 0.5)), the image pyramid truncates (int(0.5 cols)); where they differ the image level is edge-padded to the camera
+    level's size: out(y, x) = in(min(y, rows - 1), min(x, cols - 1)).  Masks get the same padding."""
+    out = []
+    for a, cam in zip(levels_arrays, camera_levels):
+        a = np.ascontiguousarray(a)
+        ys = np.minimum(np.arange(cam.height), a.shape[0] - 1); xs = np.minimum(np.arange(cam.width), a.shape[1] - 1)
+        out.append(np.ascontiguousarray(a[np.ix_(ys, xs)]))
+    return out
+
+
+def camera_space(S, pts=None):
+    """f32 camera-space coordinates R p + t of the scene's points (what the straddle test of the frustum scene is decided on)."""
+    p = S["pts"] if pts is None else pts
+    return (p.astype(np.float32) @ S["R"].astype(np.float32).T + S["t"].astype(np.float32)).astype(np.float32)
+
+
+def cutoff_straddlers(S, cam, cam_pts=None):
+    """Points inside the camera's cut-off radius whose radius twin (X + point_radius, Y, Z) lies outside it, decided in f32 from
+    X / Z, Y / Z as NormalizedToImage / the fisheye Distort decide it (r^2 > cutoff2, atan(r)^2 > inner_cutoff2)."""
+    c = camera_space(S) if cam_pts is None else cam_pts
+    with np.errstate(all="ignore"):
+        def outside(x):
+            nx, ny = x / c[:, 2], c[:, 1] / c[:, 2]
+            r2 = (nx * nx + ny * ny).astype(np.float32)
+            at = np.arctan(np.sqrt(r2)).astype(np.float32)
+            return (r2 > np.float32(cam.cutoff2)) | ((at * at).astype(np.float32) > np.float32(cam.inner_cutoff2))
+        return (c[:, 2] > 0) & ~outside(c[:, 0]) & outside((c[:, 0] + np.float32(S["point_radius"])).astype(np.float32))
+
+
+def _seeded_straddlers(rb, cam, point_radius, rng, want=40):
+    """Camera-space points at the scene's nearest depth, a fraction of the twin offset inside the cut-off radius, at the places
+    straddle_spots finds (with these cameras: a few pixels in the right-hand corners, since the distorted radius is largest at the
+    cut-off); each at least 1 px inside level 0 with its twin outside the radius.  None where straddle_spots finds no place."""
+    rc = cutoff_radius(cam)
+    spots = straddle_spots(rb, cam, point_radius)
+    out = []
+    for _ in range(4000 if spots else 0):
+        if len(out) >= want:
+            break
+        phi, s = spots[rng.randint(len(spots))]
+        phi += rng.uniform(-0.5, 0.5) * (2 * np.pi / 720); Z = rng.uniform(FRUSTUM_Z_MIN, 1.05 * FRUSTUM_Z_MIN)
+        P = np.array([rc * np.cos(phi) * Z - s * point_radius, rc * np.sin(phi) * Z, Z])       # the twin ends (1 - s) radius outside along x
+        if (P[0] / Z) ** 2 + (P[1] / Z) ** 2 >= rc * rc * (1 - 1e-4) or ((P[0] + point_radius) / Z) ** 2 + (P[1] / Z) ** 2 <= rc * rc * (1 + 1e-4):
+            continue
+        ip = rb.cam_project(cam, P.astype(np.float32))
+        if np.isfinite(ip).all() and 1.05 <= ip[0] <= cam.width - 2.05 and 1.05 <= ip[1] <= cam.height - 2.05:
+            out.append(P)
+    return np.array(out).reshape(-1, 3)
+
+
+FRUSTUM_Z_MIN = 0.3       # nearest depth of the frustum scene: the widest twin offset point_radius / Z in the normalized plane
+
+
+def cutoff_radius(cam):
+    """Radius of the cut-off circle in the normalized plane (inf: no cut-off, or a fisheye one beyond atan's range)."""
+    if np.isfinite(cam.inner_cutoff2):
+        th = np.sqrt(cam.inner_cutoff2)
+        return np.tan(th) if th < 0.5 * np.pi - 1e-3 else np.inf
+    return np.sqrt(cam.cutoff2)
+
+
+def straddle_spots(rb, cam, point_radius, steps=720):
+    """Where a point of the frustum scene can straddle the cut-off radius AND project at least 1 px inside the image (oracle
+    projection): (angle on the cut-off circle, fraction s of the twin offset by which the point lies inside it along x), for the widest
+    offset the scene has, point_radius / FRUSTUM_Z_MIN.  Empty: no point of such a cloud can, whatever its seed -- the cut-off circle
+    and the band inside it project outside the image, or the model has no reachable cut-off."""
+    rc = cutoff_radius(cam)
+    if not np.isfinite(rc):
+        return []
+    delta = point_radius / FRUSTUM_Z_MIN
+    out = []
+    for phi in np.linspace(-0.5 * np.pi, 0.5 * np.pi, steps // 2, endpoint=False):
+        for s in (0.15, 0.4, 0.65, 0.9):
+            nx, ny = rc * np.cos(phi) - s * delta, rc * np.sin(phi)
+            if nx * nx + ny * ny >= rc * rc or (nx + delta) ** 2 + ny * ny <= rc * rc:
+                continue
+            ip = rb.cam_project(cam, np.array([nx, ny, 1.0], np.float32))
+            if np.isfinite(ip).all() and 1 <= ip[0] <= cam.width - 2 and 1 <= ip[1] <= cam.height - 2:
+                out.append((phi, s))
+    return out
+
+
+@functools.lru_cache(maxsize=8)
+def _frustum_cloud(W, H, n_points, seed, K):
+    """The random part of the frustum scene (the same for every camera model): pose, world points, their K nearest neighbours, the tree."""
+    from scipy.spatial import cKDTree
+    rng = np.random.RandomState(seed)
+    fx = 0.8 * W; fy = 0.98 * fx
+    Z = np.exp(rng.uniform(np.log(FRUSTUM_Z_MIN), np.log(40.0), n_points))
+    X = rng.uniform(-1.25, 1.25, n_points) * (W / 2) / fx * Z
+    Y = rng.uniform(-1.25, 1.25, n_points) * (H / 2) / fy * Z
+    n_behind = n_points // 20
+    Z[:n_behind] *= -1
+    Z[n_behind:n_behind + 50] = 0
+    cam_pts = np.stack([X, Y, Z], 1)
+    R0, t = look_at_pose((0.1, -0.4, 0.05), (0, 3, 0))
+    q = quat_from_R(R0)
+    R = quat_to_R(q)          # so3().matrix() of the stored quaternion: what both implementations actually use
+    pts = ((cam_pts - t.astype(np.float64)) @ R.astype(np.float64)).astype(np.float32)
+    tree = cKDTree(pts)
+    nbr = tree.query(pts, k=K + 1)[1][:, 1:].astype(np.uint32)
+    for a in (R, q, t, pts, nbr):
+        a.setflags(write=False)
+    return R, q, t, pts, nbr, tree
+
+
+def make_frustum_scene(model, width, height, n_levels, min_image_scale, image_scale_count, n_points=40000, seed=5, K=5, splat_stride=128):
+    """A cloud that fills more than the camera's frustum, for the branches make_reg_scene never takes: depths 0.3 .. 40 m (log-uniform:
+    observation scales from far below 0 to above the coarsest level), positions up to 1.25 x the half image size (outside the
+    image, at its borders, beyond the cut-off radius of the distorted models), 5 % of the points behind the camera and 50 in its
+    plane, an over-saturated block, odd image sizes at every halving (the image levels are edge-padded to the camera levels) and a
+    camera whose pyramid starts at `min_image_scale`.  Points straddling the cut-off radius (inside, radius twin outside) are added
+    near the right-hand corners where they can project into the image (straddle_spots).  Same keys as make_reg_scene, plus
+    `min_image_scale` and `image_scale_count`; `pyr` and every mask pyramid made with frustum_mask_pyramid have the camera levels'
+    sizes.  `splat_pts` is every `splat_stride`-th point: the occluding geometry for the splat depth map.  (The whole cloud as
+    occluders hides everything: a tenth of it lies within 0.8 m, where a 3 cm splat is the 21 x 21 pixel maximum.)"""
+    from oracle import reg_binding as rb
+    assert n_levels == image_scale_count - min_image_scale
+    W, H = width, height
+    fx = 0.8 * W; fy = 0.98 * fx; cx = W / 2 - 0.3; cy = H / 2 + 0.2
+    params = camera_params(model, fx, fy, cx, cy)
+    levels = rb.camera_pyramid(rb.make_camera(W, H, params, model), n_levels)
+    point_radius = 0.012
+    R, q, t, cloud, cloud_nbr, tree = _frustum_cloud(W, H, n_points, seed, K)
+    # the straddling points come last and find their neighbours in the random cloud (any fixed neighbour graph works for the kernels)
+    rng = np.random.RandomState(seed + 1)
+    extra = _seeded_straddlers(rb, levels[0], point_radius, rng)
+    extra = ((extra - t.astype(np.float64)) @ R.astype(np.float64)).astype(np.float32)
+    pts = np.concatenate([cloud, extra])
+    nbr = np.concatenate([cloud_nbr, tree.query(extra, k=K)[1].reshape(-1, K).astype(np.uint32)])
+    n = len(pts)
+    yy, xx = np.mgrid[0:H, 0:W]
+    img = (110 + 60 * np.sin(xx / 9.0) * np.cos(yy / 7.0) + 40 * np.sin((xx + 2 * yy) / 23.0)).clip(0, 250)
+    img = img.astype(np.uint8)
+    img[:H // 5, :W // 5] = 255                               # an over-saturated block
+    pyr = pad_to_levels(pyramid_u8(img, n_levels), levels)
+    fixed_desc = rng.normal(0, 8, (n, K)).astype(np.float32)
+    var_desc = rng.normal(0, 8, (n, K)).astype(np.float32)
+    obs_counts = rng.randint(0, 4, n).astype(np.int32)
+    return dict(pts=pts, nbr=nbr, K=K, pyr=pyr, R=R, q=q, t=t, params=params, width=W, height=H, n_levels=n_levels,
+                fixed_desc=fixed_desc, var_desc=var_desc, obs_counts=obs_counts, point_radius=point_radius, model=model,
+                min_image_scale=min_image_scale, image_scale_count=image_scale_count, splat_pts=np.ascontiguousarray(pts[::splat_stride]))
+
+
+def frustum_mask_pyramid(S, mask):
+    """Image::BuildMaskPyramid (2 x 2 OR, odd trailing rows / columns dropped) of a level-0 mask, padded to the camera levels."""
+    from oracle import reg_binding as rb
+    masks = [np.ascontiguousarray(mask, np.uint8)]
+    for _ in range(1, S["n_levels"]):
+        m = masks[-1]; h, w = (m.shape[0] // 2) * 2, (m.shape[1] // 2) * 2
+        masks.append(m[0:h:2, 0:w:2] | m[0:h:2, 1:w:2] | m[1:h:2, 0:w:2] | m[1:h:2, 1:w:2])
+    return pad_to_levels(masks, rb.camera_pyramid(rb.make_camera(S["width"], S["height"], S["params"], S["model"]), S["n_levels"]))
 
 
 def make_rig_scene(n_points=6000, n_frames=2, width=240, height=180, n_levels=3, K=5, seed=0, perturb=0.004, model=0):

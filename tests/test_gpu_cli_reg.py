@@ -24,7 +24,8 @@ def _write_png(path, img):
     Image.fromarray(np.ascontiguousarray(img, np.uint8), mode="L").save(path)
 
 
-def _write_dataset(tmp, M, names, rigs=None, model_name="PINHOLE"):
+def _write_dataset(tmp, M, names, rigs=None, model_name="PINHOLE", second=None):
+    """second = (M2, names2): a second camera (id 8) of its own size with its own images, same scan."""
     from tools.make_multires_cache import write_cache
     d = str(tmp)
     write_ply_xyz(os.path.join(d, "scan.ply"), M["pts"], rgb=np.full((len(M["pts"]), 3), 128, np.uint8))
@@ -35,11 +36,17 @@ def _write_dataset(tmp, M, names, rigs=None, model_name="PINHOLE"):
     p = M["params"].astype(np.float64).copy(); p[ci] += 0.5; p[ci + 1] += 0.5   # COLMAP's pixel-corner convention
     with open(os.path.join(d, "state", "cameras.txt"), "w") as f:
         f.write("# cameras\n7 %s %d %d %s\n" % (model_name, M["width"], M["height"], " ".join("%.9g" % v for v in p)))
+        if second is not None:
+            p2 = second[0]["params"].astype(np.float64).copy(); p2[ci] += 0.5; p2[ci + 1] += 0.5
+            f.write("8 %s %d %d %s\n" % (model_name, second[0]["width"], second[0]["height"], " ".join("%.9g" % v for v in p2)))
     with open(os.path.join(d, "state", "images.txt"), "w") as f:
         f.write("# images\n")
         for i, (im, name) in enumerate(zip(M["images"], names)):
             q, t = im.get("q_init", im.get("q_true")), im.get("t_init", im.get("t_true"))
             f.write("%d %s %s 7 %s\n\n" % (10 + i, " ".join("%.9g" % v for v in q), " ".join("%.9g" % v for v in t), name))
+            _write_png(os.path.join(d, "images", name), im["pyr"][0])
+        for i, (im, name) in enumerate(zip(*(second[0]["images"], second[1]) if second is not None else ((), ()))):
+            f.write("%d %s %s 8 %s\n\n" % (10 + len(names) + i, " ".join("%.9g" % v for v in im["q_init"]), " ".join("%.9g" % v for v in im["t_init"]), name))
             _write_png(os.path.join(d, "images", name), im["pyr"][0])
     if rigs is not None:
         import json
@@ -65,11 +72,11 @@ def _point_scales(M):
     return out
 
 
-def _run_tool(d, extra=()):
+def _run_tool(d, extra=(), area=3000):
     cmd = [os.path.join(BIN, "ImageRegistrator"), "--scan_alignment_path", os.path.join(d, "scans.mlp"), "--multi_res_point_cloud_directory_path",
            os.path.join(d, "cache"), "--image_base_path", os.path.join(d, "images"), "--state_path", os.path.join(d, "state"),
            "--output_folder_path", os.path.join(d, "out"), "--observations_cache_path", os.path.join(d, "obs_cache"),
-           "--max_iterations", "4", "--max_initial_image_area_in_pixels", "3000"] + list(extra)
+           "--max_iterations", "4", "--max_initial_image_area_in_pixels", str(area)] + list(extra)
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return r.stdout
@@ -155,6 +162,50 @@ def test_image_registrator_cli_matches_binding(tmp_path, e3d):
                                os.path.join(d, "obs_cache"), "--max_iterations", "2", "--max_initial_image_area_in_pixels", "3000",
                                "--cache_observations", "1"], capture_output=True, text=True, timeout=600)
     assert cmd_fail.returncode != 0 and "Missing file for observed point indices" in cmd_fail.stderr
+
+
+def test_image_registrator_cli_two_camera_sizes(tmp_path, e3d):
+    """Two cameras of different size in one dataset, 640 x 480 and 320 x 240: with the default initial image area (200 x 160) they have
+    3 and 2 image scales (Intrinsics::ComputeImageScaleCount), so the problem has 3 and the small camera gets min_image_scale 1
+    (problem.cc:487-493) -- the usual DSLR-plus-rig setting.  The tool's optimum equals the binding's driven the same way."""
+    from reg_util import pyramid_u8
+    big = make_multi_image_scene(n_points=6000, n_images=4, width=640, height=480, seed=12, perturb=0.006)
+    small = make_multi_image_scene(n_points=6000, n_images=4, width=320, height=240, seed=12, perturb=0.006)
+    assert np.array_equal(big["pts"], small["pts"])
+    big["images"] = big["images"][:2]; small["images"] = small["images"][2:]
+    names = ["dslr/img_%d.png" % i for i in range(2)]; names2 = ["rig/img_%d.png" % i for i in range(2, 4)]
+    d = _write_dataset(tmp_path, big, names, second=(small, names2))
+    out = _run_tool(d, area=200 * 160)
+    assert "#Image scales: 3" in out and "--- Optimizing at scaling factor 0.5 ---" in out and "Finished!" in out
+    G = e3d.RegProblem(e3d.default_reg_params(image_scale_count=3, point_neighbor_count=big["K"]))
+    G.set_intrinsics(0, big["width"], big["height"], big["params"], 0, 3)
+    G.set_intrinsics(1, small["width"], small["height"], small["params"], 1, 2)
+    for s_i, sc in enumerate(_point_scales(big)):
+        G.set_point_scale(s_i, sc["pts"], sc["radius"], sc["nbr"], sc["fixed"])
+    G.set_splat_points(big["pts"])
+    for i, im in enumerate(big["images"] + small["images"]):
+        G.set_image(i, i // 2, pyramid_u8(im["pyr"][0], 3 - i // 2)); G.set_image_pose(i, im["q_init"], im["t_init"])
+    for scale in (1, 0):
+        prm = G.params; prm.current_image_scale = scale; G.set_params(prm)
+        G.set_cache_observations(scale != 1)           # enabled after the first scale (image_registrator.cc:230-235)
+        cost = G.run_on_current_scale(4, 0.0, 15, False)[1]
+        folder = os.path.join(d, "out", "scale_%s_state" % ("0.5" if scale == 1 else "1"))
+        meta = open(os.path.join(folder, "metadata.txt")).read()
+        assert np.isfinite(cost) and abs(float(meta.strip().split("optimum_cost ")[1]) - cost) <= 1e-4 * cost
+        st = _read_images_txt(os.path.join(folder, "images.txt"))
+        assert sorted(st) == [0, 1, 2, 3]
+        for i in range(4):
+            q, t = G.get_image_pose(i)
+            assert np.abs(st[i][0] - q).max() <= 2e-5 and np.abs(st[i][1] - t).max() <= 2e-5 and st[i][3] == (names + names2)[i]
+        assert st[0][2] == st[1][2] != st[2][2] == st[3][2]
+        cams = [l.split() for l in open(os.path.join(folder, "cameras.txt")) if l.strip() and not l.startswith("#")]
+        assert len(cams) == 2
+        for cam in cams:
+            iid = [st[0][2], st[2][2]].index(int(cam[0]))
+            M = (big, small)[iid]
+            p = G.intrinsics_level(iid, 0)[2].astype(np.float64); p[2] += 0.5; p[3] += 0.5
+            assert cam[1:4] == ["PINHOLE", str(M["width"]), str(M["height"])]
+            assert np.abs(np.array(cam[4:], np.float64) - p).max() <= 2e-3
 
 
 def test_image_registrator_cli_camera_and_image_masks(tmp_path, e3d):

@@ -187,7 +187,7 @@ def test_color_update(e3d, rb):
     assert np.array_equal(c, co) and np.array_equal(d.view(np.uint32), do.view(np.uint32))
 
 
-def test_reg_errors(e3d):
+def test_reg_errors(e3d, rb):
     P = e3d.RegProblem()
     with pytest.raises(e3d.E3DError):
         P.observe(0, 0, 0, 1)
@@ -195,6 +195,20 @@ def test_reg_errors(e3d):
         P.set_intrinsics(0, 64, 48, [50, 50, 32, 24, 0.1, 0, 0, 0], 0, 2, camera_type=2)   # THIN_PRISM_FISHEYE takes 12 parameters
     with pytest.raises(e3d.E3DError):
         P.set_intrinsics(0, 64, 48, [50, 50, 32, 24], 0, 2, camera_type=7)
+    # a negative border size is refused by both entry points that take one (it would let a position outside the level pass the
+    # border test); border 0 stays legal, and the handle works after the refusals
+    S = make_reg_scene(n_points=2000, seed=6)
+    P, levels = _setup(e3d, rb, S)
+    P.render_depth(0, 0)
+    with pytest.raises(e3d.E3DError, match="negative border"):
+        P.observe(0, 0, 0, -1)
+    with pytest.raises(e3d.E3DError, match="negative border"):
+        P.observe(0, 0, 0, -1, indices=np.arange(10, dtype=np.uint32))
+    with pytest.raises(e3d.E3DError, match="negative border"):
+        P.update_observations(-1)
+    n0 = P.observe(0, 0, 0, 0)
+    assert n0 >= P.observe(0, 0, 0, 1) > 1000
+    P.update_observations(0)
 
 
 # ---- optimizer driver (Optimizer::RunOnCurrentScale / IntrinsicsAndPoseOptimizer::Apply) ---------------------------------------

@@ -169,6 +169,40 @@ def test_observations_and_flags(rb):
     assert np.array_equal(obs2[0], oi) and np.array_equal(obs2[1], ox) and np.array_equal(obs2[3], os_)
 
 
+def test_point_straddling_the_cutoff_is_no_observation(rb):
+    """A point just inside the cut-off radius of an OPENCV camera whose radius twin (X + point_radius, Y, Z) lies just outside it:
+    the twin projects to infinity, so the observation scale is +inf.  The reference truncates it to int before the scale test
+    (visibility_estimator.cc:450-483; undefined behaviour, INT_MIN on x86, which passes) and then indexes the image pyramid with it;
+    here the scale test compares floats and the point is no observation -- alone and inside a cloud, in the all-points pass (with
+    and without masks) and in the indexed one."""
+    from reg_util import camera_params, cutoff_straddlers, pad_to_levels
+    W, H, n_levels = 323, 243, 4
+    params = camera_params(1, 258.4, 253.232, 161.2, 121.7)
+    levels = rb.camera_pyramid(rb.make_camera(W, H, params, 1), n_levels)
+    assert abs(levels[0].cutoff2 - 0.67482) < 1e-4
+    point = np.array([[0.27621, -0.21209, 0.43176]], np.float32)
+    radius = 0.012
+    R = np.eye(3, dtype=np.float32); t = np.zeros(3, np.float32)
+    S = dict(pts=point, R=R, t=t, point_radius=radius)
+    assert cutoff_straddlers(S, levels[0]).all()                          # r^2 = 0.6505 inside, the twin's 0.6869 outside
+    ip = rb.cam_project(levels[0], point[0])
+    assert 1 <= ip[0] <= W - 2 and 1 <= ip[1] <= H - 2                    # and it projects into the image
+    pyr = pad_to_levels(pyramid_u8(np.full((H, W), 100, np.uint8), n_levels), levels)
+    masks = [np.zeros_like(p) for p in pyr]
+    rng = np.random.RandomState(0)
+    z = rng.uniform(1.5, 4.0, 1000)
+    cloud = np.stack([rng.uniform(-0.5, 0.5, 1000) * z, rng.uniform(-0.35, 0.35, 1000) * z, z], 1).astype(np.float32)
+    cloud[500] = point[0]
+    for pts, idx in ((point, 0), (cloud, 500)):
+        depth = rb.splat_depth(pts, R, t, levels[0], 0.03)
+        for m in (None, masks):
+            o = rb.observe(pts, radius, R, t, levels, 0, pyr, m, depth, 0, 1, 0, n_levels)
+            assert idx not in o[0] and np.isfinite(o[3]).all()
+            assert len(o[0]) == 0 if len(pts) == 1 else len(o[0]) > 500
+        o2 = rb.observe(pts, radius, R, t, levels, 0, pyr, None, None, 0, 1, 0, n_levels, indices=np.arange(len(pts), dtype=np.uint32))
+        assert idx not in o2[0] and np.isfinite(o2[3]).all()
+
+
 def test_accumulate_matches_cost_and_is_consistent(rb):
     S = make_reg_scene(seed=3)
     levels, depth, obs, flags = _scene_obs(rb, S)
