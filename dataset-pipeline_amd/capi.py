@@ -155,6 +155,20 @@ SIGNATURES = {
                                       C.c_float, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_render_cube_map": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_cube_map_timings": (C.c_int, [C.c_void_p]),
+    # PointCloudEditor: selections and edits of one object's points
+    "e3d_edit_create": (C.c_void_p, [C.c_void_p, C.c_size_t]),
+    "e3d_edit_destroy": (None, [C.c_void_p]),
+    "e3d_edit_size": (C.c_int64, [C.c_void_p]),
+    "e3d_edit_get_points": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_edit_get_selection": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_edit_set_selection": (C.c_int64, [C.c_void_p, C.c_void_p]),
+    "e3d_edit_selection_count": (C.c_int64, [C.c_void_p]),
+    "e3d_edit_lasso": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
+    "e3d_edit_beyond_plane": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "e3d_edit_pick": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
+    "e3d_edit_delete_selected": (C.c_int64, [C.c_void_p]),
+    "e3d_edit_extract_selected": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_size_t]),
+    "e3d_edit_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
 }
 
 
@@ -546,6 +560,112 @@ def render_cube_map(xyz, rgb, size, fill=True, timings=None):
         timings.update(points_ms=float(tm[0]), resolve_ms=float(tm[1]), fill_ms=float(tm[2]), dilation_ms=float(tm[3]),
                        batches=int(tm[4]), sweeps_launched=int(tm[5]))
     return color, depth, sweeps
+
+
+# ---- PointCloudEditor --------------------------------------------------------------------------------------------------
+class EditView(C.Structure):
+    """e3d_view -- the editor's view: pinhole camera, camera_T_object (row-major 3 x 4, rotation * scale | translation), depth range."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("camera_T_object", C.c_float * 12), ("min_depth", C.c_float), ("max_depth", C.c_float)]
+
+
+def edit_view(width, height, camera_T_object=None, min_depth=0.1, max_depth=100.0, fx=None, fy=None, cx=None, cy=None):
+    """An EditView; the intrinsics default to RenderWidget::SetFreeOrbitViewport's (fx = fy = height, principal point at the centre)."""
+    T = np.eye(4, dtype=np.float32)[:3] if camera_T_object is None else _pose12(camera_T_object)
+    return EditView(int(width), int(height), float(height if fx is None else fx), float(height if fy is None else fy),
+                    float(np.float32(0.5 * width - 0.5) if cx is None else cx), float(np.float32(0.5 * height - 0.5) if cy is None else cy),
+                    (C.c_float * 12)(*[float(v) for v in T.ravel()]), float(min_depth), float(max_depth))
+
+
+class PointCloudEdit:
+    """One object's points and their selection on the device (include/e3d_hip.h: e3d_edit_*) -- the PointCloudEditor's lasso,
+    beyond-plane selection, picking, delete and move.  Colours, labels and faces stay with the caller."""
+    REPLACE, ADD, REMOVE = 0, 1, 2
+    _MODES = {"replace": 0, "add": 1, "remove": 2}
+
+    def __init__(self, xyz):
+        keep = []
+        n = int(xyz.shape[0])
+        self._h = lib().e3d_edit_create(_ptr(xyz, np.float32, keep) if n else None, n)
+        if not self._h:
+            _err("e3d_edit_create")
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h:
+            lib().e3d_edit_destroy(h)
+            self._h = None
+
+    def _chk(self, r, what):
+        if r < 0:
+            _err(what, r)
+        return int(r)
+
+    def __len__(self):
+        return self._chk(lib().e3d_edit_size(self._h), "e3d_edit_size")
+
+    def points(self):
+        out = np.zeros((len(self), 3), np.float32)
+        self._chk(lib().e3d_edit_get_points(self._h, C.c_void_p(out.ctypes.data)), "e3d_edit_get_points")
+        return out
+
+    def selection(self):
+        """bool flag per point."""
+        out = np.zeros(len(self), np.uint8)
+        self._chk(lib().e3d_edit_get_selection(self._h, C.c_void_p(out.ctypes.data)), "e3d_edit_get_selection")
+        return out.astype(bool)
+
+    def set_selection(self, flags):
+        keep = []
+        flags = np.ascontiguousarray(flags).astype(np.uint8) if not _is_torch(flags) else flags
+        if int(flags.shape[0]) != len(self):
+            raise E3DError("set_selection: %d flags for %d points" % (int(flags.shape[0]), len(self)))
+        return self._chk(lib().e3d_edit_set_selection(self._h, _ptr(flags, np.uint8, keep)), "e3d_edit_set_selection")
+
+    def selection_count(self):
+        return self._chk(lib().e3d_edit_selection_count(self._h), "e3d_edit_selection_count")
+
+    def lasso(self, view, polygon, mode="replace", depth=None):
+        """polygon: (m, 2) pixel positions, not closed.  depth: (height, width) f32 rendering of the object, for meshes.
+        Returns the number of selected points."""
+        keep = []
+        poly = np.ascontiguousarray(polygon, np.float64).reshape(-1, 2)
+        if depth is not None and tuple(depth.shape) != (view.height, view.width):
+            raise E3DError("lasso: depth image %s for a %d x %d view" % (tuple(depth.shape), view.width, view.height))
+        return self._chk(lib().e3d_edit_lasso(self._h, C.byref(view), C.c_void_p(poly.ctypes.data), poly.shape[0], self._MODES.get(mode, mode),
+                                              _ptr(depth, np.float32, keep)), "e3d_edit_lasso")
+
+    def beyond_plane(self, view, points, camera_position_object, limit_to_visible=False):
+        """points: (3, 3), the plane; the side of camera_position_object stays unselected.  Returns the number of selected points."""
+        p = np.ascontiguousarray(points, np.float32).reshape(3, 3)
+        c = np.ascontiguousarray(camera_position_object, np.float32).reshape(3)
+        return self._chk(lib().e3d_edit_beyond_plane(self._h, C.byref(view), C.c_void_p(p.ctypes.data), C.c_void_p(c.ctypes.data),
+                                                     int(bool(limit_to_visible))), "e3d_edit_beyond_plane")
+
+    def pick(self, view, clicks):
+        """clicks: (m <= 8, 2) pixel positions -> (index[m] int64, -1 where no point is in range; squared pixel distance[m] f32)."""
+        ck = np.ascontiguousarray(clicks, np.float64).reshape(-1, 2)
+        idx = np.full(ck.shape[0], -1, np.int64)
+        d = np.full(ck.shape[0], np.inf, np.float32)
+        self._chk(lib().e3d_edit_pick(self._h, C.byref(view), C.c_void_p(ck.ctypes.data), ck.shape[0], C.c_void_p(idx.ctypes.data),
+                                      C.c_void_p(d.ctypes.data)), "e3d_edit_pick")
+        return idx, d
+
+    def delete_selected(self):
+        """Removes the selected points (the others keep their order) and clears the selection; returns the new point count."""
+        return self._chk(lib().e3d_edit_delete_selected(self._h), "e3d_edit_delete_selected")
+
+    def extract_selected(self):
+        """Coordinates of the selected points, in index order."""
+        m = self.selection_count()
+        out = np.zeros((m, 3), np.float32)
+        self._chk(lib().e3d_edit_extract_selected(self._h, C.c_void_p(out.ctypes.data), m), "e3d_edit_extract_selected")
+        return out
+
+    def kernel_ms(self):
+        ms = C.c_float(0)
+        self._chk(lib().e3d_edit_kernel_ms(self._h, C.byref(ms)), "e3d_edit_kernel_ms")
+        return ms.value
 
 
 # ---- (B) image registration kernels ------------------------------------------------------------------------------------

@@ -618,6 +618,90 @@ int e3d_reg_set_shard(e3d_reg_t* reg, int rank, int world_size, e3d_allreduce_fn
 int e3d_reg_set_comm(e3d_reg_t* reg, e3d_comm_t* comm);
 int e3d_reg_image_owner(e3d_reg_t* reg, int image_id);
 
+/* ---- PointCloudEditor (src/point_cloud_editor): selections and edits of one object's points --------------------------
+ * The GUI's lasso, beyond-plane selection, point picking, "delete" and "move" as batch operations.  An edit handle keeps one
+ * object's coordinates and its selection on the device for the whole session; a selection call is one pass over the points
+ * and one synchronisation (for the count it returns).  Colours, labels and faces stay with the caller, who compacts them with
+ * the flags fetched before a delete.
+ *
+ * Selection.  One byte per point, 0 or 1.  The reference keeps a list of indices (Scene::selected_point_indices), but every
+ * path leaves that list in ascending index order -- replace and beyond-plane push indices in point order, add sorts and
+ * removes duplicates, remove keeps the order -- so flags hold the same information, and "delete" / "move" / "label" visit the
+ * points in the same order.
+ *
+ * e3d_view: the GUI's view.  A pinhole camera (RenderWidget::SetFreeOrbitViewport makes fx = fy = height, cx = width / 2 - 0.5,
+ * cy = height / 2 - 0.5), camera_T_object as the row-major 3 x 4 [R * s | t] of the reference's Sim3 camera_RsT_object, and the
+ * depth range of the Near / Far sliders.  Per point, in f32 and in this order:
+ *     camera_point = ((r0 * x + r1 * y) + r2 * z) + t          (per row; Eigen's order, no contraction)
+ *     in range     = min_depth <= camera_point.z <= max_depth   (both ends inclusive; NaN is out of range)
+ *     pixel        = (fx * (camera_point.x / camera_point.z) + cx) + 0.5f, and the same in y */
+typedef struct e3d_edit e3d_edit_t;
+typedef struct e3d_view {
+  int32_t width, height;
+  float   fx, fy, cx, cy;
+  float   camera_T_object[12];
+  float   min_depth, max_depth;
+} e3d_view;
+#define E3D_EDIT_REPLACE 0
+#define E3D_EDIT_ADD     1
+#define E3D_EDIT_REMOVE  2
+#define E3D_EDIT_MAX_POLYGON 1024
+#define E3D_EDIT_MAX_CLICKS  8
+
+/* Uploads n points (n x 3 f32, host or device; n < 2^32, n == 0 is legal here and in every call below) with an empty
+ * selection; NULL on failure. */
+e3d_edit_t* e3d_edit_create(const float* xyz, size_t n);
+void e3d_edit_destroy(e3d_edit_t* edit);
+int64_t e3d_edit_size(e3d_edit_t* edit);                          /* the current number of points */
+int e3d_edit_get_points(e3d_edit_t* edit, float* xyz);            /* their coordinates, in order */
+/* The selection: n bytes out (0 / 1), n bytes in (any non-zero byte selects; returns the number selected), the number selected
+ * (kept on the host: no device work). */
+int e3d_edit_get_selection(e3d_edit_t* edit, uint8_t* flags);
+int64_t e3d_edit_set_selection(e3d_edit_t* edit, const uint8_t* flags);
+int64_t e3d_edit_selection_count(e3d_edit_t* edit);
+
+/* LassoSelectionTool::applySelection (tool_select_lasso.cc:104-230).  polygon_xy: n_vertices x 2 doubles in pixels, not closed
+ * (the library repeats the first vertex).  mode: E3D_EDIT_REPLACE / _ADD / _REMOVE.  A point in range whose pixel is inside the
+ * polygon is selected (added, removed).  Inside = odd-even rule over the closed polygon's edges in f64, the f32 pixel promoted:
+ * an edge with y1 == y2 is skipped; otherwise it is ordered so that y1 < y2 and counts if
+ *     y >= y1 && y < y2 && x1 + ((x2 - x1) / (y2 - y1)) * (y - y1) <= x.
+ * This is QPolygonF::containsPoint(..., Qt::OddEvenFill) with its qFuzzyCompare(y1, y2) replaced by exact equality.  For the
+ * polygons the GUI makes the two are the same test: mouse positions are integers, so |y1 - y2| >= 1 wherever y1 != y2, and with
+ * |y| < 10^12 Qt's fuzzy comparison (|y1 - y2| * 10^12 <= min(|y1|, |y2|)) is then false.
+ * Fewer than 3 vertices: nothing happens (:105) and the selection stays.  More than E3D_EDIT_MAX_POLYGON: an error.
+ * depth (optional; width x height f32, row-major, host or device): the visibility test of mesh vertices (:177-190).  The pixel
+ * is truncated to int (saturating), then clamped to the image; a vertex is not selected if the depth there is finite and
+ * < 0.99f * camera_point.z.  +-inf and NaN let it pass.
+ * Returns the number of selected points after the call. */
+int64_t e3d_edit_lasso(e3d_edit_t* edit, const e3d_view* view, const double* polygon_xy, int n_vertices, int mode,
+                       const float* depth);
+
+/* BeyondPlaneSelectionTool::PerformSelection (tool_select_beyond_plane.cc:43-102); always replaces the selection.  points: p0,
+ * p1, p2.  The plane as Eigen::Hyperplane<float, 3>::Through makes it, in f32: n = (p2 - p0) x (p1 - p0), divided by its norm,
+ * offset = -p0 . n; all four coefficients negated if the signed distance of camera_position_object is negative.  A point is
+ * selected if ((n.x * x + n.y * y) + n.z * z) + offset < 0 (a point on the plane and NaN are not), and with limit_to_visible
+ * only if it is also in range and 0 <= pixel.x < width, 0 <= pixel.y < height.
+ * Difference: where |n| <= |p2 - p0| * |p1 - p0| * FLT_EPSILON (three points on a line) Eigen fits a plane by SVD; here that is
+ * an error.  Returns the number of selected points. */
+int64_t e3d_edit_beyond_plane(e3d_edit_t* edit, const e3d_view* view, const float points[9],
+                              const float camera_position_object[3], int limit_to_visible);
+
+/* BeyondPlaneSelectionTool::mousePressEvent (:108-155) for up to E3D_EDIT_MAX_CLICKS clicks in one pass: per click (x, y
+ * doubles in pixels) the point in range with the smallest (float)(dx * dx + dy * dy), dx and dy in f64 (the f32 pixel promoted).
+ * The comparison is the reference's strict `<` starting from +inf: of equal distances the lowest index wins and a NaN or
+ * infinite distance never does.  index_out[c] = -1 (and distance_out[c] = +inf) if no point qualifies.  distance_out may be
+ * NULL. */
+int e3d_edit_pick(e3d_edit_t* edit, const e3d_view* view, const double* clicks_xy, int n_clicks, int64_t* index_out,
+                  float* distance_out);
+
+/* The Delete key (render_widget.cc:570-642): removes the selected points, keeping the order of the others, and clears the
+ * selection; returns the new number of points.  The "move" key (:677-732) is e3d_edit_extract_selected -- the selected points'
+ * coordinates in index order, capacity in points, returns their number -- followed by e3d_edit_delete_selected. */
+int64_t e3d_edit_delete_selected(e3d_edit_t* edit);
+int64_t e3d_edit_extract_selected(e3d_edit_t* edit, float* xyz_out, size_t capacity);
+/* HIP-event time of the kernels of the last selection, pick, extract or delete call on this handle, in ms. */
+int e3d_edit_kernel_ms(e3d_edit_t* edit, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
