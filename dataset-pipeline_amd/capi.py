@@ -132,6 +132,10 @@ SIGNATURES = {
     "e3d_reg_scan_rendering": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
     "e3d_reg_mask_transfer_source": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
     "e3d_reg_mask_transfer_target": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_reg_pick_scan_points": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_reg_image_bearings": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "e3d_reg_project_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "e3d_pose_from_bearings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_set_cache_observations": (C.c_int, [C.c_void_p, C.c_int]),
     "e3d_reg_determine_observed_indices": (C.c_int, [C.c_void_p]),
     "e3d_reg_get_observed_indices": (C.c_int64, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
@@ -697,6 +701,23 @@ def merge_close_points(merge_distance, num_scans, xyz, colors, scan_indices, max
     return ox[:m].copy(), oc[:m].copy(), osc[:m].copy(), om[:m].copy()
 
 
+def pose_from_bearings(points, bearings, q, t):
+    """Host only (no device needed): the pose image_T_global that minimises sum |f_i - (R p_i + t) / |R p_i + t||^2 over >= 6 pairs of
+    global points ((n, 3) float64) and unit bearings ((n, 3) float64), by Levenberg-Marquardt from (q, t) -> (q (4,) float32 unit, w >= 0;
+    t (3,) float32; stats = (RMS angle before, after, iterations, converged))."""
+    p = np.ascontiguousarray(points, np.float64).reshape(-1, 3); f = np.ascontiguousarray(bearings, np.float64).reshape(-1, 3)
+    if len(p) != len(f):
+        raise E3DError("pose_from_bearings: %d points, %d bearings" % (len(p), len(f)))
+    q = np.ascontiguousarray(q, np.float32); t = np.ascontiguousarray(t, np.float32)
+    assert q.shape == (4,) and t.shape == (3,)
+    qo = np.zeros(4, np.float32); to = np.zeros(3, np.float32); stats = np.zeros(4, np.float64)
+    r = lib().e3d_pose_from_bearings(C.c_void_p(p.ctypes.data), C.c_void_p(f.ctypes.data), len(p), C.c_void_p(q.ctypes.data), C.c_void_p(t.ctypes.data),
+                                     C.c_void_p(qo.ctypes.data), C.c_void_p(to.ctypes.data), C.c_void_p(stats.ctypes.data))
+    if r < 0:
+        _err("e3d_pose_from_bearings", r)
+    return qo, to, (float(stats[0]), float(stats[1]), int(stats[2]), bool(stats[3]))
+
+
 class RegParams(C.Structure):
     """e3d_reg_params -- the opt::Parameters fields the device code reads (src/opt/parameters.h:40-68)."""
     _fields_ = [("point_neighbor_count", C.c_int32), ("robust_weighting_type", C.c_int32),
@@ -937,6 +958,40 @@ class RegProblem:
         self._chk(lib().e3d_reg_mask_transfer_target(self._h, image_id, e, C.c_void_p(out.ctypes.data), C.c_void_p(stats.ctypes.data)),
                   "e3d_reg_mask_transfer_target")
         return (out, tuple(int(v) for v in stats)) if return_stats else out
+
+    # ---- ImageLocalizer (DatasetInspector "Localize image", localize_image_tool.cc) ------------------------------------------------
+    def pick_scan_points(self, image_id, clicks):
+        """The scan point nearest to each of 1 .. 32 clicks ((k, 2) float32, (0, 0) = centre of the top-left pixel) among the points
+        visible in image_id at its current pose -> (indices (k,) int64, -1 = none; pixels (k, 2) float32, the winners' unrounded
+        positions; squared distances (k,) float32, +inf = none; number of visible points)."""
+        clicks = np.ascontiguousarray(clicks, np.float32).reshape(-1, 2)
+        k = len(clicks)
+        index = np.zeros(k, np.int64); pixel = np.zeros((k, 2), np.float32); dist = np.zeros(k, np.float32)
+        visible = self._chk(lib().e3d_reg_pick_scan_points(self._h, int(image_id), C.c_void_p(clicks.ctypes.data), k, C.c_void_p(index.ctypes.data),
+                                                           C.c_void_p(pixel.ctypes.data), C.c_void_p(dist.ctypes.data)), "e3d_reg_pick_scan_points")
+        return index, pixel, dist, int(visible)
+
+    def image_bearings(self, image_id, pixels):
+        """Unit bearing vectors ((k, 3) float64, camera frame) of pixel positions ((k, 2) float32) of image_id's level-0 model."""
+        pixels = np.ascontiguousarray(pixels, np.float32).reshape(-1, 2)
+        out = np.zeros((len(pixels), 3), np.float64)
+        self._chk(lib().e3d_reg_image_bearings(self._h, int(image_id), C.c_void_p(pixels.ctypes.data), len(pixels), C.c_void_p(out.ctypes.data)),
+                  "e3d_reg_image_bearings")
+        return out
+
+    def project_points(self, image_id, xyz):
+        """Global points ((k, 3) float32) in image_id at its current pose -> (unrounded level-0 pixel positions (k, 2) float32, NaN behind
+        the camera; states (k,) uint8: 0 = behind the camera or outside the image, 1 = visible, 2 = behind the occlusion depth)."""
+        xyz = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        pixel = np.zeros((len(xyz), 2), np.float32); state = np.zeros(len(xyz), np.uint8)
+        self._chk(lib().e3d_reg_project_points(self._h, int(image_id), C.c_void_p(xyz.ctypes.data), len(xyz), C.c_void_p(pixel.ctypes.data),
+                                               C.c_void_p(state.ctypes.data)), "e3d_reg_project_points")
+        return pixel, state
+
+    @staticmethod
+    def pose_from_bearings(points, bearings, q, t):
+        """The module's pose_from_bearings (host only): the solve that follows pick_scan_points and image_bearings."""
+        return pose_from_bearings(points, bearings, q, t)
 
     def set_cache_observations(self, enabled):
         """Optimizer::set_cache_observations: update_observations re-projects the cached point index lists."""

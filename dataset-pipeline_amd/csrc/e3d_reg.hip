@@ -740,12 +740,11 @@ __global__ __launch_bounds__(kBlock) void k_mask_boundaries(const MeshEdge* __re
 }
 
 // ==== f1: per-point radius range (ComputeMinMaxPointRadius, multi_scale_point_cloud.cc:126-180) ==================================
-// CameraBaseImpl::InitializeUndistortionLookup (camera_base_impl.h:252-268): one Undistort per pixel
+// CameraBaseImpl::InitializeUndistortionLookup (camera_base_impl.h:252-268): one Undistort per pixel.  undistort_lookup_entry is the
+// table's entry for the pixel (x, y): the kernel fills the whole table with it, e3d_reg_image_bearings evaluates the four entries
+// around a position and builds no table.
 template <int M>
-__global__ __launch_bounds__(kBlock) void k_undistort_lookup(CamLevel c, float2* __restrict__ out) {
-  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (size_t)c.width * c.height) return;
-  const int x = (int)(i % c.width), y = (int)(i / c.width);
+__device__ __forceinline__ float2 undistort_lookup_entry(const CamLevel& c, int x, int y) {
   const float dx = c.fx_inv * x + c.cx_inv, dy = c.fy_inv * y + c.cy_inv;
   float ux, uy;
   if constexpr (M == kPinhole || M == kSimplePinhole) { ux = dx; uy = dy; }
@@ -758,12 +757,20 @@ __global__ __launch_bounds__(kBlock) void k_undistort_lookup(CamLevel c, float2*
       ux = factor * ux; uy = factor * uy;
     }
   }
-  out[i] = make_float2(ux, uy);
+  return make_float2(ux, uy);
+}
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_undistort_lookup(CamLevel c, float2* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (size_t)c.width * c.height) return;
+  out[i] = undistort_lookup_entry<M>(c, (int)(i % c.width), (int)(i / c.width));
 }
 
 // ImageToNormalized(Vector2f) through the lookup table (camera_base_impl.h:188-211); the row index y + 1 is clamped where the
-// reference reads one row past the table with weight 0
-__device__ __forceinline__ float2 image_to_normalized(const CamLevel& c, const float2* __restrict__ lookup, float px, float py) {
+// reference reads one row past the table with weight 0.  entry(x, y) is the table's value at a lattice position: a read of the
+// table, or the entry computed on the spot.
+template <class Entry>
+__device__ __forceinline__ float2 image_to_normalized_from(const CamLevel& c, float px, float py, Entry entry) {
   float cx = px < c.width - 1.001f ? px : c.width - 1.001f;
   float cy = py < c.height - 1.00f ? py : c.height - 1.00f;
   if (!(cx > 0.f)) cx = 0.f;
@@ -771,10 +778,33 @@ __device__ __forceinline__ float2 image_to_normalized(const CamLevel& c, const f
   const int ix = (int)cx, iy = (int)cy;
   const float fx = cx - (float)ix, fy = cy - (float)iy;
   const int iy1 = iy + 1 < c.height ? iy + 1 : c.height - 1;
-  const float2 tl = lookup[(size_t)iy * c.width + ix], tr = lookup[(size_t)iy * c.width + ix + 1];
-  const float2 bl = lookup[(size_t)iy1 * c.width + ix], br = lookup[(size_t)iy1 * c.width + ix + 1];
+  const float2 tl = entry(ix, iy), tr = entry(ix + 1, iy);
+  const float2 bl = entry(ix, iy1), br = entry(ix + 1, iy1);
   return make_float2((1 - fy) * ((1 - fx) * tl.x + fx * tr.x) + fy * ((1 - fx) * bl.x + fx * br.x),
                      (1 - fy) * ((1 - fx) * tl.y + fx * tr.y) + fy * ((1 - fx) * bl.y + fx * br.y));
+}
+// ImageToNormalized of the camera model M: FisheyeFOVCamera and the two pinhole models have their own, without the table
+template <int M, class Entry>
+__device__ __forceinline__ float2 camera_image_to_normalized(const CamLevel& c, float px, float py, Entry entry) {
+  if constexpr (M == kFov) {      // Undistort(ImageToDistorted(p)) (camera_fisheye_fov.h:65-74)
+    float2 nxy;
+    cam_fov_undistort(c, c.fx_inv * px + c.cx_inv, c.fy_inv * py + c.cy_inv, nxy.x, nxy.y);
+    return nxy;
+  } else if constexpr (M == kPinhole || M == kSimplePinhole) {   // ImageToDistorted (camera_pinhole.h:55-63)
+    return make_float2(c.fx_inv * px + c.cx_inv, c.fy_inv * py + c.cy_inv);
+  } else {
+    return image_to_normalized_from(c, px, py, entry);
+  }
+}
+
+// e3d_reg_image_bearings: ImageToNormalized of n pixel positions (LocalizeImageTool, localize_image_tool.cc:58-61), the four lattice
+// entries around each computed here where the model goes through the table
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_image_bearings(CamLevel c, const float2* __restrict__ pixels, int n, float2* __restrict__ out) {
+  const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+  if (i >= n) return;
+  const float2 p = pixels[i];
+  out[i] = camera_image_to_normalized<M>(c, p.x, p.y, [&](int x, int y) { return undistort_lookup_entry<M>(c, x, y); });
 }
 
 struct RadiusParams { int image_scale, min_image_scale; float occlusion_threshold, max_valid_intensity; double min_scaling_factor; };
@@ -834,14 +864,7 @@ __global__ __launch_bounds__(kBlock) void k_point_radius(const float4* __restric
   const float G0 = ((p.x + w * ux) + cx) + P.t[0], G1 = ((p.y + w * uy) + cy) + P.t[1], G2 = ((p.z + w * uz) + cz) + P.t[2];
   if (!(G2 > 0.f)) return;
   const float offx = (mx - 0.5f < 0) ? (mx + 0.5f) : (mx - 0.5f);
-  float2 nxy;
-  if constexpr (M == kFov) {      // FisheyeFOVCamera's own ImageToNormalized: Undistort(ImageToDistorted(p)) (camera_fisheye_fov.h:65-74)
-    cam_fov_undistort(cam_min, cam_min.fx_inv * offx + cam_min.cx_inv, cam_min.fy_inv * my + cam_min.cy_inv, nxy.x, nxy.y);
-  } else if constexpr (M == kPinhole || M == kSimplePinhole) {   // their own ImageToNormalized: ImageToDistorted (camera_pinhole.h:55-63)
-    nxy = make_float2(cam_min.fx_inv * offx + cam_min.cx_inv, cam_min.fy_inv * my + cam_min.cy_inv);
-  } else {
-    nxy = image_to_normalized(cam_min, lookup_min, offx, my);
-  }
+  const float2 nxy = camera_image_to_normalized<M>(cam_min, offx, my, [&](int x, int y) { return lookup_min[(size_t)y * cam_min.width + x]; });
   const float d0 = G0 - G2 * nxy.x, d1 = G1 - G2 * nxy.y, d2 = G2 - G2 * 1.f;
   const float point_radius = sqrtf(d0 * d0 + (d1 * d1 + d2 * d2));
   if (point_radius < min_radius[i]) min_radius[i] = point_radius;
@@ -1059,27 +1082,44 @@ __global__ __launch_bounds__(kBlock) void k_scan_visibility(const float4* __rest
 // Visibility of a point in an image (:909-921, :931-943): z > 0, the rounded pixel inside the image at the highest resolution,
 // occlusion + threshold >= z; returns the pixel's index or -1.  Unlike the visibility test above, the reference also asks for
 // pxy + 0.5f >= 0 here: (int) truncates towards zero, so a position in (-1.5, -0.5) would otherwise land in column / row 0.
+// mask_point_state is the test itself: 0 = behind the camera or outside the image, 1 = visible, 2 = inside the image but behind the
+// occlusion depth; pxy is the unrounded position (NaN behind the camera) and px the pixel's index (states 1 and 2).
+constexpr int kPointOutside = 0, kPointVisible = 1, kPointOccluded = 2;
+template <int M>
+__device__ __forceinline__ int mask_point_state(const float4 p, const Pose& P, const CamLevel& cam, const float* __restrict__ occlusion,
+                                                float occlusion_threshold, float2& pxy, size_t& px) {
+  float X, Yc, Z;
+  rt(P, p.x, p.y, p.z, X, Yc, Z);
+  pxy = make_float2(NAN, NAN);
+  if (!(Z > 0.f)) return kPointOutside;
+  float ixf, iyf;
+  cam_normalized_to_image<M>(cam, X / Z, Yc / Z, ixf, iyf);
+  pxy = make_float2(ixf, iyf);
+  const float rx = ixf + 0.5f, ry = iyf + 0.5f;
+  if (!(rx >= 0.f && ry >= 0.f)) return kPointOutside;
+  const int ix = f2i(rx), iy = f2i(ry);
+  if (!(ix >= 0 && iy >= 0 && ix < cam.width && iy < cam.height)) return kPointOutside;
+  px = (size_t)iy * cam.width + ix;
+  if (!(occlusion[px] + occlusion_threshold >= Z)) return kPointOccluded;
+  return kPointVisible;
+}
 template <int M>
 __device__ __forceinline__ long long mask_visible_pixel(const float4 p, const Pose& P, const CamLevel& cam, const float* __restrict__ occlusion,
                                                         float occlusion_threshold) {
-  float X, Yc, Z;
-  rt(P, p.x, p.y, p.z, X, Yc, Z);
-  if (!(Z > 0.f)) return -1;
-  float ixf, iyf;
-  cam_normalized_to_image<M>(cam, X / Z, Yc / Z, ixf, iyf);
-  const float rx = ixf + 0.5f, ry = iyf + 0.5f;
-  if (!(rx >= 0.f && ry >= 0.f)) return -1;
-  const int ix = f2i(rx), iy = f2i(ry);
-  if (!(ix >= 0 && iy >= 0 && ix < cam.width && iy < cam.height)) return -1;
-  const size_t px = (size_t)iy * cam.width + ix;
-  if (!(occlusion[px] + occlusion_threshold >= Z)) return -1;
-  return (long long)px;
+  float2 pxy;
+  size_t px = 0;
+  return mask_point_state<M>(p, P, cam, occlusion, occlusion_threshold, pxy, px) == kPointVisible ? (long long)px : -1;
 }
 
-// the block's number of set flags added to *counter: one atomic per block (every thread of the block calls it)
+// the sum of the waves' counts (every lane of a wave passes its wave's count) added to *counter: one atomic per block (every thread of
+// the block calls it)
+__device__ __forceinline__ void block_wave_counts_add(unsigned wave_count, unsigned long long* __restrict__ counter, unsigned* sc);
+// the block's number of set flags added to *counter
 __device__ __forceinline__ void block_count_add(bool flag, unsigned long long* __restrict__ counter, unsigned* sc) {
-  const unsigned long long b = __ballot(flag);
-  if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = (unsigned)__popcll(b);
+  block_wave_counts_add((unsigned)__popcll(__ballot(flag)), counter, sc);
+}
+__device__ __forceinline__ void block_wave_counts_add(unsigned wave_count, unsigned long long* __restrict__ counter, unsigned* sc) {
+  if ((threadIdx.x & 63) == 0) sc[threadIdx.x >> 6] = wave_count;
   __syncthreads();
   if (threadIdx.x == 0) {
     unsigned c = 0;
@@ -1208,6 +1248,102 @@ __global__ __launch_bounds__(kBlock) void k_mask_fill(const unsigned* __restrict
     for (int w = 0; w < kBlock / kWave; ++w) c += sc[w][threadIdx.x];
     if (c) atomicAdd(counters + threadIdx.x, (unsigned long long)c);
   }
+}
+
+// ==== ImageLocalizer: DatasetInspector's "Localize image" click on a scan point (src/dataset_inspector/localize_image_tool.cc:96-110) ====
+// The reference keeps the projections of all visible scan points (ImageWidget::UpdateScanPoints, gui_image_widget.cc:521-556: the
+// visibility test of the label transfer above) and, per click, walks them for the smallest squared pixel distance -- strict <, from
+// +inf, so of equal distances the first point wins and a NaN distance never does.  Here one pass over the cloud serves up to
+// E3D_LOCALIZE_MAX_CLICKS clicks: a block projects 256 points per step of a grid-stride loop (each point once, its occlusion value
+// gathered once) and leaves the positions of the visible ones in LDS (NaN for the others).  The compares are then dealt out by click:
+// with `group` = the click count rounded up to a power of two, lane l of a wave owns click l % group and the wave's points
+// [l / group * group, + group), read from LDS as broadcasts.  So a lane carries ONE running key whatever the click count -- the
+// register cost of the cloud pass does not depend on it -- and does `group` compares per step: 1 click is one compare of the lane's
+// own point, 32 clicks are 32 compares per lane, the same total as a key per click and thread.  key = (f32 bits of d) << 32 | index:
+// for finite d >= 0 its integer order is (d, index), the reference's order.  The launch ends with a wave minimum over the lanes of
+// one click (__shfl_xor over the offsets >= group), a block minimum through LDS and one 64-bit atomicMin per block and click, none
+// where the block found nothing.
+constexpr int kPickMaxBlocks = 2048;            // 8 blocks of 256 threads for each of the 256 CUs
+constexpr unsigned long long kPickNone = ~0ull;
+// Vector2f::squaredNorm of (pxy - click), no contraction
+__device__ __forceinline__ float pick_distance(float2 pxy, float2 click) {
+  const float dx = pxy.x - click.x, dy = pxy.y - click.y;
+  return __fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy));
+}
+template <int M>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8))) void k_pick_scan_points(const float4* __restrict__ pts, size_t n, Pose P, CamLevel cam,
+                                                             const float* __restrict__ occlusion, float occlusion_threshold,
+                                                             const float2* __restrict__ clicks, int n_clicks, int group,
+                                                             unsigned long long* __restrict__ keys, unsigned long long* __restrict__ n_visible) {
+  __shared__ float2 positions[kBlock];
+  __shared__ unsigned long long wave_best[kBlock / kWave][E3D_LOCALIZE_MAX_CLICKS];
+  __shared__ unsigned sc[kBlock / kWave];
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  const int click_id = lane & (group - 1);                                    // group: a power of two, n_clicks <= group <= 32
+  const int first = wave * kWave + (lane & ~(group - 1));                     // the lane's points of every step, as threads of the block
+  const float2 click = click_id < n_clicks ? clicks[click_id] : make_float2(NAN, NAN);      // (a lane without a click never finds a key)
+  unsigned long long best = kPickNone;
+  unsigned visible = 0;
+  for (size_t base = (size_t)blockIdx.x * kBlock; base < n; base += (size_t)gridDim.x * kBlock) {      // the same trips for the whole block
+    const size_t i = base + threadIdx.x;
+    float2 pxy = make_float2(NAN, NAN);
+    size_t px = 0;
+    const bool seen = i < n && mask_point_state<M>(pts[i], P, cam, occlusion, occlusion_threshold, pxy, px) == kPointVisible;
+    visible += (unsigned)__popcll(__ballot(seen));
+    positions[threadIdx.x] = seen ? pxy : make_float2(NAN, NAN);
+    __syncthreads();
+    for (int j = 0; j < group; ++j) {
+      const float d = pick_distance(positions[first + j], click);
+      if (d < INFINITY) {
+        const unsigned long long key = ((unsigned long long)__float_as_uint(d) << 32) | (unsigned long long)(base + first + j);
+        best = key < best ? key : best;
+      }
+    }
+    __syncthreads();
+  }
+  for (int o = kWave / 2; o >= group; o >>= 1) {
+    const unsigned long long other = __shfl_xor(best, o, kWave);
+    best = other < best ? other : best;
+  }
+  if (lane < n_clicks) wave_best[wave][lane] = best;
+  __syncthreads();
+  if ((int)threadIdx.x < n_clicks) {
+    unsigned long long b = wave_best[0][threadIdx.x];
+    for (int w = 1; w < kBlock / kWave; ++w) b = wave_best[w][threadIdx.x] < b ? wave_best[w][threadIdx.x] : b;
+    if (b != kPickNone) atomicMin(keys + threadIdx.x, b);
+  }
+  block_wave_counts_add(visible, n_visible, sc);
+}
+// ... and the winners once more, for the position and the distance the key has no room for: result[3 c ..] = {pxy.x, pxy.y, d},
+// {NaN, NaN, +inf} without a winner
+template <int M>
+__global__ __launch_bounds__(kWave) void k_pick_finish(const float4* __restrict__ pts, Pose P, CamLevel cam, const float* __restrict__ occlusion,
+                                                       float occlusion_threshold, const float2* __restrict__ clicks, int n_clicks,
+                                                       const unsigned long long* __restrict__ keys, float* __restrict__ result) {
+  const int c = (int)threadIdx.x;
+  if (c >= n_clicks) return;
+  const unsigned long long key = keys[c];
+  float2 pxy = make_float2(NAN, NAN);
+  float d = INFINITY;
+  if (key != kPickNone) {
+    size_t px = 0;
+    mask_point_state<M>(pts[key & 0xffffffffull], P, cam, occlusion, occlusion_threshold, pxy, px);
+    d = pick_distance(pxy, clicks[c]);
+  }
+  result[3 * c] = pxy.x; result[3 * c + 1] = pxy.y; result[3 * c + 2] = d;
+}
+// e3d_reg_project_points: position and state (mask_point_state) of arbitrary points, xyz packed
+template <int M>
+__global__ __launch_bounds__(kBlock) void k_project_points(const float* __restrict__ xyz, size_t n, Pose P, CamLevel cam,
+                                                           const float* __restrict__ occlusion, float occlusion_threshold,
+                                                           float2* __restrict__ pixel, unsigned char* __restrict__ state) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  float2 pxy;
+  size_t px = 0;
+  state[i] = (unsigned char)mask_point_state<M>(make_float4(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], 0.f), P, cam, occlusion,
+                                                occlusion_threshold, pxy, px);
+  pixel[i] = pxy;
 }
 
 // ==== a22 ===============================================================================================================================
@@ -2602,6 +2738,12 @@ struct e3d_reg {
   DevBuf<unsigned long long> mask_counters;
   bool mask_labels_ready = false;
   int mask_transfer_eval_obs = 0;
+  // ImageLocalizer (e3d_reg_pick_scan_points, _image_bearings, _project_points): {visible points | one key per click | {pxy, d} per
+  // click as floats}, the clicks, and the staging of the two per-position calls
+  DevBuf<unsigned long long> pick_words;
+  DevBuf<float2> pick_clicks;
+  DevBuf<float> localize_in, localize_out;
+  DevBuf<unsigned char> localize_state;
   // scratch
   DevBuf<int> valid;
   DevBuf<float> tx, ty, ts;
@@ -4734,6 +4876,257 @@ int e3d_reg_mask_transfer_target(e3d_reg_t* h, int target_image_id, const uint8_
   copy_out(mask_out, h->mask_result.p, px, h->stream);
   rsync(h);
   if (stats) for (int k = 0; k < 3; ++k) stats[k] = (int64_t)counters[k];
+  return 0;
+  E3D_CATCH()
+}
+
+// ---- ImageLocalizer (LocalizeImageTool, src/dataset_inspector/localize_image_tool.cc) ---------------------------------------------------
+int64_t e3d_reg_pick_scan_points(e3d_reg_t* h, int image_id, const float* clicks_xy, int n_clicks, int64_t* index_out, float* pixel_out,
+                                 float* distance_out) {
+  E3D_TRY_ON(h)
+  if (!h || !clicks_xy || !index_out) throw Error(E3D_ERR_INVALID, "null argument");
+  if (n_clicks < 1 || n_clicks > E3D_LOCALIZE_MAX_CLICKS)
+    throw Error(E3D_ERR_INVALID, fmt("n_clicks %d outside 1 .. %d", n_clicks, E3D_LOCALIZE_MAX_CLICKS));
+  if (!h->scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
+  if (h->n_scan >= 0xFFFFFFFFull) throw Error(E3D_ERR_INVALID, "too many scan points for 32-bit indices");
+  ImageDev& im = mask_transfer_image(h, image_id);
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  const size_t n = h->n_scan;
+  constexpr int kKeys = 1, kResult = 1 + E3D_LOCALIZE_MAX_CLICKS, kWords = kResult + (3 * E3D_LOCALIZE_MAX_CLICKS * sizeof(float) + 7) / 8;
+  h->pick_words.reserve(kWords); h->pick_clicks.reserve(E3D_LOCALIZE_MAX_CLICKS);
+  copy_in(h->pick_clicks.p, clicks_xy, sizeof(float2) * n_clicks, h->stream);
+  E3D_HIP(hipMemsetAsync(h->pick_words.p, 0, sizeof(unsigned long long), h->stream));
+  E3D_HIP(hipMemsetAsync(h->pick_words.p + kKeys, 0xFF, sizeof(unsigned long long) * E3D_LOCALIZE_MAX_CLICKS, h->stream));      // kPickNone
+  float* result = reinterpret_cast<float*>(h->pick_words.p + kResult);
+  if (n) {
+    render_depth(h, image_id, in.min_image_scale, nullptr);         // as the label transfer renders it for its source image
+    int group = 1;
+    while (group < n_clicks) group *= 2;
+    const unsigned blocks = std::min<unsigned>(nblk(n), kPickMaxBlocks);
+    KT kt(h, "localize.pick", (double)n);
+    E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_pick_scan_points<M>, dim3(blocks), dim3(kBlock), 0, h->stream, h->scan_pts.p, n, im.pose, cam,
+                                               im.depth.p, h->prm.occlusion_depth_threshold, h->pick_clicks.p, n_clicks, group,
+                                               h->pick_words.p + kKeys, h->pick_words.p));
+  }
+  E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_pick_finish<M>, dim3(1), dim3(kWave), 0, h->stream, h->scan_pts.p, im.pose, cam, im.depth.p,
+                                             h->prm.occlusion_depth_threshold, h->pick_clicks.p, n_clicks, h->pick_words.p + kKeys, result));
+  unsigned long long words[kWords];
+  read_back(h, words, h->pick_words.p, sizeof words);
+  E3D_HIP(hipGetLastError());
+  const float* r = reinterpret_cast<const float*>(words + kResult);
+  for (int c = 0; c < n_clicks; ++c) {
+    index_out[c] = words[kKeys + c] == kPickNone ? -1 : (int64_t)(words[kKeys + c] & 0xffffffffull);
+    if (pixel_out) { pixel_out[2 * c] = r[3 * c]; pixel_out[2 * c + 1] = r[3 * c + 1]; }
+    if (distance_out) distance_out[c] = r[3 * c + 2];
+  }
+  return (int64_t)words[0];
+  E3D_CATCH()
+}
+
+int e3d_reg_image_bearings(e3d_reg_t* h, int image_id, const float* pixels_xy, int n, double* bearings_out) {
+  E3D_TRY_ON(h)
+  if (!h || (n > 0 && (!pixels_xy || !bearings_out))) throw Error(E3D_ERR_INVALID, "null argument");
+  if (n < 0) throw Error(E3D_ERR_INVALID, "negative count");
+  ImageDev& im = mask_transfer_image(h, image_id);
+  if (n == 0) return 0;
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  h->localize_in.reserve(2 * (size_t)n); h->localize_out.reserve(2 * (size_t)n);
+  copy_in(h->localize_in.p, pixels_xy, sizeof(float) * 2 * n, h->stream);
+  E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_image_bearings<M>, dim3(nblk(n)), dim3(kBlock), 0, h->stream, cam,
+                                             reinterpret_cast<const float2*>(h->localize_in.p), n, reinterpret_cast<float2*>(h->localize_out.p)));
+  std::vector<float> nxy(2 * (size_t)n);
+  copy_out(nxy.data(), h->localize_out.p, sizeof(float) * nxy.size(), h->stream);
+  rsync(h);
+  E3D_HIP(hipGetLastError());
+  for (int i = 0; i < n; ++i) {                       // Vector3d(nxy.x, nxy.y, 1).normalized()
+    const double x = nxy[2 * i], y = nxy[2 * i + 1];
+    const double norm = std::sqrt(x * x + y * y + 1.0);
+    bearings_out[3 * i] = x / norm; bearings_out[3 * i + 1] = y / norm; bearings_out[3 * i + 2] = 1.0 / norm;
+  }
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_project_points(e3d_reg_t* h, int image_id, const float* xyz, size_t n, float* pixel_out, uint8_t* state_out) {
+  E3D_TRY_ON(h)
+  if (!h || (n > 0 && (!xyz || !pixel_out || !state_out))) throw Error(E3D_ERR_INVALID, "null argument");
+  ImageDev& im = mask_transfer_image(h, image_id);
+  if (n == 0) return 0;
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  h->localize_in.reserve(3 * n); h->localize_out.reserve(2 * n); h->localize_state.reserve(n);
+  copy_in(h->localize_in.p, xyz, sizeof(float) * 3 * n, h->stream);
+  render_depth(h, image_id, in.min_image_scale, nullptr);
+  E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_project_points<M>, dim3(nblk(n)), dim3(kBlock), 0, h->stream, h->localize_in.p, n, im.pose, cam,
+                                             im.depth.p, h->prm.occlusion_depth_threshold, reinterpret_cast<float2*>(h->localize_out.p),
+                                             h->localize_state.p));
+  copy_out(pixel_out, h->localize_out.p, sizeof(float) * 2 * n, h->stream);
+  copy_out(state_out, h->localize_state.p, n, h->stream);
+  rsync(h);
+  E3D_HIP(hipGetLastError());
+  return 0;
+  E3D_CATCH()
+}
+
+// ---- e3d_pose_from_bearings: host only ---------------------------------------------------------------------------------------------------
+namespace {
+struct BearingPose { double R[9], t[3]; };
+void quat_to_rotation(const double q[4], double R[9]) {
+  const double w = q[0], x = q[1], y = q[2], z = q[3];
+  R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+  R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
+  R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
+}
+void rotation_to_quat(const double R[9], double q[4]) {
+  const double tr = R[0] + R[4] + R[8];
+  if (tr > 0) {
+    const double s = std::sqrt(tr + 1.0) * 2;
+    q[0] = 0.25 * s; q[1] = (R[7] - R[5]) / s; q[2] = (R[2] - R[6]) / s; q[3] = (R[3] - R[1]) / s;
+  } else if (R[0] > R[4] && R[0] > R[8]) {
+    const double s = std::sqrt(1.0 + R[0] - R[4] - R[8]) * 2;
+    q[0] = (R[7] - R[5]) / s; q[1] = 0.25 * s; q[2] = (R[1] + R[3]) / s; q[3] = (R[2] + R[6]) / s;
+  } else if (R[4] > R[8]) {
+    const double s = std::sqrt(1.0 + R[4] - R[0] - R[8]) * 2;
+    q[0] = (R[2] - R[6]) / s; q[1] = (R[1] + R[3]) / s; q[2] = 0.25 * s; q[3] = (R[5] + R[7]) / s;
+  } else {
+    const double s = std::sqrt(1.0 + R[8] - R[0] - R[4]) * 2;
+    q[0] = (R[3] - R[1]) / s; q[1] = (R[2] + R[6]) / s; q[2] = (R[5] + R[7]) / s; q[3] = 0.25 * s;
+  }
+  const double norm = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  const double sign = q[0] < 0 ? -1.0 : 1.0;
+  for (int k = 0; k < 4; ++k) q[k] = sign * q[k] / norm;
+}
+// exp of a rotation vector (Rodrigues), the series near 0
+void rotation_exp(const double w[3], double E[9]) {
+  const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2], th = std::sqrt(th2);
+  const double a = th < 1e-8 ? 1.0 - th2 / 6 : std::sin(th) / th, b = th < 1e-8 ? 0.5 - th2 / 24 : (1 - std::cos(th)) / th2;
+  const double K[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 3; ++c) {
+      double kk = 0;
+      for (int k = 0; k < 3; ++k) kk += K[3 * r + k] * K[3 * k + c];
+      E[3 * r + c] = (r == c ? 1.0 : 0.0) + a * K[3 * r + c] + b * kk;
+    }
+}
+// d_i = (R p_i + t) / |R p_i + t|; cost = sum |f_i - d_i|^2 and, on request, the mean squared angle between f_i and d_i
+double bearing_cost(const BearingPose& T, const double* p, const double* f, int n, double* mean_squared_angle) {
+  double cost = 0, angles = 0;
+  for (int i = 0; i < n; ++i) {
+    double x[3], d[3];
+    for (int r = 0; r < 3; ++r) x[r] = T.R[3 * r] * p[3 * i] + T.R[3 * r + 1] * p[3 * i + 1] + T.R[3 * r + 2] * p[3 * i + 2] + T.t[r];
+    const double len = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+    for (int r = 0; r < 3; ++r) { d[r] = x[r] / len; const double e = f[3 * i + r] - d[r]; cost += e * e; }
+    const double* g = f + 3 * i;
+    const double cx = g[1] * d[2] - g[2] * d[1], cy = g[2] * d[0] - g[0] * d[2], cz = g[0] * d[1] - g[1] * d[0];
+    const double angle = std::atan2(std::sqrt(cx * cx + cy * cy + cz * cz), g[0] * d[0] + g[1] * d[1] + g[2] * d[2]);
+    angles += angle * angle;
+  }
+  if (mean_squared_angle) *mean_squared_angle = angles / n;
+  return cost;
+}
+// A = L D L^T without pivoting, in place (L below the diagonal, D on it); false where a pivot is not above min_ratio * the diagonal
+// entry it started from
+bool ldlt6(double A[36], double min_ratio) {
+  for (int j = 0; j < 6; ++j) {
+    const double start = A[7 * j];
+    double d = start;
+    for (int k = 0; k < j; ++k) d -= A[6 * j + k] * A[6 * j + k] * A[7 * k];
+    if (!(d > min_ratio * start) || !std::isfinite(d)) return false;
+    A[7 * j] = d;
+    for (int i = j + 1; i < 6; ++i) {
+      double v = A[6 * i + j];
+      for (int k = 0; k < j; ++k) v -= A[6 * i + k] * A[6 * j + k] * A[7 * k];
+      A[6 * i + j] = v / d;
+    }
+  }
+  return true;
+}
+void ldlt6_solve(const double A[36], double x[6]) {
+  for (int i = 0; i < 6; ++i) for (int k = 0; k < i; ++k) x[i] -= A[6 * i + k] * x[k];
+  for (int i = 0; i < 6; ++i) x[i] /= A[7 * i];
+  for (int i = 5; i >= 0; --i) for (int k = i + 1; k < 6; ++k) x[i] -= A[6 * k + i] * x[k];
+}
+}  // namespace
+
+int e3d_pose_from_bearings(const double* points, const double* bearings, int n, const float q_in[4], const float t_in[3], float q_out[4],
+                           float t_out[3], double stats[4]) {
+  E3D_TRY
+  if (!points || !bearings || !q_in || !t_in || !q_out || !t_out) throw Error(E3D_ERR_INVALID, "null argument");
+  if (n < 6) throw Error(E3D_ERR_INVALID, fmt("%d correspondences: at least 6 are required", n));
+  bool finite = true;
+  for (int i = 0; i < 3 * n; ++i) finite = finite && std::isfinite(points[i]) && std::isfinite(bearings[i]);
+  for (int k = 0; k < 4; ++k) finite = finite && std::isfinite(q_in[k]);
+  for (int k = 0; k < 3; ++k) finite = finite && std::isfinite(t_in[k]);
+  double q[4] = {q_in[0], q_in[1], q_in[2], q_in[3]};
+  const double qn = std::sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
+  if (!finite || !(qn > 0)) throw Error(E3D_ERR_INVALID, "a point, a bearing or the start pose is not finite");
+  for (int k = 0; k < 4; ++k) q[k] /= qn;
+  BearingPose T;
+  quat_to_rotation(q, T.R);
+  for (int k = 0; k < 3; ++k) T.t[k] = t_in[k];
+  double msa_before = 0, msa_after = 0;
+  double cost = bearing_cost(T, points, bearings, n, &msa_before);
+  double lambda = 1e-4;
+  int iterations = 0;
+  bool converged = false;
+  while (iterations < 100 && !converged) {
+    ++iterations;
+    // residual r_i = f_i - d_i(x), x = R p_i + t; the perturbation x -> exp(w) x + v gives dx = [-[x]x | I] (w, v) and
+    // dd/dx = (I - d d^T) / |x|, so J_i = -(I - d d^T) / |x| * [-[x]x | I]
+    double H[36] = {0}, g[6] = {0};
+    for (int i = 0; i < n; ++i) {
+      double x[3], d[3], res[3];
+      for (int r = 0; r < 3; ++r) x[r] = T.R[3 * r] * points[3 * i] + T.R[3 * r + 1] * points[3 * i + 1] + T.R[3 * r + 2] * points[3 * i + 2] + T.t[r];
+      const double len = std::sqrt(x[0] * x[0] + x[1] * x[1] + x[2] * x[2]);
+      for (int r = 0; r < 3; ++r) { d[r] = x[r] / len; res[r] = bearings[3 * i + r] - d[r]; }
+      const double dx[3][6] = {{0, x[2], -x[1], 1, 0, 0}, {-x[2], 0, x[0], 0, 1, 0}, {x[1], -x[0], 0, 0, 0, 1}};
+      double J[3][6];
+      for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 6; ++c) {
+          double v = 0;
+          for (int k = 0; k < 3; ++k) v += ((r == k ? 1.0 : 0.0) - d[r] * d[k]) * dx[k][c];
+          J[r][c] = -v / len;
+        }
+      for (int a = 0; a < 6; ++a) {
+        for (int r = 0; r < 3; ++r) g[a] += J[r][a] * res[r];
+        for (int b = 0; b < 6; ++b)
+          for (int r = 0; r < 3; ++r) H[6 * a + b] += J[r][a] * J[r][b];
+      }
+    }
+    double check[36];
+    memcpy(check, H, sizeof H);
+    if (!ldlt6(check, 1e-10)) throw Error(E3D_ERR_INVALID, "the correspondences do not determine the pose (LDLT of the normal matrix failed)");
+    // damped steps until one lowers the cost or the step is below the stopping length
+    for (;;) {
+      double A[36], step[6];
+      memcpy(A, H, sizeof H);
+      for (int k = 0; k < 6; ++k) { A[7 * k] += lambda * H[7 * k]; step[k] = -g[k]; }
+      if (!ldlt6(A, 0.0)) throw Error(E3D_ERR_INVALID, "LDLT of the damped normal matrix failed");
+      ldlt6_solve(A, step);
+      double norm = 0;
+      for (int k = 0; k < 6; ++k) norm += step[k] * step[k];
+      if (std::sqrt(norm) < 1e-12) { converged = true; break; }
+      BearingPose N;
+      double E[9];
+      rotation_exp(step, E);
+      for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) N.R[3 * r + c] = E[3 * r] * T.R[c] + E[3 * r + 1] * T.R[3 + c] + E[3 * r + 2] * T.R[6 + c];
+        N.t[r] = E[3 * r] * T.t[0] + E[3 * r + 1] * T.t[1] + E[3 * r + 2] * T.t[2] + step[3 + r];
+      }
+      const double new_cost = bearing_cost(N, points, bearings, n, nullptr);
+      if (new_cost < cost) { T = N; cost = new_cost; lambda = std::max(lambda * 0.1, 1e-15); break; }
+      lambda *= 10;
+      if (lambda > 1e15) { converged = true; break; }        // no step lowers the cost any more: a minimum to rounding
+    }
+  }
+  bearing_cost(T, points, bearings, n, &msa_after);
+  double qo[4];
+  rotation_to_quat(T.R, qo);
+  for (int k = 0; k < 4; ++k) q_out[k] = (float)qo[k];
+  for (int k = 0; k < 3; ++k) t_out[k] = (float)T.t[k];
+  if (stats) { stats[0] = std::sqrt(msa_before); stats[1] = std::sqrt(msa_after); stats[2] = iterations; stats[3] = converged ? 1.0 : 0.0; }
   return 0;
   E3D_CATCH()
 }

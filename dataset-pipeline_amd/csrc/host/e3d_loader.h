@@ -26,6 +26,7 @@ struct Api {
   E3D_FN(e3d_create_splats) E3D_FN(e3d_render_cube_map)
   E3D_FN(e3d_reg_scan_colors_begin) E3D_FN(e3d_reg_scan_colors_add_image) E3D_FN(e3d_reg_scan_colors_get_sums) E3D_FN(e3d_reg_scan_colors_set_sums) E3D_FN(e3d_reg_scan_colors_finish)
   E3D_FN(e3d_reg_mask_transfer_source) E3D_FN(e3d_reg_mask_transfer_target)
+  E3D_FN(e3d_reg_pick_scan_points) E3D_FN(e3d_reg_image_bearings) E3D_FN(e3d_reg_project_points) E3D_FN(e3d_pose_from_bearings)
   E3D_FN(e3d_reg_render_depth)
   E3D_FN(e3d_edit_create) E3D_FN(e3d_edit_destroy) E3D_FN(e3d_edit_size) E3D_FN(e3d_edit_get_points) E3D_FN(e3d_edit_get_selection) E3D_FN(e3d_edit_set_selection) E3D_FN(e3d_edit_selection_count) E3D_FN(e3d_edit_lasso) E3D_FN(e3d_edit_beyond_plane) E3D_FN(e3d_edit_pick) E3D_FN(e3d_edit_delete_selected) E3D_FN(e3d_edit_extract_selected) E3D_FN(e3d_edit_kernel_ms)
 #undef E3D_FN
@@ -66,6 +67,7 @@ inline Api& api() {
   E3D_LOAD(e3d_create_splats) E3D_LOAD(e3d_render_cube_map)
   E3D_LOAD(e3d_reg_scan_colors_begin) E3D_LOAD(e3d_reg_scan_colors_add_image) E3D_LOAD(e3d_reg_scan_colors_get_sums) E3D_LOAD(e3d_reg_scan_colors_set_sums) E3D_LOAD(e3d_reg_scan_colors_finish)
   E3D_LOAD(e3d_reg_mask_transfer_source) E3D_LOAD(e3d_reg_mask_transfer_target)
+  E3D_LOAD(e3d_reg_pick_scan_points) E3D_LOAD(e3d_reg_image_bearings) E3D_LOAD(e3d_reg_project_points) E3D_LOAD(e3d_pose_from_bearings)
   E3D_LOAD(e3d_reg_render_depth)
   E3D_LOAD(e3d_edit_create) E3D_LOAD(e3d_edit_destroy) E3D_LOAD(e3d_edit_size) E3D_LOAD(e3d_edit_get_points) E3D_LOAD(e3d_edit_get_selection) E3D_LOAD(e3d_edit_set_selection) E3D_LOAD(e3d_edit_selection_count) E3D_LOAD(e3d_edit_lasso) E3D_LOAD(e3d_edit_beyond_plane) E3D_LOAD(e3d_edit_pick) E3D_LOAD(e3d_edit_delete_selected) E3D_LOAD(e3d_edit_extract_selected) E3D_LOAD(e3d_edit_kernel_ms)
 #undef E3D_LOAD

@@ -552,6 +552,40 @@ int e3d_reg_scan_colors_finish(e3d_reg_t* reg, uint8_t* rgb);
  * no labels).  No scan points (n = 0) is not an error: 0 labels, mask_out = existing_mask or zeros. */
 int64_t e3d_reg_mask_transfer_source(e3d_reg_t* reg, int source_image_id, const uint8_t* source_mask, int transfer_eval_obs);
 int e3d_reg_mask_transfer_target(e3d_reg_t* reg, int target_image_id, const uint8_t* existing_mask, uint8_t* mask_out, int64_t* stats);
+/* DatasetInspector pose repair, "Localize image" (src/dataset_inspector/localize_image_tool.cc): the user clicks a rendered scan point,
+ * then the pixel it belongs at; from >= 6 such pairs the image's pose is refined on bearing vectors.  Four calls; the first three use
+ * the image's level-0 model, its current pose and -- for visibility -- exactly the test, the occlusion geometry and the occlusion
+ * depth of e3d_reg_mask_transfer_source.  Pixel coordinates: (0, 0) is the centre of the top-left pixel.
+ *   e3d_reg_pick_scan_points: mousePressEvent (:96-110) over the scan points ImageWidget::UpdateScanPoints keeps
+ *     (gui_image_widget.cc:521-556), for n_clicks = 1 .. E3D_LOCALIZE_MAX_CLICKS clicks (clicks_xy: x y per click) in one pass over
+ *     the points of e3d_reg_set_scan_points.  Per click the visible point with the smallest d = fl(fl(dx * dx) + fl(dy * dy)),
+ *     dx = pxy.x - click.x, dy = pxy.y - click.y in f32 without contraction, pxy the point's unrounded position.  The reference's
+ *     comparison is a strict < from +inf: of equal distances the lowest index wins, a NaN or infinite d never wins (so a NaN click
+ *     finds nothing).  index_out[c]: the index in e3d_reg_set_scan_points order or -1; pixel_out (optional, 2 floats per click): the
+ *     winner's pxy, NaN NaN without one; distance_out (optional): d, +inf without a winner.  Returns the number of visible points.
+ *     Fewer than 2^32 - 1 scan points.  n = 0 scan points is not an error: every index is -1.
+ *   e3d_reg_image_bearings: the bearing of n pixel positions (:58-61): the model's ImageToNormalized -- through the undistortion
+ *     lookup with bilinear interpolation (camera_base_impl.h:188-211; the four lattice entries around each position are computed,
+ *     no table is built), except for the models with their own (PINHOLE, SIMPLE_PINHOLE: linear; FOV: closed form) -- then
+ *     (nx, ny, 1) as doubles divided by their norm: 3 doubles per position, host memory.
+ *   e3d_reg_project_points: for n global points (xyz packed) the unrounded pixel position (NaN NaN behind the camera) and a state:
+ *     0 = behind the camera or outside the image, 1 = visible, 2 = inside the image but behind the occlusion depth.
+ *   e3d_pose_from_bearings: HOST ONLY (needs no device).  With d_i = (R p_i + t) / |R p_i + t| it minimises sum |f_i - d_i|^2 over the
+ *     pose image_T_global = (R, t) (conventions of e3d_reg_set_image_pose) by Levenberg-Marquardt in f64 from (q_in, t_in): update
+ *     (R, t) <- (exp(w) R, exp(w) t + v), analytic Jacobians, at most 100 iterations, stops when the step (w, v) is shorter than
+ *     1e-12.  points: n global points, bearings: n unit vectors in the camera frame, 3 doubles each.  q_out (unit, w >= 0) and
+ *     t_out are the result rounded to f32.  stats (optional): RMS angle between f_i and d_i before, after, iterations, 1 if it
+ *     stopped on the step length.  Refused: n < 6 (:138-141), a non-finite input, a normal matrix whose LDLT fails (all points on
+ *     one line, for instance).
+ * Errors of the first three as for the label transfer: null handle or outputs, n_clicks outside its range, unknown image
+ * (E3D_ERR_INDEX), an image of another rank, no scan points set (pick only). */
+#define E3D_LOCALIZE_MAX_CLICKS 32
+int64_t e3d_reg_pick_scan_points(e3d_reg_t* reg, int image_id, const float* clicks_xy, int n_clicks, int64_t* index_out, float* pixel_out,
+                                 float* distance_out);
+int e3d_reg_image_bearings(e3d_reg_t* reg, int image_id, const float* pixels_xy, int n, double* bearings_out);
+int e3d_reg_project_points(e3d_reg_t* reg, int image_id, const float* xyz, size_t n, float* pixel_out, uint8_t* state_out);
+int e3d_pose_from_bearings(const double* points, const double* bearings, int n, const float q_in[4], const float t_in[3], float q_out[4],
+                           float t_out[3], double stats[4]);
 /* Observations cache (src/opt/observations_cache.{h,cc}; Optimizer::set_cache_observations, optimizer.h).  When enabled, the
  * observation update re-projects a fixed per-image list of point indices with the current state and applies only the
  * scale-fit and border tests (VisibilityEstimator::AppendObservationsForIndexedPointsVisibleInImage,
