@@ -126,6 +126,13 @@ struct Cloud {
   // impl cloud 0 never moves, fixed clouds never do -- is not transformed again
   bool G4_valid = false;
   float G4_T[12];
+  // source view (LmSet): this cloud's half of every resident row it is the source of, in the sorted order of `view_gen`; local
+  // frame, or (view_global) the global frame at pose view_T for a cloud that does not move inside the call (ensure_source_view)
+  DevBuf<float4> V0;
+  DevBuf<float2> V1;
+  bool view_valid = false, view_global = false;
+  unsigned long long view_gen = 0;
+  float view_T[12];
   // per-pose quantities every directed pair with this cloud as target asks for (an all-pairs job asks 15 times per outer iteration:
   // the Jacobi sweeps and the inversion were 0.1 ms of host time per batch of 32 pairs)
   mutable bool pose_cache_valid = false;
@@ -151,9 +158,11 @@ struct PairState {
   // motion of the source's queries relative to the target since the state was created (MotionBound, e3d_icp_kernels.hpp): a query
   // at distance rho from the source's bounding-box centre has moved at most mA * rho + mB in the target's frame
   double mA = 0.0, mB = 0.0;
-  // resident correspondence rows (LmSet): one row per query at its source position, rewritten only where the partner changed
-  DevBuf<float4> pA, pB, pC;
-  DevBuf<int> plane_match;         // the partner each row encodes (-1: zero row)
+  // resident correspondence rows (LmSet): one row per query at its source position, rewritten only where the partner changed;
+  // the target half alone (R0 = {tp.xy}, R1 = {tp.z, tn.xyz}), the source half is the source cloud's view
+  DevBuf<float2> r0;
+  DevBuf<float4> r1;
+  DevBuf<int> plane_match;         // the partner each row encodes (-1: none, the row carries the mark)
   DevBuf<unsigned> glist;          // active 64-row groups of the last update
   bool rows_valid = false;         // plane_match describes the planes (same sorted orders, same frames)
   bool src_global = false, tgt_global = false;   // the half is stored in the global frame (its cloud never moves) at pose *_T
@@ -343,7 +352,8 @@ static Slice slice_of(const e3d_icp* h, const Cloud& src) {
   const size_t j1 = (size_t)((unsigned __int128)src.n * (unsigned)(h->rank + 1) / (unsigned)h->world);
   return {j0, j1 - j0};
 }
-static void release_rows(PairState& ps) { ps.pA.release(); ps.pB.release(); ps.pC.release(); ps.rows_valid = false; }
+static void release_rows(PairState& ps) { ps.r0.release(); ps.r1.release(); ps.rows_valid = false; }
+static void release_view(Cloud& c) { c.V0.release(); c.V1.release(); c.view_valid = false; }
 
 static void upload_cloud(e3d_icp* h, Cloud& c, const float* xyz, const float* nrm, size_t n) {
   c.n = n;
@@ -834,7 +844,11 @@ static bool far_list_is_short(size_t n_far, size_t n) {
   return n_far > 0 && (div <= 0 || n_far * (size_t)div < n);
 }
 static size_t resident_rows_cap(size_t n) { return div_up(n, 64) * 64; }
-static size_t resident_bytes(size_t n) { return resident_rows_cap(n) * 48 + n * 4 + div_up(n, 64) * 4; }
+static size_t resident_bytes(size_t n) { return resident_rows_cap(n) * 24 + n * 4 + div_up(n, 64) * 4; }
+// rows of a cloud's source view: a rank's slice starts anywhere, and the last 64-row group of a slice is read whole
+static size_t source_view_cap(size_t n) { return resident_rows_cap(n) + 64; }
+static size_t source_view_bytes(size_t n) { return source_view_cap(n) * 24; }
+static bool alloc_trace() { static const bool on = [] { const char* e = getenv("E3D_ALLOC_TRACE"); return e && e[0] == '1'; }(); return on; }
 
 // ---- what the three drivers of the certificate search share -----------------------------------------------------------------------
 // One directed pair of the certificate search: who (filled by the caller), what its kernels are asked to do at this outer iteration
@@ -940,19 +954,33 @@ static void print_pair_stats(const BatchItem& it) {
 // the LM passes for it.  If such a cloud did move since the rows were written (another role in an earlier call), or a half changes
 // frames, every row is rewritten once: plane_match is reset to "never written" (enqueued on s).
 struct RowFrames { bool sg, tg; bool reset; };      // source / target half in the global frame; the rows were reset
-static RowFrames ensure_resident_rows(PairState& ps, const Cloud& src, const Cloud& tgt, size_t n, hipStream_t s) {
+// The source half: one view per cloud for every pair it is the source of and every rank's slice, tagged with the sorted order, the
+// frame and (global frame) the pose it was written for; written again when one of them changed (enqueued on s; G4 is at pose T).
+static void ensure_source_view(Cloud& c, bool global, hipStream_t s) {
+  const size_t cap = source_view_cap(c.n);
+  bool valid = c.view_valid && c.V0.cap >= cap && c.V1.cap >= cap && c.view_gen == c.generation && c.view_global == global;
+  if (valid && global && std::memcmp(c.view_T, c.T, sizeof c.view_T) != 0) valid = false;
+  if (valid) return;
+  if (alloc_trace() && (c.V0.cap < cap || c.V1.cap < cap))
+    fprintf(stderr, "[rows] source view of cloud %d: %zu points, %zu bytes (%s frame)\n", c.cloud_index, c.n, source_view_bytes(c.n), global ? "global" : "local");
+  c.V0.reserve(cap); c.V1.reserve(cap);
+  launch_source_view(global ? c.G4.p : c.L4.p, c.LN.p, c.n, cap, global, to_affine(c.T), c.V0.p, c.V1.p, s);
+  c.view_valid = true; c.view_global = global; c.view_gen = c.generation;
+  std::memcpy(c.view_T, c.T, sizeof c.view_T);
+}
+static RowFrames ensure_resident_rows(PairState& ps, Cloud& src, const Cloud& tgt, size_t n, hipStream_t s) {
   const size_t cap = resident_rows_cap(n);
   const bool sg = src.fixed || src.cloud_index == 0, tg = tgt.fixed || tgt.cloud_index == 0;
-  bool valid = ps.rows_valid && ps.pA.cap >= cap && ps.src_global == sg && ps.tgt_global == tg;
+  ensure_source_view(src, sg, s);
+  bool valid = ps.rows_valid && ps.r0.cap >= cap && ps.r1.cap >= cap && ps.src_global == sg && ps.tgt_global == tg;
   if (valid && sg && std::memcmp(ps.src_T, src.T, sizeof ps.src_T) != 0) valid = false;
   if (valid && tg && std::memcmp(ps.tgt_T, tgt.T, sizeof ps.tgt_T) != 0) valid = false;
   if (!valid) {
-    ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap); ps.plane_match.reserve(n); ps.glist.reserve(div_up(n, 64));
+    ps.r0.reserve(cap); ps.r1.reserve(cap); ps.plane_match.reserve(n); ps.glist.reserve(div_up(n, 64));
     E3D_HIP(hipMemsetAsync(ps.plane_match.p, 0xFE, sizeof(int) * n, s));
-    if (cap > n) {                                                                 // the rows past the last query stay zero rows
-      E3D_HIP(hipMemsetAsync(ps.pA.p + n, 0, sizeof(float4) * (cap - n), s));
-      E3D_HIP(hipMemsetAsync(ps.pB.p + n, 0, sizeof(float4) * (cap - n), s));
-      E3D_HIP(hipMemsetAsync(ps.pC.p + n, 0, sizeof(float4) * (cap - n), s));
+    if (cap > n) {                              // the rows past the last query carry the mark (all bits set: a NaN in tp.x)
+      E3D_HIP(hipMemsetAsync(ps.r0.p + n, 0xFF, sizeof(float2) * (cap - n), s));
+      E3D_HIP(hipMemsetAsync(ps.r1.p + n, 0, sizeof(float4) * (cap - n), s));
     }
     ps.src_global = sg; ps.tgt_global = tg;
     std::memcpy(ps.src_T, src.T, sizeof ps.src_T); std::memcpy(ps.tgt_T, tgt.T, sizeof ps.tgt_T);
@@ -965,13 +993,12 @@ static RowFrames ensure_resident_rows(PairState& ps, const Cloud& src, const Clo
 // the totals (count, active groups, rewritten rows) and the distance sum stay on the device for the caller's read-back
 static void update_resident_rows(e3d_icp* h, BatchItem& it, const float* match_d2, unsigned long long* totals_out, double* d2_out, e3d_icp_iter_record& rec) {
   hipStream_t s = h->stream;
-  const Cloud& src = *it.src; const Cloud& tgt = *it.tgt;
+  Cloud& src = *it.src; const Cloud& tgt = *it.tgt;
   PairState& ps = *it.ps;
   const RowFrames rf = ensure_resident_rows(ps, src, tgt, it.n, s);
   h->tm_compact.start(s);
-  launch_corr_update(ps.match.p, ps.plane_match.p, match_d2, it.n, (rf.sg ? src.G4.p : src.L4.p) + it.j0, src.LN.p + it.j0, rf.sg, to_affine(src.T),
-                     rf.tg ? tgt.G4.p : tgt.L4.p, tgt.LN.p, rf.tg, to_affine(tgt.T), ps.pA.p, ps.pB.p, ps.pC.p, h->block_counts.p,
-                     h->block_d2.p, h->block_groups.p, s);
+  launch_corr_update(ps.match.p, ps.plane_match.p, match_d2, it.n, rf.tg ? tgt.G4.p : tgt.L4.p, tgt.LN.p, rf.tg, to_affine(tgt.T), ps.r0.p, ps.r1.p,
+                     h->block_counts.p, h->block_d2.p, h->block_groups.p, s);
   h->tm_compact.stop(s);
   h->tm_scan.start(s);
   launch_corr_totals(it.n, h->block_counts.p, h->block_d2.p, h->block_groups.p, h->chunk_sum.p, h->chunk_d2.p, h->chunk_groups.p,
@@ -1215,7 +1242,7 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
     sl.match_d2.reserve(n); sl.todo_near.reserve(n); sl.todo_far.reserve(n);
     prepare_pair(it, d);
     const RowFrames rf = ensure_resident_rows(ps, src, tgt, n, s);
-    const bool sg = rf.sg, tg = rf.tg;
+    const bool tg = rf.tg;
     it.rows_reset = rf.reset;
     NnPairDev& P = T.pair[i];
     P.Gsrc = src.G4.p + it.j0; P.Gtgt = tgt.G4.p; P.S = tgt.dense_start.p; P.H8 = tgt.half_prefix.p;
@@ -1224,9 +1251,9 @@ static bool find_pairs_multi(e3d_icp* h, std::vector<BatchItem>& items, float d,
     P.n = (unsigned)n; P.none_near = it.none_near ? 1 : 0;
     P.cum_up = it.cum_up; P.near2 = it.near2;
     P.g = tgt.grid; P.im = it.im; P.qr = tgt.qrange; P.bp = it.bp;
-    P.Psrc = (sg ? src.G4.p : src.L4.p) + it.j0; P.LNsrc = src.LN.p + it.j0; P.Ptgt = tg ? tgt.G4.p : tgt.L4.p; P.LNtgt = tgt.LN.p;
-    P.src_global = sg ? 1 : 0; P.tgt_global = tg ? 1 : 0; P.Tsrc = to_affine(src.T); P.Ttgt = to_affine(tgt.T);
-    P.A = ps.pA.p; P.B = ps.pB.p; P.C = ps.pC.p; P.plane_match = ps.plane_match.p; P.glist = ps.glist.p;
+    P.Ptgt = tg ? tgt.G4.p : tgt.L4.p; P.LNtgt = tgt.LN.p;
+    P.tgt_global = tg ? 1 : 0; P.Ttgt = to_affine(tgt.T);
+    P.R0 = ps.r0.p; P.R1 = ps.r1.p; P.plane_match = ps.plane_match.p; P.glist = ps.glist.p;
     if (it.certified) { cert_blocks += (unsigned)div_up(n, (size_t)kNnCertBlockQueries); cert_queries += (long long)n; }
     T.cert_end[i] = cert_blocks;
     const unsigned nb = (unsigned)div_up(n, kBlock);
@@ -1590,12 +1617,14 @@ static void lm_prepare(e3d_icp* h, LmSystem& L, std::vector<PairJob>& jobs) {
       if (j->resident) {
         // resident rows: the pass walks the listed 64-row groups; local halves get the outer pose of this iteration
         const PairState& ps = *j->resident;
-        S.A = ps.pA.p; S.B = ps.pB.p; S.C = ps.pC.p; S.glist = ps.glist.p; S.n = j->vrows;
+        const Cloud& src = cloud_at(h, j->src);
+        // split rows: the source half from the cloud's view at this rank's slice, the target half from the pair's planes
+        S.A = src.V0.p + ps.jbase; S.V1 = src.V1.p + ps.jbase; S.B = nullptr; S.R0 = ps.r0.p; S.C = ps.r1.p; S.glist = ps.glist.p; S.n = j->vrows;
         if ((size_t)j->vrows == resident_rows_cap(ps.n)) S.glist = nullptr;      // every group is listed: rows [0, n) as they lie
         S.outer = (ps.src_global ? 0 : 1) | (ps.tgt_global ? 0 : 2);
         S.Tos = to_affine(cloud_at(h, j->src).T); S.Tot = to_affine(cloud_at(h, j->tgt).T);
       } else {
-        S.A = h->cA.p + j->corr_off; S.B = h->cB.p + j->corr_off; S.C = h->cC.p + j->corr_off; S.glist = nullptr; S.n = j->count;
+        S.A = h->cA.p + j->corr_off; S.B = h->cB.p + j->corr_off; S.C = h->cC.p + j->corr_off; S.V1 = nullptr; S.R0 = nullptr; S.glist = nullptr; S.n = j->count;
         S.outer = 0;
         S.Tos = Affine{}; S.Tot = Affine{};
       }
@@ -1796,11 +1825,16 @@ static std::vector<PairJob> list_pairs(e3d_icp* h, int fixed_vertex) {
 }
 
 // Where this outer iteration's correspondences live (h->resident_now).  Pairs of the certificate path keep RESIDENT rows (one row per
-// query, 48 B + 4 B, for as long as the grids live) when all of them fit beside what is already allocated; otherwise every pair goes
+// query, 24 B + 4 B, for as long as the grids live; beside them 24 B per point of every source cloud, its view) when all of them fit
+// beside what is already allocated; otherwise every pair goes
 // through the compacted planes cA / cB / cC, sized here (correspondences <= queries: no hipMalloc / hipFree inside the batch loop).
 static void plan_rows(e3d_icp* h, const std::vector<PairJob>& jobs) {
   auto wants_rows = [&](const PairJob& j, size_t nq) { const Cloud& tgt = cloud_at(h, j.tgt); return pair_uses_rows(h, tgt) && nq != 0 && tgt.n != 0; };
-  auto release_all = [&] { for (auto& kv : h->pair_state) release_rows(*kv.second); };
+  auto release_all = [&] {
+    for (auto& kv : h->pair_state) release_rows(*kv.second);
+    for (auto& c : h->clouds) release_view(*c);
+    if (h->fixed) release_view(*h->fixed);
+  };
   bool resident = h->resident_rows;
   size_t rows_new = 0, q_max = 0;
   for (const PairJob& j : jobs) {
@@ -1808,8 +1842,18 @@ static void plan_rows(e3d_icp* h, const std::vector<PairJob>& jobs) {
     q_max = std::max(q_max, nq);
     if (!wants_rows(j, nq)) continue;
     auto it = h->pair_state.find(std::make_pair(j.src, j.tgt));
-    if (it == h->pair_state.end() || it->second->pA.cap < resident_rows_cap(nq)) rows_new += resident_bytes(nq);
+    if (it == h->pair_state.end() || it->second->r1.cap < resident_rows_cap(nq)) rows_new += resident_bytes(nq);
   }
+  // ... and one source view per cloud that is the source of such a pair
+  std::vector<Cloud*> view_clouds;
+  for (const PairJob& j : jobs) {
+    Cloud& src = cloud_at(h, j.src);
+    if (!wants_rows(j, slice_of(h, src).n) || std::find(view_clouds.begin(), view_clouds.end(), &src) != view_clouds.end()) continue;
+    view_clouds.push_back(&src);
+    if (src.V0.cap < source_view_cap(src.n)) rows_new += source_view_bytes(src.n);
+  }
+  for (auto& c : h->clouds) if (std::find(view_clouds.begin(), view_clouds.end(), c.get()) == view_clouds.end()) release_view(*c);
+  if (h->fixed && std::find(view_clouds.begin(), view_clouds.end(), h->fixed.get()) == view_clouds.end()) release_view(*h->fixed);
   // rows of pairs that have left the job list (their bounding boxes no longer intersect) go back first
   for (auto& kv : h->pair_state) {
     bool listed = false;
@@ -1834,11 +1878,20 @@ static void plan_rows(e3d_icp* h, const std::vector<PairJob>& jobs) {
         if (!wants_rows(j, sl.n)) continue;
         PairState& ps = pair_state_for(h, j.src, j.tgt, src, cloud_at(h, j.tgt), sl.j0, sl.n);
         const size_t cap = resident_rows_cap(sl.n);
-        if (ps.pA.cap < cap || ps.pB.cap < cap || ps.pC.cap < cap) {
+        if (ps.r0.cap < cap || ps.r1.cap < cap) {
+          if (alloc_trace()) fprintf(stderr, "[rows] pair %d->%d: %zu queries, %zu bytes of resident rows\n", j.src, j.tgt, sl.n, resident_bytes(sl.n));
           ps.rows_valid = false;
-          ps.pA.reserve(cap); ps.pB.reserve(cap); ps.pC.reserve(cap);
+          ps.r0.reserve(cap); ps.r1.reserve(cap);
         }
         ps.plane_match.reserve(sl.n); ps.glist.reserve(div_up(sl.n, 64));
+      }
+      for (Cloud* c : view_clouds) {
+        const size_t cap = source_view_cap(c->n);
+        if (c->V0.cap < cap || c->V1.cap < cap) {
+          if (alloc_trace()) fprintf(stderr, "[rows] source view of cloud %d: %zu points, %zu bytes\n", c->cloud_index, c->n, source_view_bytes(c->n));
+          c->view_valid = false;
+          c->V0.reserve(cap); c->V1.reserve(cap);
+        }
       }
     } catch (const Error&) {
       (void)hipGetLastError();

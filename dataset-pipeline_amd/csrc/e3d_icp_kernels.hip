@@ -2231,19 +2231,57 @@ __global__ __launch_bounds__(kBlock) void k_compact_corr(const int* __restrict__
   st_stream(C + o, make_float4(tp.z, tn.x, tn.y, tn.z));
 }
 
-// Resident rows (LmSet): one row per query of the pair, at its source position.  Rewrites the rows whose partner differs from the
-// one the row encodes -- in the settled state of an alignment a handful per launch, where k_compact_corr gathered and rewrote all
+// Resident rows (LmSet): one row per query of the pair, at its source position.  A row is twelve floats; the six of the SOURCE
+// are the cloud's own point and normal at that position, the same for every pair with this cloud as source and unchanged while
+// the cloud's frame stands: they live once per cloud in its source view (k_source_view), and a pair keeps the TARGET half only,
+//   R0[j] = (tp.x, tp.y)   R1[j] = (tp.z, tn.xyz).
+// A query without a partner carries a NaN in tp.x (kRowMark): no partner has one -- a target point with a NaN coordinate never
+// compares nearer than anything in the searches -- and the LM passes turn such a row into the all-zero row whose residuals and
+// Jacobian rows are exactly 0.  (Not "all zeros": a partner at the local origin with a zero normal is a correspondence.)
+__device__ __forceinline__ float row_mark() { return __uint_as_float(0x7FC00000u); }
+typedef float row_v2f __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void st_stream2(float2* __restrict__ p, const float2 v) {
+  if constexpr (E3D_NT >= 2) { const row_v2f w = {v.x, v.y}; __builtin_nontemporal_store(w, reinterpret_cast<row_v2f*>(p)); }
+  else *p = v;
+}
+
+// The source view of a cloud in its sorted order: V0[j] = (p.xyz, n.x), V1[j] = (n.y, n.z) for j < n, zeros up to cap.  A cloud
+// that can move is held in its LOCAL frame (P = L4); one that never moves inside the call (impl cloud 0, fixed clouds) in the
+// global frame at pose T exactly as k_compact_corr writes it (P = G4, normal = pcl_so3(T, ln)).
+__global__ __launch_bounds__(kBlock) void k_source_view(const float4* __restrict__ P, const float4* __restrict__ LN, size_t n, size_t cap,
+                                                        const int global, Affine T, float4* __restrict__ V0, float2* __restrict__ V1) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= cap) return;
+  float4 v0 = make_float4(0.f, 0.f, 0.f, 0.f);
+  float2 v1 = make_float2(0.f, 0.f);
+  if (j < n) {
+    const float4 sp = ld_stream(P + j);
+    const float4 ln = ld_stream(LN + j);
+    float3 sn = make_float3(ln.x, ln.y, ln.z);
+    if (global) sn = pcl_so3(T, ln.x, ln.y, ln.z);
+    v0 = make_float4(sp.x, sp.y, sp.z, sn.x);
+    v1 = make_float2(sn.y, sn.z);
+  }
+  st_stream(V0 + j, v0); st_stream2(V1 + j, v1);
+}
+
+// The update rewrites the rows whose partner differs from the one the row encodes -- in the settled state of an alignment a handful per launch, where k_compact_corr gathered and rewrote all
 // of them every outer iteration -- and produces what the progress line and the LM passes need from the match list: per-block
 // match counts and squared-distance sums (the arithmetic of k_match_block_counts) and the active 64-row groups of the block
 // (count in bits 0..7, mask in bits 8..11; bits 16..24: rows rewritten, a statistic -- summed without atomics: an atomic per
-// wave on one counter made a launch that rewrites every row 3.5 times slower than k_compact_corr).  Halves of clouds that never move (impl cloud 0, fixed clouds) are stored in the
-// global frame exactly as k_compact_corr writes them; halves of movable clouds in the cloud's local frame (row_to_global).
+// wave on one counter made a launch that rewrites every row 3.5 times slower than k_compact_corr).  The half of a cloud that never
+// moves (impl cloud 0, fixed clouds) is stored in the global frame exactly as k_compact_corr writes it; that of a movable cloud in
+// the cloud's local frame (row_to_global).
+// E3D_R0_RUN: rows per rewritten run of the float2 plane, 8 (64 B) or 16 (a whole 128-byte line; the rows of the line's other
+// half gather their partner's point again).  Measured: profiles/split_rows.txt.
+#ifndef E3D_R0_RUN
+#define E3D_R0_RUN 8
+#endif
+static_assert(E3D_R0_RUN == 8 || E3D_R0_RUN == 16, "runs of the float2 plane: 8 or 16 rows");
 __device__ __forceinline__ void corr_update_body(const unsigned bx, const int* __restrict__ match, int* __restrict__ plane_match,
-                                                 const float* __restrict__ match_d2, size_t n,
-                                                 const float4* __restrict__ Psrc, const float4* __restrict__ LNsrc,
-                                                 const int src_global, const Affine& Tsrc, const float4* __restrict__ Ptgt,
+                                                 const float* __restrict__ match_d2, size_t n, const float4* __restrict__ Ptgt,
                                                  const float4* __restrict__ LNtgt, const int tgt_global, const Affine& Ttgt,
-                                                 float4* __restrict__ A, float4* __restrict__ B, float4* __restrict__ C,
+                                                 float2* __restrict__ R0, float4* __restrict__ R1,
                                                  unsigned* __restrict__ block_counts, double* __restrict__ block_d2,
                                                  unsigned* __restrict__ block_groups, const unsigned char* __restrict__ done = nullptr) {
   if (done && done[bx]) return;      // every query settled by its certificate: nn_certify_body wrote this block's results
@@ -2252,28 +2290,30 @@ __device__ __forceinline__ void corr_update_body(const unsigned bx, const int* _
   const int m = in ? ld_stream(match + j) : -1;
   const int pm = in ? ld_stream(plane_match + j) : -1;
   const bool f = m >= 0;
-  // Rows are rewritten in whole 128-byte lines (8 rows of a plane): a lone 16-byte store is a partial line write all the way to
-  // HBM -- measured: 3.5 ms per launch with 5 % of the rows rewritten one by one, against 1.0 ms for ALL rows in full lines.
+  // Rows are rewritten in whole 128-byte lines (8 rows of the float4 plane): a lone 16-byte store is a partial line write all the
+  // way to HBM -- measured: 3.5 ms per launch with 5 % of the rows rewritten one by one, against 1.0 ms for ALL rows in full lines.
   const unsigned long long chg = __ballot(in && m != pm);
   const bool wr = in && (((chg >> (threadIdx.x & 56)) & 0xFFull) != 0ull);
+  const bool wr0 = (E3D_R0_RUN == 8) ? wr : (in && (((chg >> (threadIdx.x & 48)) & 0xFFFFull) != 0ull));
   const unsigned long long wrb = __ballot(wr);
-  if (wr) {
-    float4 ra = make_float4(0.f, 0.f, 0.f, 0.f), rb = ra, rc = ra;
+  if (wr0) {
+    float2 r0 = make_float2(row_mark(), 0.f);
+    float4 r1 = make_float4(0.f, 0.f, 0.f, 0.f);
     if (f) {
-      const float4 sp = Psrc[j];
-      const float4 ln = LNsrc[j];
-      float3 sn = make_float3(ln.x, ln.y, ln.z);
-      if (src_global) sn = pcl_so3(Tsrc, ln.x, ln.y, ln.z);
       const float4 tp = Ptgt[m];
-      const float4 tl = LNtgt[m];
-      float3 tn = make_float3(tl.x, tl.y, tl.z);
-      if (tgt_global) tn = pcl_so3(Ttgt, tl.x, tl.y, tl.z);
-      ra = make_float4(sp.x, sp.y, sp.z, sn.x);
-      rb = make_float4(sn.y, sn.z, tp.x, tp.y);
-      rc = make_float4(tp.z, tn.x, tn.y, tn.z);
+      r0 = make_float2(tp.x, tp.y);
+      if (wr) {
+        const float4 tl = LNtgt[m];
+        float3 tn = make_float3(tl.x, tl.y, tl.z);
+        if (tgt_global) tn = pcl_so3(Ttgt, tl.x, tl.y, tl.z);
+        r1 = make_float4(tp.z, tn.x, tn.y, tn.z);
+      }
     }
-    st_stream(A + j, ra); st_stream(B + j, rb); st_stream(C + j, rc);
-    if (m != pm) plane_match[j] = m;
+    st_stream2(R0 + j, r0);
+    if (wr) {
+      st_stream(R1 + j, r1);
+      if (m != pm) plane_match[j] = m;
+    }
   }
   const unsigned long long b = __ballot(f);
   double d = f ? (double)ld_stream(match_d2 + j) : 0.0;
@@ -2290,15 +2330,12 @@ __device__ __forceinline__ void corr_update_body(const unsigned bx, const int* _
 }
 
 __global__ __launch_bounds__(kBlock) void k_corr_update(const int* __restrict__ match, int* __restrict__ plane_match,
-                                                        const float* __restrict__ match_d2, size_t n,
-                                                        const float4* __restrict__ Psrc, const float4* __restrict__ LNsrc,
-                                                        const int src_global, Affine Tsrc, const float4* __restrict__ Ptgt,
+                                                        const float* __restrict__ match_d2, size_t n, const float4* __restrict__ Ptgt,
                                                         const float4* __restrict__ LNtgt, const int tgt_global, Affine Ttgt,
-                                                        float4* __restrict__ A, float4* __restrict__ B, float4* __restrict__ C,
+                                                        float2* __restrict__ R0, float4* __restrict__ R1,
                                                         unsigned* __restrict__ block_counts, double* __restrict__ block_d2,
                                                         unsigned* __restrict__ block_groups) {
-  corr_update_body(blockIdx.x, match, plane_match, match_d2, n, Psrc, LNsrc, src_global, Tsrc, Ptgt, LNtgt, tgt_global, Ttgt, A, B, C,
-                   block_counts, block_d2, block_groups);
+  corr_update_body(blockIdx.x, match, plane_match, match_d2, n, Ptgt, LNtgt, tgt_global, Ttgt, R0, R1, block_counts, block_d2, block_groups);
 }
 
 // the resident rows of a batch of pairs: the per-block results of pair p go to entries [blk0(p), blk0(p) + blocks of p) of the batch's arrays
@@ -2307,9 +2344,9 @@ __global__ __launch_bounds__(kBlock) void k_corr_update_multi(const NnBatchDev* 
   const int p = nn_find_range(Bt->upd_end, Bt->n_pairs, blockIdx.x);
   const unsigned b0 = p ? Bt->upd_end[p - 1] : 0u;
   const NnPairDev& P = Bt->pair[p];
-  const Affine Ts = P.Tsrc, Tt = P.Ttgt;
-  corr_update_body(blockIdx.x - b0, P.match, P.plane_match, P.match_d2, (size_t)P.n, P.Psrc, P.LNsrc, P.src_global, Ts, P.Ptgt, P.LNtgt,
-                   P.tgt_global, Tt, P.A, P.B, P.C, block_counts + b0, block_d2 + b0, block_groups + b0, P.upd_done);
+  const Affine Tt = P.Ttgt;
+  corr_update_body(blockIdx.x - b0, P.match, P.plane_match, P.match_d2, (size_t)P.n, P.Ptgt, P.LNtgt, P.tgt_global, Tt, P.R0, P.R1,
+                   block_counts + b0, block_d2 + b0, block_groups + b0, P.upd_done);
 }
 
 // ascending list of the active 64-row groups: one thread per query block (4 groups), scan inside the chunk + the chunk's base
@@ -2664,6 +2701,37 @@ __device__ __forceinline__ float4 ld_row(const lm_rows_ptr p, const long long r)
   if constexpr (E3D_NT >= 1) v = __builtin_nontemporal_load(p + r); else v = p[r];
   return make_float4(v.x, v.y, v.z, v.w);
 }
+typedef const __attribute__((address_space(1))) row_v2f* lm_rows2_ptr;
+__device__ __forceinline__ float2 ld_row2(const lm_rows2_ptr p, const long long r) {
+  row_v2f v;
+  if constexpr (E3D_NT >= 1) v = __builtin_nontemporal_load(p + r); else v = p[r];
+  return make_float2(v.x, v.y);
+}
+// The twelve floats of row r.  SPLIT rows (LmSet::V1 set): the source half from the cloud's view, the target half from the pair's
+// two planes -- the same 48 bytes as the three planes of a legacy row, in four loads.  Which of the two a set holds is uniform for
+// the block and decided once, in front of the body (k_lm_pass, k_lm_cost_multi): each body carries the pointers of its layout only.
+template <bool SPLIT>
+struct LmRowPtrs {
+  lm_rows_ptr pa, pb, pc;      // legacy: A, B, C; split: V0, -, R1
+  lm_rows2_ptr pv1, pr0;       // split: V1, R0
+  __device__ __forceinline__ explicit LmRowPtrs(const LmSet& S)
+      : pa((lm_rows_ptr)S.A), pb((lm_rows_ptr)S.B), pc((lm_rows_ptr)S.C), pv1((lm_rows2_ptr)S.V1), pr0((lm_rows2_ptr)S.R0) {}
+  __device__ __forceinline__ void load(const long long r, float4& a, float4& b, float4& c) const {
+    a = ld_row(pa, r);
+    if constexpr (SPLIT) { const float2 v = ld_row2(pv1, r), t = ld_row2(pr0, r); b = make_float4(v.x, v.y, t.x, t.y); }
+    else b = ld_row(pb, r);
+    c = ld_row(pc, r);
+  }
+  // a split row without a partner (NaN in tp.x) becomes the all-zero row, before anything is computed from it
+  __device__ __forceinline__ void unmark(float4& a, float4& b, float4& c) const {
+    if constexpr (SPLIT) {
+      if (b.z != b.z) { a = make_float4(0.f, 0.f, 0.f, 0.f); b = a; c = a; }
+    }
+  }
+};
+__device__ __forceinline__ bool lm_block_is_split(const LmSet* __restrict__ sets, const int* __restrict__ block_set, const int gb) {
+  return sets[block_set[gb]].V1 != nullptr;
+}
 
 // A resident row's local halves into the global frame of the outer iteration: pcl::transformPointCloudWithNormals' operation
 // order (icp_point_to_plane.cc:192-195), i.e. the very roundings k_transform_bbox / k_compact_corr apply -- the pass then sees
@@ -2689,7 +2757,7 @@ __device__ __forceinline__ void row_to_global(const LmSet&, V4&, V4&, V4&) {}   
 //   UNR  correspondences per trip (1 or 2);
 //   PF   the next trip's float4 loads are issued before the current trip's arithmetic (at 2 - 3 waves per SIMD -- the f64
 //        accumulators -- the loads in flight per lane, not the occupancy, have to cover the HBM latency).
-template <int MODE, int UNR, bool PF>
+template <int MODE, int UNR, bool PF, bool SPLIT = false>
 __device__ __forceinline__ void lm_pass_body(const LmSet* __restrict__ sets, const int* __restrict__ block_set, const int block_base,
                                              double* __restrict__ partial) {
   constexpr bool kOne = (MODE == kModeOne);
@@ -2703,7 +2771,8 @@ __device__ __forceinline__ void lm_pass_body(const LmSet* __restrict__ sets, con
   for (int i = 0; i < NACC; ++i) acc[i] = 0.0;
 
   const long long stride = (long long)S.nblocks * kBlock;
-  const lm_rows_ptr pa = (lm_rows_ptr)S.A, pb = (lm_rows_ptr)S.B, pc = (lm_rows_ptr)S.C;
+  const LmRowPtrs<SPLIT> rows(S);
+  const lm_rows_ptr pa = rows.pa, pb = rows.pb, pc = rows.pc;      // (the two-row shape: legacy rows only)
   const lm_glist_ptr gl = (lm_glist_ptr)S.glist;
   const long long lane64 = threadIdx.x & 63;
   long long c = (long long)(gb - S.block_begin) * kBlock + threadIdx.x;
@@ -2730,6 +2799,7 @@ __device__ __forceinline__ void lm_pass_body(const LmSet* __restrict__ sets, con
     }
   } else {
     auto trip = [&](float4 ua, float4 ub, float4 uc) {
+      rows.unmark(ua, ub, uc);
       row_to_global(S, ua, ub, uc);
       CorrRowsT<float> R;
       lm_rows<MODE, float>(S, ua, ub, uc, R);
@@ -2743,22 +2813,22 @@ __device__ __forceinline__ void lm_pass_body(const LmSet* __restrict__ sets, con
       const int ng = (int)(S.n >> 6), gstride = S.nblocks * (kBlock / kWave);
       int gw = __builtin_amdgcn_readfirstlane((gb - S.block_begin) * (kBlock / kWave) + (int)(threadIdx.x >> 6));
       unsigned g0 = (gw < ng) ? gl[gw] : 0u, g1 = (gw + gstride < ng) ? gl[gw + gstride] : 0u;
-      if (gw < ng) { const long long r = ((long long)g0 << 6) | lane64; a0 = ld_row(pa, r); b0 = ld_row(pb, r); c0 = ld_row(pc, r); }
+      if (gw < ng) { const long long r = ((long long)g0 << 6) | lane64; rows.load(r, a0, b0, c0); }
       while (gw < ng) {
         const float4 ua = a0, ub = b0, uc = c0;
         gw += gstride;
         g0 = g1;
         if (gw + gstride < ng) g1 = gl[gw + gstride];
-        if (gw < ng) { const long long r = ((long long)g0 << 6) | lane64; a0 = ld_row(pa, r); b0 = ld_row(pb, r); c0 = ld_row(pc, r); }
+        if (gw < ng) { const long long r = ((long long)g0 << 6) | lane64; rows.load(r, a0, b0, c0); }
         trip(ua, ub, uc);
       }
     } else {
-      if (PF && c < S.n) { a0 = ld_row(pa, c); b0 = ld_row(pb, c); c0 = ld_row(pc, c); }
+      if (PF && c < S.n) { rows.load(c, a0, b0, c0); }
       while (c < S.n) {
-        if (!PF) { a0 = ld_row(pa, c); b0 = ld_row(pb, c); c0 = ld_row(pc, c); }
+        if (!PF) { rows.load(c, a0, b0, c0); }
         const float4 ua = a0, ub = b0, uc = c0;
         c += stride;
-        if (PF && c < S.n) { a0 = ld_row(pa, c); b0 = ld_row(pb, c); c0 = ld_row(pc, c); }
+        if (PF && c < S.n) { rows.load(c, a0, b0, c0); }
         trip(ua, ub, uc);
       }
     }
@@ -2808,7 +2878,8 @@ template <> struct LmCfg<kModeOne> { static constexpr int unr = 1; static conste
 template <int MODE>
 __global__ __launch_bounds__(kBlock, LmCfg<MODE>::minw) void k_lm_pass(const LmSet* __restrict__ sets, const int* __restrict__ block_set,
                                                                        int block_base, double* __restrict__ partial) {
-  lm_pass_body<MODE, LmCfg<MODE>::unr, LmCfg<MODE>::pf>(sets, block_set, block_base, partial);
+  if (lm_block_is_split(sets, block_set, block_base + (int)blockIdx.x)) lm_pass_body<MODE, LmCfg<MODE>::unr, LmCfg<MODE>::pf, true>(sets, block_set, block_base, partial);
+  else lm_pass_body<MODE, LmCfg<MODE>::unr, LmCfg<MODE>::pf, false>(sets, block_set, block_base, partial);
 }
 
 // a8, batched: the LM tries 1..9 of one inner iteration (lambda doubled each time, icp_point_to_plane_impl.h:216-283)
@@ -2828,7 +2899,7 @@ __global__ __launch_bounds__(kBlock, LmCfg<MODE>::minw) void k_lm_pass(const LmS
 // by row r1^2 then r2^2: the same sums as k_lm_pass<kModeCost>.
 constexpr int kLmCmRows = 1;
 
-template <bool PF, int U = kLmCmRows>
+template <bool PF, int U = kLmCmRows, bool SPLIT = false>
 __device__ __forceinline__ void lm_cost_multi_body(const LmSet* __restrict__ sets, const LmPose* __restrict__ poses, int n_sets,
                                                    int n_poses, const int* __restrict__ block_set, double* __restrict__ partial) {
   const int gb = blockIdx.x;
@@ -2838,7 +2909,7 @@ __device__ __forceinline__ void lm_cost_multi_body(const LmSet* __restrict__ set
 #pragma unroll
   for (int k = 0; k < kLmMaxPoses; ++k) acc[k] = 0.0;
   const long long stride = (long long)S.nblocks * kBlock;
-  const lm_rows_ptr pa = (lm_rows_ptr)S.A, pb = (lm_rows_ptr)S.B, pc = (lm_rows_ptr)S.C;
+  const LmRowPtrs<SPLIT> rows(S);
   const lm_glist_ptr gl = (lm_glist_ptr)S.glist;
   const long long lane64 = threadIdx.x & 63;
   const bool fixed_tgt = (S.mode == kModeOne && S.side == 0), fixed_src = (S.mode == kModeOne && S.side == 1);
@@ -2848,6 +2919,7 @@ __device__ __forceinline__ void lm_cost_multi_body(const LmSet* __restrict__ set
     CorrPts<float> F[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
+      rows.unmark(a[u], b[u], cc[u]);
       row_to_global(S, a[u], b[u], cc[u]);
       if (fixed_tgt) corr_tgt<float>(S.Rt, S.tt, b[u].z, b[u].w, cc[u].x, cc[u].y, cc[u].z, cc[u].w, F[u]);
       if (fixed_src) corr_src<float>(S.Rs, S.ts, a[u].x, a[u].y, a[u].z, a[u].w, b[u].x, b[u].y, F[u]);
@@ -2880,7 +2952,7 @@ __device__ __forceinline__ void lm_cost_multi_body(const LmSet* __restrict__ set
         const int gi = gw + u * gstride;
         valid[u] = gi < ng;
         const long long r = ((long long)gl[valid[u] ? gi : gw] << 6) | lane64;
-        a[u] = ld_row(pa, r); b[u] = ld_row(pb, r); cc[u] = ld_row(pc, r);
+        rows.load(r, a[u], b[u], cc[u]);
       }
       trip(a, b, cc, valid);
       gw += U * gstride;
@@ -2893,7 +2965,7 @@ __device__ __forceinline__ void lm_cost_multi_body(const LmSet* __restrict__ set
         const long long ci = c + u * stride;
         valid[u] = ci < S.n;
         const long long r = valid[u] ? ci : c;
-        a[u] = ld_row(pa, r); b[u] = ld_row(pb, r); cc[u] = ld_row(pc, r);
+        rows.load(r, a[u], b[u], cc[u]);
       }
       trip(a, b, cc, valid);
       c += U * stride;
@@ -2920,7 +2992,8 @@ __device__ __forceinline__ void lm_cost_multi_body(const LmSet* __restrict__ set
 __global__ __launch_bounds__(kBlock) void k_lm_cost_multi(const LmSet* __restrict__ sets, const LmPose* __restrict__ poses,
                                                           int n_sets, int n_poses, const int* __restrict__ block_set,
                                                           double* __restrict__ partial) {
-  lm_cost_multi_body<true>(sets, poses, n_sets, n_poses, block_set, partial);
+  if (lm_block_is_split(sets, block_set, (int)blockIdx.x)) lm_cost_multi_body<true, kLmCmRows, true>(sets, poses, n_sets, n_poses, block_set, partial);
+  else lm_cost_multi_body<true, kLmCmRows, false>(sets, poses, n_sets, n_poses, block_set, partial);
 }
 
 // one block per set: sum the set's block partials in a fixed order.  kRedParts threads share each of the
@@ -3197,12 +3270,17 @@ void launch_compact_corr(const int* match_pos, const unsigned* order, size_t n, 
                      block_offsets, Gsrc, LNsrc, Tsrc, Gtgt, LNtgt, Ttgt, A, B, C, out_base);
 }
 
-void launch_corr_update(const int* match, int* plane_match, const float* match_d2, size_t n, const float4* Psrc, const float4* LNsrc,
-                        bool src_global, const Affine& Tsrc, const float4* Ptgt, const float4* LNtgt, bool tgt_global, const Affine& Ttgt,
-                        float4* A, float4* B, float4* C, unsigned* block_counts, double* block_d2, unsigned* block_groups, hipStream_t s) {
+void launch_source_view(const float4* P, const float4* LN, size_t n, size_t cap, bool global, const Affine& T, float4* V0, float2* V1, hipStream_t s) {
+  if (!cap) return;
+  hipLaunchKernelGGL(k_source_view, dim3((unsigned)div_up(cap, kBlock)), dim3(kBlock), 0, s, P, LN, n, cap, global ? 1 : 0, T, V0, V1);
+}
+
+void launch_corr_update(const int* match, int* plane_match, const float* match_d2, size_t n, const float4* Ptgt, const float4* LNtgt,
+                        bool tgt_global, const Affine& Ttgt, float2* R0, float4* R1, unsigned* block_counts, double* block_d2,
+                        unsigned* block_groups, hipStream_t s) {
   if (!n) return;
-  hipLaunchKernelGGL(k_corr_update, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, s, match, plane_match, match_d2, n, Psrc,
-                     LNsrc, src_global ? 1 : 0, Tsrc, Ptgt, LNtgt, tgt_global ? 1 : 0, Ttgt, A, B, C, block_counts, block_d2, block_groups);
+  hipLaunchKernelGGL(k_corr_update, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, s, match, plane_match, match_d2, n, Ptgt, LNtgt,
+                     tgt_global ? 1 : 0, Ttgt, R0, R1, block_counts, block_d2, block_groups);
 }
 
 void launch_corr_totals(size_t n, const unsigned* block_counts, const double* block_d2, const unsigned* block_groups,

@@ -38,8 +38,14 @@ struct QueryRange { int lo[3]; unsigned D[3]; };
 //     correspondence, n = 64 * number of listed groups is the number of virtual rows the pass walks.  A half whose cloud can move
 //     is kept in the cloud's LOCAL frame and the pass applies the outer pose (Tos / Tot, PCL's operation order: the bits of G4)
 //     before the inner one, so a row only changes when the query's partner does (k_corr_update).
+//     SPLIT rows (V1 != nullptr; what the library keeps): the source half of row j is the source cloud's own point and normal at
+//     j, held once per cloud (its source view: V0 = {sp.xyz, sn.x}, V1 = {sn.yz}; here at this rank's slice) for every pair, and
+//     the pair holds the target half alone: R0 = {tp.xy}, R1 = {tp.z, tn.xyz}.  A = V0 and C = R1 then, B is not read.  A query
+//     without a partner has a NaN in tp.x and the passes read its row as twelve zeros.  V1 == nullptr: three planes as above
+//     (compacted rows, tools/micro).
 struct LmSet {
   const float4 *A, *B, *C; // row 0 of the pair's planes
+  const float2 *V1, *R0;   // split rows: the float2 planes of the source view and of the pair (else nullptr)
   const unsigned* glist;   // resident rows: indices of the active 64-row groups (ascending); nullptr: compacted rows
   long long n;             // (virtual) rows
   int block_begin, nblocks;
@@ -148,10 +154,10 @@ struct NnPairDev {
   float near2;
   GridDesc g; InvMap im; QueryRange qr; BoundParams bp;
   // resident rows (k_corr_update)
-  const float4 *Psrc, *LNsrc, *Ptgt, *LNtgt;
-  int src_global, tgt_global;
-  Affine Tsrc, Ttgt;
-  float4 *A, *B, *C;
+  const float4 *Ptgt, *LNtgt;      // the target's points (global frame if tgt_global, else local) and local normals
+  int tgt_global;
+  Affine Ttgt;
+  float2* R0; float4* R1;          // the pair's target-half planes
   int* plane_match;
   unsigned* glist;
   // per-block results of the row update that the certificate kernel writes itself for blocks it settles whole (round 6; nullptr: off)
@@ -232,14 +238,17 @@ void launch_match_d2_by_original(const int* match_pos, const float* match_d2, co
 void launch_lm_pass(int mode, const LmSet* sets, const int* block_set, int block_base, int nblocks, double* partial, hipStream_t s);
 void launch_lm_cost_multi(const LmSet* sets, const LmPose* poses, int n_sets, int n_poses, const int* block_set, int nblocks,
                           double* partial, hipStream_t s);
-// Resident rows of one directed pair (see LmSet): rewrites the rows whose partner changed since the planes were last brought up
-// to date (plane_match = the partner each row encodes, -1 zero row, anything else below -1 = never written), and produces the
+// The source view of a cloud (see LmSet): V0 / V1 for rows [0, n) from P (L4, or G4 if global) and the local normals LN (rotated by
+// T if global), zeros for rows [n, cap)
+void launch_source_view(const float4* P, const float4* LN, size_t n, size_t cap, bool global, const Affine& T, float4* V0, float2* V1, hipStream_t s);
+// Resident rows of one directed pair (see LmSet): rewrites the target halves of the rows whose partner changed since the planes were
+// last brought up to date (plane_match = the partner each row encodes, -1 marked row, anything else below -1 = never written), and produces the
 // per-block match counts / squared-distance sums (same arithmetic as launch_match_scan) plus the number of active 64-row groups
 // per block; launch_corr_totals then yields totals[0] = correspondences, totals[1] = active groups, totals[2] = rows rewritten
 // (chunk_groups: 2 x the number of 256-block chunks), total_d2 and the group list.
-void launch_corr_update(const int* match, int* plane_match, const float* match_d2, size_t n, const float4* Psrc, const float4* LNsrc,
-                        bool src_global, const Affine& Tsrc, const float4* Ptgt, const float4* LNtgt, bool tgt_global, const Affine& Ttgt,
-                        float4* A, float4* B, float4* C, unsigned* block_counts, double* block_d2, unsigned* block_groups, hipStream_t s);
+void launch_corr_update(const int* match, int* plane_match, const float* match_d2, size_t n, const float4* Ptgt, const float4* LNtgt,
+                        bool tgt_global, const Affine& Ttgt, float2* R0, float4* R1, unsigned* block_counts, double* block_d2,
+                        unsigned* block_groups, hipStream_t s);
 void launch_corr_totals(size_t n, const unsigned* block_counts, const double* block_d2, const unsigned* block_groups,
                         unsigned long long* chunk_sum, double* chunk_d2, unsigned* chunk_groups, unsigned long long* totals,
                         double* total_d2, unsigned* glist, hipStream_t s);
