@@ -15,21 +15,40 @@
 
 namespace e3d_host {
 
+// Every entry point the tools resolve, once: X(name) becomes a member of Api and a dlsym() in api().  A new entry point goes here
+// and nowhere else.
+#define E3D_API_LIST(X)                                                                                                \
+  X(e3d_abi_version) X(e3d_init) X(e3d_last_error)                                                                     \
+  X(e3d_icp_create) X(e3d_icp_destroy) X(e3d_icp_add_cloud) X(e3d_icp_run) X(e3d_icp_get_pose)                         \
+  X(e3d_transform_cloud) X(e3d_normals_knn) X(e3d_normals_radius) X(e3d_find_correspondences)                          \
+  X(e3d_reg_create) X(e3d_reg_destroy) X(e3d_reg_set_params) X(e3d_reg_set_point_scale)                                \
+  X(e3d_reg_set_intrinsics) X(e3d_reg_set_camera_mask) X(e3d_reg_get_intrinsics_level)                                 \
+  X(e3d_reg_set_image) X(e3d_reg_set_image_pose) X(e3d_reg_get_image_pose)                                             \
+  X(e3d_reg_set_rig) X(e3d_reg_get_rig) X(e3d_reg_add_rig_images) X(e3d_reg_set_rig_depth_residuals)                   \
+  X(e3d_reg_set_splat_points) X(e3d_reg_run_on_current_scale) X(e3d_reg_compute_cost)                                  \
+  X(e3d_determine_point_neighbors) X(e3d_reg_point_radius_minmax) X(e3d_merge_close_points)                            \
+  X(e3d_reg_add_occlusion_mesh) X(e3d_reg_set_occlusion_options) X(e3d_reg_set_cache_observations)                     \
+  X(e3d_reg_determine_observed_indices) X(e3d_reg_get_observed_indices) X(e3d_reg_set_observed_indices)                \
+  X(e3d_local_outlier_removal) X(e3d_reg_set_scan_points) X(e3d_reg_count_scan_observations)                           \
+  X(e3d_reg_get_scan_observation_counts) X(e3d_reg_ground_truth_depth) X(e3d_reg_scan_rendering)                       \
+  X(e3d_comm_create_all) X(e3d_comm_destroy) X(e3d_comm_abort) X(e3d_icp_set_comm) X(e3d_reg_set_comm)                 \
+  X(e3d_create_splats) X(e3d_render_cube_map)                                                                          \
+  X(e3d_reg_scan_colors_begin) X(e3d_reg_scan_colors_add_image) X(e3d_reg_scan_colors_get_sums)                        \
+  X(e3d_reg_scan_colors_set_sums) X(e3d_reg_scan_colors_finish)                                                        \
+  X(e3d_reg_mask_transfer_source) X(e3d_reg_mask_transfer_target)                                                      \
+  X(e3d_reg_pick_scan_points) X(e3d_reg_image_bearings) X(e3d_reg_project_points) X(e3d_pose_from_bearings)            \
+  X(e3d_reg_render_depth)                                                                                              \
+  X(e3d_edit_create) X(e3d_edit_destroy) X(e3d_edit_size) X(e3d_edit_get_points)                                       \
+  X(e3d_edit_get_selection) X(e3d_edit_set_selection) X(e3d_edit_selection_count)                                      \
+  X(e3d_edit_lasso) X(e3d_edit_beyond_plane) X(e3d_edit_pick)                                                          \
+  X(e3d_edit_delete_selected) X(e3d_edit_extract_selected) X(e3d_edit_kernel_ms)
+
 struct Api {
   void* handle = nullptr;
   int device_count = 0;
-#define E3D_FN(name) decltype(&::name) name = nullptr;
-  E3D_FN(e3d_abi_version) E3D_FN(e3d_init) E3D_FN(e3d_last_error) E3D_FN(e3d_icp_create) E3D_FN(e3d_icp_destroy)
-  E3D_FN(e3d_icp_add_cloud) E3D_FN(e3d_icp_run) E3D_FN(e3d_icp_get_pose) E3D_FN(e3d_transform_cloud)
-  E3D_FN(e3d_normals_knn) E3D_FN(e3d_normals_radius) E3D_FN(e3d_find_correspondences)
-  E3D_FN(e3d_reg_create) E3D_FN(e3d_reg_destroy) E3D_FN(e3d_reg_set_params) E3D_FN(e3d_reg_set_point_scale) E3D_FN(e3d_reg_set_intrinsics) E3D_FN(e3d_reg_set_camera_mask) E3D_FN(e3d_reg_get_intrinsics_level) E3D_FN(e3d_reg_set_image) E3D_FN(e3d_reg_set_image_pose) E3D_FN(e3d_reg_get_image_pose) E3D_FN(e3d_reg_set_rig) E3D_FN(e3d_reg_get_rig) E3D_FN(e3d_reg_add_rig_images) E3D_FN(e3d_reg_set_rig_depth_residuals) E3D_FN(e3d_reg_set_splat_points) E3D_FN(e3d_reg_run_on_current_scale) E3D_FN(e3d_reg_compute_cost) E3D_FN(e3d_determine_point_neighbors) E3D_FN(e3d_reg_point_radius_minmax) E3D_FN(e3d_merge_close_points) E3D_FN(e3d_reg_add_occlusion_mesh) E3D_FN(e3d_reg_set_occlusion_options) E3D_FN(e3d_reg_set_cache_observations) E3D_FN(e3d_reg_determine_observed_indices) E3D_FN(e3d_reg_get_observed_indices) E3D_FN(e3d_reg_set_observed_indices) E3D_FN(e3d_local_outlier_removal) E3D_FN(e3d_reg_set_scan_points) E3D_FN(e3d_reg_count_scan_observations) E3D_FN(e3d_reg_get_scan_observation_counts) E3D_FN(e3d_reg_ground_truth_depth) E3D_FN(e3d_reg_scan_rendering) E3D_FN(e3d_comm_create_all) E3D_FN(e3d_comm_destroy) E3D_FN(e3d_comm_abort) E3D_FN(e3d_icp_set_comm) E3D_FN(e3d_reg_set_comm)
-  E3D_FN(e3d_create_splats) E3D_FN(e3d_render_cube_map)
-  E3D_FN(e3d_reg_scan_colors_begin) E3D_FN(e3d_reg_scan_colors_add_image) E3D_FN(e3d_reg_scan_colors_get_sums) E3D_FN(e3d_reg_scan_colors_set_sums) E3D_FN(e3d_reg_scan_colors_finish)
-  E3D_FN(e3d_reg_mask_transfer_source) E3D_FN(e3d_reg_mask_transfer_target)
-  E3D_FN(e3d_reg_pick_scan_points) E3D_FN(e3d_reg_image_bearings) E3D_FN(e3d_reg_project_points) E3D_FN(e3d_pose_from_bearings)
-  E3D_FN(e3d_reg_render_depth)
-  E3D_FN(e3d_edit_create) E3D_FN(e3d_edit_destroy) E3D_FN(e3d_edit_size) E3D_FN(e3d_edit_get_points) E3D_FN(e3d_edit_get_selection) E3D_FN(e3d_edit_set_selection) E3D_FN(e3d_edit_selection_count) E3D_FN(e3d_edit_lasso) E3D_FN(e3d_edit_beyond_plane) E3D_FN(e3d_edit_pick) E3D_FN(e3d_edit_delete_selected) E3D_FN(e3d_edit_extract_selected) E3D_FN(e3d_edit_kernel_ms)
-#undef E3D_FN
+#define E3D_MEMBER(name) decltype(&::name) name = nullptr;
+  E3D_API_LIST(E3D_MEMBER)
+#undef E3D_MEMBER
 };
 
 inline std::string exe_dir() {
@@ -60,16 +79,7 @@ inline Api& api() {
 #define E3D_LOAD(name)                                                             \
   a.name = reinterpret_cast<decltype(a.name)>(dlsym(a.handle, #name));             \
   if (!a.name) { fprintf(stderr, "FATAL: libe3dhip.so lacks symbol %s\n", #name); exit(EXIT_FAILURE); }
-  E3D_LOAD(e3d_abi_version) E3D_LOAD(e3d_init) E3D_LOAD(e3d_last_error) E3D_LOAD(e3d_icp_create)
-  E3D_LOAD(e3d_icp_destroy) E3D_LOAD(e3d_icp_add_cloud) E3D_LOAD(e3d_icp_run) E3D_LOAD(e3d_icp_get_pose)
-  E3D_LOAD(e3d_transform_cloud) E3D_LOAD(e3d_normals_knn) E3D_LOAD(e3d_normals_radius) E3D_LOAD(e3d_find_correspondences)
-  E3D_LOAD(e3d_reg_create) E3D_LOAD(e3d_reg_destroy) E3D_LOAD(e3d_reg_set_params) E3D_LOAD(e3d_reg_set_point_scale) E3D_LOAD(e3d_reg_set_intrinsics) E3D_LOAD(e3d_reg_set_camera_mask) E3D_LOAD(e3d_reg_get_intrinsics_level) E3D_LOAD(e3d_reg_set_image) E3D_LOAD(e3d_reg_set_image_pose) E3D_LOAD(e3d_reg_get_image_pose) E3D_LOAD(e3d_reg_set_rig) E3D_LOAD(e3d_reg_get_rig) E3D_LOAD(e3d_reg_add_rig_images) E3D_LOAD(e3d_reg_set_rig_depth_residuals) E3D_LOAD(e3d_reg_set_splat_points) E3D_LOAD(e3d_reg_run_on_current_scale) E3D_LOAD(e3d_reg_compute_cost) E3D_LOAD(e3d_determine_point_neighbors) E3D_LOAD(e3d_reg_point_radius_minmax) E3D_LOAD(e3d_merge_close_points) E3D_LOAD(e3d_reg_add_occlusion_mesh) E3D_LOAD(e3d_reg_set_occlusion_options) E3D_LOAD(e3d_reg_set_cache_observations) E3D_LOAD(e3d_reg_determine_observed_indices) E3D_LOAD(e3d_reg_get_observed_indices) E3D_LOAD(e3d_reg_set_observed_indices) E3D_LOAD(e3d_local_outlier_removal) E3D_LOAD(e3d_reg_set_scan_points) E3D_LOAD(e3d_reg_count_scan_observations) E3D_LOAD(e3d_reg_get_scan_observation_counts) E3D_LOAD(e3d_reg_ground_truth_depth) E3D_LOAD(e3d_reg_scan_rendering) E3D_LOAD(e3d_comm_create_all) E3D_LOAD(e3d_comm_destroy) E3D_LOAD(e3d_comm_abort) E3D_LOAD(e3d_icp_set_comm) E3D_LOAD(e3d_reg_set_comm)
-  E3D_LOAD(e3d_create_splats) E3D_LOAD(e3d_render_cube_map)
-  E3D_LOAD(e3d_reg_scan_colors_begin) E3D_LOAD(e3d_reg_scan_colors_add_image) E3D_LOAD(e3d_reg_scan_colors_get_sums) E3D_LOAD(e3d_reg_scan_colors_set_sums) E3D_LOAD(e3d_reg_scan_colors_finish)
-  E3D_LOAD(e3d_reg_mask_transfer_source) E3D_LOAD(e3d_reg_mask_transfer_target)
-  E3D_LOAD(e3d_reg_pick_scan_points) E3D_LOAD(e3d_reg_image_bearings) E3D_LOAD(e3d_reg_project_points) E3D_LOAD(e3d_pose_from_bearings)
-  E3D_LOAD(e3d_reg_render_depth)
-  E3D_LOAD(e3d_edit_create) E3D_LOAD(e3d_edit_destroy) E3D_LOAD(e3d_edit_size) E3D_LOAD(e3d_edit_get_points) E3D_LOAD(e3d_edit_get_selection) E3D_LOAD(e3d_edit_set_selection) E3D_LOAD(e3d_edit_selection_count) E3D_LOAD(e3d_edit_lasso) E3D_LOAD(e3d_edit_beyond_plane) E3D_LOAD(e3d_edit_pick) E3D_LOAD(e3d_edit_delete_selected) E3D_LOAD(e3d_edit_extract_selected) E3D_LOAD(e3d_edit_kernel_ms)
+  E3D_API_LIST(E3D_LOAD)
 #undef E3D_LOAD
   if (a.e3d_abi_version() != E3D_ABI_VERSION) {
     fprintf(stderr, "FATAL: libe3dhip.so ABI version %d, expected %d\n", a.e3d_abi_version(), E3D_ABI_VERSION);

@@ -5,7 +5,6 @@
 // point visibility, depth maps) runs on the MI355X behind e3d_reg_count_scan_observations / e3d_reg_ground_truth_depth.
 // --write_scan_renderings: the image painted with the visible scan points (io_image.h decodes / encodes the colour images, the library
 // decides per pixel which point ends up on top).
-#include <exception>
 #include <zlib.h>
 
 #include <cmath>
@@ -66,7 +65,8 @@ static int run_tool(int argc, char** argv) {
     return EXIT_FAILURE;
   }
 
-  // opt::LoadPointClouds: scans in the global frame (pcl::transformPointCloud on the GPU)
+  // opt::LoadPointClouds: scans in the global frame (pcl::transformPointCloud on the GPU), kept apart until the upright rotation is
+  // done; a project without meshes is refused here, a cloud without points only after the rotation
   std::vector<MeshInfo> scan_infos;
   if (!ReadMeshLabProject(scan_alignment_path, &scan_infos) || scan_infos.empty()) {
     std::cerr << "Cannot read scan poses from " << scan_alignment_path << std::endl;
@@ -76,29 +76,14 @@ static int run_tool(int argc, char** argv) {
   const std::string project_dir = parent_path(scan_alignment_path);
   std::vector<std::vector<float>> scans(scan_infos.size());
   std::vector<uint8_t> all_colors;                             // r g b per scan point (pcl::PointXYZRGB; 0 0 0 without colour properties)
-  auto transform = [&](std::vector<float>& xyz, const float* T) {
-    if (xyz.empty()) return true;
-    std::vector<float> out(xyz.size());
-    float bmin[3], bmax[3];
-    if (api().e3d_transform_cloud(xyz.data(), nullptr, xyz.size() / 3, T, out.data(), nullptr, bmin, bmax) < 0) {
-      std::cerr << "transform failed: " << api().e3d_last_error() << std::endl;
-      return false;
-    }
-    xyz.swap(out);
-    return true;
-  };
   for (size_t i = 0; i < scan_infos.size(); ++i) {
-    PointCloud local;
-    const std::string filename = (!scan_infos[i].filename.empty() && scan_infos[i].filename[0] == '/') ? scan_infos[i].filename : join_path(project_dir, scan_infos[i].filename);
-    if (loadPLYFile(filename, local, write_scan_renderings) < 0) { std::cerr << "Cannot load scan point clouds." << std::endl; return EXIT_FAILURE; }
+    PointCloud global;                                         // colours only for the scan renderings
+    if (!load_scan(scan_infos[i], project_dir, /*want_rgb=*/write_scan_renderings, /*announce_unreadable=*/true, &global)) return EXIT_FAILURE;
     if (write_scan_renderings) {
-      if (local.rgb.size() != local.xyz.size()) local.rgb.assign(local.xyz.size(), 0);
-      all_colors.insert(all_colors.end(), local.rgb.begin(), local.rgb.end());
+      if (global.rgb.size() != global.xyz.size()) global.rgb.assign(global.xyz.size(), 0);
+      all_colors.insert(all_colors.end(), global.rgb.begin(), global.rgb.end());
     }
-    float T[12];
-    scan_infos[i].global_T_mesh.matrix3x4(T);
-    scans[i].swap(local.xyz);
-    if (!transform(scans[i], T)) return EXIT_FAILURE;
+    scans[i].swap(global.xyz);
   }
   std::cout << "Done." << std::endl;
 
@@ -128,7 +113,7 @@ static int run_tool(int argc, char** argv) {
           P[4 * r + c] = U[4 * r] * Mi[c] + U[4 * r + 1] * Mi[4 + c] + U[4 * r + 2] * Mi[8 + c] + (c == 3 ? U[4 * r + 3] : 0.f);
       P[15] = 1.f;
       scan_infos[i].global_T_mesh = Sim3f(P);
-      if (!transform(scans[i], U)) return EXIT_FAILURE;
+      if (!transform_points(scans[i], U)) return EXIT_FAILURE;
     }
   }
 
@@ -141,8 +126,6 @@ static int run_tool(int argc, char** argv) {
   }
   if (all_points.empty()) { std::cerr << "Point cloud is empty." << std::endl; return EXIT_FAILURE; }
 
-  problem.occlusion_mesh_path = occlusion_mesh_path;
-  problem.occlusion_splats_path = occlusion_mesh_path.empty() ? std::string() : occlusion_splats_path;   // splats only with a mesh (:314-319)
   if (!problem.InitializeStateFromColmapModel(state_path, image_base_path, std::unordered_set<int>())) return EXIT_FAILURE;
   if (rotate_first_scan_upright) {
     // global_T_image <- U * global_T_image (:333-339), i.e. image_T_global <- image_T_global * U^-1
@@ -151,7 +134,7 @@ static int run_tool(int argc, char** argv) {
   }
   if (!problem.InitializeImages()) return EXIT_FAILURE;
   if (!occlusion_mesh_path.empty()) std::cout << "Loading Occlusion mesh" << std::endl;
-  if (!problem.SetOcclusionGeometry(all_points, rotate_first_scan_upright ? U : nullptr)) return EXIT_FAILURE;
+  if (!problem.SetScanToolOcclusionGeometry(occlusion_mesh_path, occlusion_splats_path, all_points, rotate_first_scan_upright ? U : nullptr)) return EXIT_FAILURE;
 
   create_directories(output_folder_path);
   std::cout << "Writing COLMAP state file ..." << std::endl;
@@ -160,13 +143,12 @@ static int run_tool(int argc, char** argv) {
   std::cout << "Done." << std::endl;
 
   // Count observations of each scan point (:359-392)
-  if (api().e3d_reg_set_scan_points(problem.reg, all_points.data(), all_points.size() / 3) < 0) { std::cerr << api().e3d_last_error() << std::endl; return EXIT_FAILURE; }
+  if (!problem.SetScanPoints(all_points)) return EXIT_FAILURE;
   std::cout << "Count observations of each scan point, dismiss images with less than 2 scan point" << std::endl;
   const size_t images_nb = problem.images.size();
   constexpr int kEvalObs = 2;                                  // opt::MaskType::kEvalObs (image.h:43-47)
   auto load_mask = [&](const HostImage& im, const HostIntrinsics& in, GrayImage* mask) {
-    const std::string image_dir = path_parent(im.file_path), dataset_dir = path_parent(image_dir);
-    const std::string mask_path = dataset_dir + "/masks_for_images/" + path_filename(image_dir) + "/" + replace_extension(path_filename(im.file_path), "png");
+    const std::string mask_path = own_image_mask_path(im);
     *mask = GrayImage();
     if (!file_exists(mask_path)) return true;
     std::string err;
@@ -195,10 +177,9 @@ static int run_tool(int argc, char** argv) {
     create_directories(points_dir);
     std::vector<MlpMesh> out_meshes;
     for (size_t i = 0; i < scan_infos.size(); ++i) {
-      const std::string filename = (!scan_infos[i].filename.empty() && scan_infos[i].filename[0] == '/') ? scan_infos[i].filename : join_path(project_dir, scan_infos[i].filename);
       const std::string base_name = path_filename(scan_infos[i].filename);
       PointCloud cloud;
-      if (loadPLYFile(filename, cloud, false) >= 0) {
+      if (loadPLYFile(scan_file_path(project_dir, scan_infos[i]), cloud, false) >= 0) {
         std::vector<float> trimmed;
         const size_t n = std::min(cloud.size(), scan_offset[i + 1] - scan_offset[i]);
         for (size_t p = 0; p < n; ++p)
@@ -277,12 +258,4 @@ static int run_tool(int argc, char** argv) {
   return EXIT_SUCCESS;
 }
 
-// library errors (no device, out of memory, ...) arrive as exceptions of the host classes: report, EXIT_FAILURE
-int main(int argc, char** argv) {
-  try {
-    return run_tool(argc, argv);
-  } catch (const std::exception& e) {
-    std::cerr << "GroundTruthCreator: " << e.what() << std::endl;
-    return EXIT_FAILURE;
-  }
-}
+int main(int argc, char** argv) { return run_main("GroundTruthCreator", run_tool, argc, argv); }

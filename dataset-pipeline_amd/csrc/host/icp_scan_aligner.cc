@@ -249,13 +249,6 @@ static int run_tool(int argc, char** argv) {
   return EXIT_SUCCESS;
 }
 
-// Errors of the library (no device, out of memory, k beyond its limit, ...) surface as exceptions of the host classes: report them
-// and leave with EXIT_FAILURE like the tool's other error paths instead of std::terminate.
-int main(int argc, char** argv) {
-  try {
-    return run_tool(argc, argv);
-  } catch (const std::exception& e) {
-    std::cerr << "ICPScanAligner: " << e.what() << std::endl;
-    return EXIT_FAILURE;
-  }
-}
+// Errors of the library (no device, out of memory, k beyond its limit, ...) surface as exceptions of the host classes: run_main reports
+// them and leaves with EXIT_FAILURE like the tool's other error paths instead of std::terminate.
+int main(int argc, char** argv) { return run_main("ICPScanAligner", run_tool, argc, argv); }

@@ -25,8 +25,6 @@
 // Everything that can be refused is refused before the scans are read or the library is loaded.  A script without `pick` and `solve`
 // needs neither: it runs on the host alone.  The state is written as ImageRegistrator writes its final state (cameras.txt, images.txt,
 // points3D.txt, rigs.json).
-#include <exception>
-
 #include <cmath>
 #include <cstdlib>
 #include <fstream>
@@ -94,22 +92,6 @@ bool parse_script(const std::string& path, std::vector<ScriptLine>* out) {
     out->push_back(l);
   }
   return true;
-}
-
-bool all_digits(const std::string& s) {
-  if (s.empty()) return false;
-  for (char c : s) if (c < '0' || c > '9') return false;
-  return true;
-}
-int find_image(const Problem& problem, const std::string& image_base_path, const std::string& key) {
-  const std::string full = (!key.empty() && key[0] == '/') ? key : join_path(image_base_path, key);
-  for (const auto& kv : problem.images)
-    if (kv.second.file_path == full) return kv.first;
-  if (all_digits(key) && key.size() < 10) {
-    const int id = atoi(key.c_str());
-    if (problem.images.count(id)) return id;
-  }
-  return -1;
 }
 
 // Sophus' SE3f::exp of (upsilon | omega) in f32, sin and cos from the shared elementary functions: the rotation as a unit quaternion
@@ -195,15 +177,13 @@ bool distribute_relative_pose(Problem& problem, int image_id, std::vector<int>* 
 }
 
 int run_tool(int argc, char** argv) {
-  std::string scan_alignment_path, occlusion_mesh_path, occlusion_splats_path, image_base_path, state_path, output_folder_path,
-      camera_ids_to_ignore_string, script_path;
+  std::string scan_alignment_path, occlusion_mesh_path, occlusion_splats_path, image_base_path, state_path, output_folder_path, script_path;
   parse_argument(argc, argv, "--scan_alignment_path", scan_alignment_path);
   parse_argument(argc, argv, "--occlusion_mesh_path", occlusion_mesh_path);
   parse_argument(argc, argv, "--occlusion_splats_path", occlusion_splats_path);
   parse_argument(argc, argv, "--image_base_path", image_base_path);
   parse_argument(argc, argv, "--state_path", state_path);
   parse_argument(argc, argv, "--output_folder_path", output_folder_path);
-  parse_argument(argc, argv, "--camera_ids_to_ignore", camera_ids_to_ignore_string);
   parse_argument(argc, argv, "--script", script_path);
 
   Problem problem;
@@ -225,16 +205,14 @@ int run_tool(int argc, char** argv) {
   }
 
   // the state; then the rest of what can be refused: image names, solve without enough correspondences, an image without a rig
-  std::unordered_set<int> camera_ids_to_ignore;
-  for (const std::string& id : SplitStringIntoSet(',', camera_ids_to_ignore_string)) camera_ids_to_ignore.insert(atoi(id.c_str()));
-  if (!problem.InitializeStateFromColmapModel(state_path, image_base_path, camera_ids_to_ignore)) return EXIT_FAILURE;
+  if (!problem.InitializeStateFromColmapModel(state_path, image_base_path, parse_camera_ids_to_ignore(argc, argv))) return EXIT_FAILURE;
   std::vector<ColmapRig> rig_vector;
   if (ReadColmapRigs(state_path + "/rigs.json", &rig_vector) && !problem.AssignRigs(rig_vector)) return EXIT_FAILURE;
   {
     int current = -1, pending = 0;
     for (ScriptLine& l : script) {
       if (l.op == Op::kImage) {
-        current = find_image(problem, image_base_path, l.name);
+        current = problem.FindImage(image_base_path, l.name);
         if (current < 0) { std::cerr << script_path << ":" << l.line << ": " << l.name << " is not an image of the state." << std::endl; return EXIT_FAILURE; }
         pending = 0;
       }
@@ -256,6 +234,7 @@ int run_tool(int argc, char** argv) {
 
   std::vector<float> all_points;
   if (needs_device) {
+    // opt::LoadPointClouds as in MaskTransfer: concatenated (an empty scan adds nothing), a project without meshes is refused
     std::vector<MeshInfo> scan_infos;
     if (!ReadMeshLabProject(scan_alignment_path, &scan_infos) || scan_infos.empty()) {
       std::cerr << "Cannot read scan poses from " << scan_alignment_path << std::endl;
@@ -264,23 +243,12 @@ int run_tool(int argc, char** argv) {
     std::cout << "Loading point clouds ..." << std::endl;
     const std::string project_dir = parent_path(scan_alignment_path);
     for (const MeshInfo& info : scan_infos) {
-      PointCloud local;
-      const std::string filename = (!info.filename.empty() && info.filename[0] == '/') ? info.filename : join_path(project_dir, info.filename);
-      if (loadPLYFile(filename, local, false) < 0) { std::cerr << "Cannot load scan point clouds." << std::endl; return EXIT_FAILURE; }
-      if (local.xyz.empty()) continue;
-      float T[12], bmin[3], bmax[3];
-      info.global_T_mesh.matrix3x4(T);
-      std::vector<float> global(local.xyz.size());
-      if (api().e3d_transform_cloud(local.xyz.data(), nullptr, local.xyz.size() / 3, T, global.data(), nullptr, bmin, bmax) < 0) {
-        std::cerr << "transform failed: " << api().e3d_last_error() << std::endl;
-        return EXIT_FAILURE;
-      }
-      all_points.insert(all_points.end(), global.begin(), global.end());
+      PointCloud global;
+      if (!load_scan(info, project_dir, /*want_rgb=*/false, /*announce_unreadable=*/true, &global)) return EXIT_FAILURE;
+      all_points.insert(all_points.end(), global.xyz.begin(), global.xyz.end());
     }
     std::cout << "Done." << std::endl;
     if (all_points.empty()) { std::cerr << "Point cloud is empty." << std::endl; return EXIT_FAILURE; }
-    problem.occlusion_mesh_path = occlusion_mesh_path;
-    problem.occlusion_splats_path = occlusion_mesh_path.empty() ? std::string() : occlusion_splats_path;
     // the device holds every image on its own: this tool moves single images, the rig is applied by distribute_relative_pose alone
     std::vector<HostRig> rigs;
     std::vector<HostRigImages> rig_images;
@@ -288,8 +256,8 @@ int run_tool(int argc, char** argv) {
     const bool initialised = problem.InitializeImages();
     rigs.swap(problem.rigs); rig_images.swap(problem.rig_images);
     if (!initialised) return EXIT_FAILURE;
-    if (!problem.SetOcclusionGeometry(all_points, nullptr)) return EXIT_FAILURE;
-    if (has_pick && api().e3d_reg_set_scan_points(problem.reg, all_points.data(), all_points.size() / 3) < 0) { std::cerr << api().e3d_last_error() << std::endl; return EXIT_FAILURE; }
+    if (!problem.SetScanToolOcclusionGeometry(occlusion_mesh_path, occlusion_splats_path, all_points, nullptr)) return EXIT_FAILURE;   // no "Loading Occlusion mesh" line here
+    if (has_pick && !problem.SetScanPoints(all_points)) return EXIT_FAILURE;
   }
   auto push_pose = [&](int image_id) {
     if (!needs_device) return true;
@@ -432,12 +400,4 @@ int run_tool(int argc, char** argv) {
 
 }  // namespace
 
-// library errors (no device, out of memory, ...) arrive as exceptions of the host classes: report, EXIT_FAILURE
-int main(int argc, char** argv) {
-  try {
-    return run_tool(argc, argv);
-  } catch (const std::exception& e) {
-    std::cerr << "ImageLocalizer: " << e.what() << std::endl;
-    return EXIT_FAILURE;
-  }
-}
+int main(int argc, char** argv) { return run_main("ImageLocalizer", run_tool, argc, argv); }

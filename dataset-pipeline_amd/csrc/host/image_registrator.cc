@@ -7,7 +7,6 @@
 // Observations are cached like in the reference: from the second image scale on (or from the first with
 // --cache_observations 1) the visible point lists are fixed and kept in --observations_cache_path.
 // --write_debug_point_clouds 1 writes the scans coloured by the images (initial_point_cloud.ply, scale_<factor>_final_point_cloud.ply).
-#include <exception>
 #include <cmath>
 #include <cstdlib>
 #include <iostream>
@@ -45,8 +44,7 @@ static int run_tool(int argc, char** argv) {
   int gpus = 1;     // not a flag of the reference: GPUs of this node to shard the images over (image id mod N)
   parse_argument(argc, argv, "--gpus", gpus);
   if (gpus > 1 && !set_gpu_count(gpus)) return EXIT_FAILURE;
-  std::unordered_set<int> camera_ids_to_ignore;
-  for (const std::string& id : SplitStringIntoSet(',', camera_ids_to_ignore_string)) camera_ids_to_ignore.insert(atoi(id.c_str()));
+  const std::unordered_set<int> camera_ids_to_ignore = parse_camera_ids_to_ignore(argc, argv);
 
   Problem problem;
   if (!problem.prm.SetFromArguments(argc, argv)) return EXIT_FAILURE;
@@ -65,7 +63,8 @@ static int run_tool(int argc, char** argv) {
   if (occlusion_mesh_path.empty() && occlusion_splats_path.empty()) std::cout << "No occlusion meshes given, using 2D splats." << std::endl;
   create_directories(output_folder_path);
 
-  // scans -> global frame (pcl::transformPointCloud on the GPU); their points are the occlusion splats
+  // scans -> global frame (pcl::transformPointCloud on the GPU); their points are the occlusion splats.  A project without meshes is
+  // read and then refused as an empty cloud; an unreadable project gets both messages
   std::vector<MeshInfo> scan_infos;
   if (!ReadMeshLabProject(scan_alignment_path, &scan_infos)) {
     std::cerr << "Cannot read scan poses from " << scan_alignment_path << std::endl;
@@ -77,22 +76,12 @@ static int run_tool(int argc, char** argv) {
   std::vector<PointCloud::Ptr> colored_scans;
   const std::string project_dir = parent_path(scan_alignment_path);
   for (const MeshInfo& info : scan_infos) {
-    PointCloud local;
-    const std::string filename = (!info.filename.empty() && info.filename[0] == '/') ? info.filename : join_path(project_dir, info.filename);
-    if (loadPLYFile(filename, local, /*want_rgb=*/true) < 0) { std::cerr << "Cannot load scan point clouds." << std::endl; return EXIT_FAILURE; }
-    float T[12], bmin[3], bmax[3];
-    info.global_T_mesh.matrix3x4(T);
     PointCloud::Ptr global(new PointCloud());
-    global->xyz.resize(local.xyz.size());
-    global->rgb.swap(local.rgb);
-    if (local.size() > 0 && api().e3d_transform_cloud(local.xyz.data(), nullptr, local.size(), T, global->xyz.data(), nullptr, bmin, bmax) < 0) {
-      std::cerr << "transform failed: " << api().e3d_last_error() << std::endl;
-      return EXIT_FAILURE;
-    }
+    if (!load_scan(info, project_dir, /*want_rgb=*/true, /*announce_unreadable=*/true, global.get())) return EXIT_FAILURE;
     occlusion_points.insert(occlusion_points.end(), global->xyz.begin(), global->xyz.end());
-    colored_scans.push_back(global);
+    colored_scans.push_back(global);                           // an empty scan stays, as an empty cloud
   }
-  if (occlusion_points.empty()) { std::cerr << "Point cloud is empty." << std::endl; return EXIT_FAILURE; }
+  if (occlusion_points.empty()) { std::cerr << "Point cloud is empty." << std::endl; return EXIT_FAILURE; }   // before "Done.", unlike the other tools
   std::cout << "Done." << std::endl;
 
   if (gpus > 1 && !file_exists(multi_res_point_cloud_directory_path + "/metadata.txt")) {
@@ -202,12 +191,4 @@ static int run_tool(int argc, char** argv) {
   return EXIT_SUCCESS;
 }
 
-// library errors (no device, out of memory, ...) arrive as exceptions of the host classes: report, EXIT_FAILURE
-int main(int argc, char** argv) {
-  try {
-    return run_tool(argc, argv);
-  } catch (const std::exception& e) {
-    std::cerr << "ImageRegistrator: " << e.what() << std::endl;
-    return EXIT_FAILURE;
-  }
-}
+int main(int argc, char** argv) { return run_main("ImageRegistrator", run_tool, argc, argv); }

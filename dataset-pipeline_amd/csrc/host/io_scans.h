@@ -1,6 +1,7 @@
-// Scan loading shared by NormalEstimator and ImageRegistrator: MeshLab project poses as Sophus::Sim3f with the global
-// scale_factor [QUIRK] (io::ReadMeshLabProject, src/io/meshlab_project.cc:39-87; opt::GlobalParameters().scale_factor,
-// src/opt/parameters.h:63).
+// The scan poses of every tool that reads a MeshLab project of scans or meshes: the project's poses as Sophus::Sim3f with the
+// global scale_factor [QUIRK] (io::ReadMeshLabProject, src/io/meshlab_project.cc:39-87; opt::GlobalParameters().scale_factor,
+// src/opt/parameters.h:63).  Host only (SfMScaleEstimator includes it through io_colmap.h and links without -ldl); loading a
+// scan's points into the global frame needs the library and is in scan_loader.h.
 #pragma once
 
 #include <cmath>

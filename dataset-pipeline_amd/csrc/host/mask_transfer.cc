@@ -16,8 +16,6 @@
 //   --in_place 1               overwrite / create the targets' own mask files ("Save image mask"); exactly one of the two
 // Per target one line on stdout with the three numbers of the transfer; a target whose merged mask equals its existing mask (or is
 // all zero without one) is reported and not written.
-#include <exception>
-
 #include <cstdlib>
 #include <iostream>
 #include <string>
@@ -27,12 +25,6 @@
 #include "opt_problem.h"
 
 using namespace e3d_host;
-
-// Image::GetImageMaskPath (image.cc): <dataset>/masks_for_images/<camera dir>/<name>.png next to <dataset>/<images>/<camera dir>/<name>
-static std::string mask_path_in(const std::string& dataset_dir, const HostImage& im) {
-  return dataset_dir + "/masks_for_images/" + path_filename(path_parent(im.file_path)) + "/" + replace_extension(path_filename(im.file_path), "png");
-}
-static std::string own_mask_path(const HostImage& im) { return mask_path_in(path_parent(path_parent(im.file_path)), im); }
 
 // a level-0 mask file: the camera's size, values 0 / 1 / 2 (image.cc:77-97)
 static bool load_mask_file(const std::string& path, const HostIntrinsics& in, GrayImage* mask) {
@@ -45,34 +37,15 @@ static bool load_mask_file(const std::string& path, const HostIntrinsics& in, Gr
   return true;
 }
 
-static bool all_digits(const std::string& s) {
-  if (s.empty()) return false;
-  for (char c : s) if (c < '0' || c > '9') return false;
-  return true;
-}
-
-// an image by its name in images.txt (relative to --image_base_path, or absolute) or by its image id; -1 if there is none
-static int find_image(const Problem& problem, const std::string& image_base_path, const std::string& key) {
-  const std::string full = (!key.empty() && key[0] == '/') ? key : join_path(image_base_path, key);
-  for (const auto& kv : problem.images)
-    if (kv.second.file_path == full) return kv.first;
-  if (all_digits(key) && key.size() < 10) {
-    const int id = atoi(key.c_str());
-    if (problem.images.count(id)) return id;
-  }
-  return -1;
-}
-
 static int run_tool(int argc, char** argv) {
   std::string scan_alignment_path, occlusion_mesh_path, occlusion_splats_path, image_base_path, state_path, output_folder_path,
-      camera_ids_to_ignore_string, source_image, target_images;
+      source_image, target_images;
   parse_argument(argc, argv, "--scan_alignment_path", scan_alignment_path);
   parse_argument(argc, argv, "--occlusion_mesh_path", occlusion_mesh_path);
   parse_argument(argc, argv, "--occlusion_splats_path", occlusion_splats_path);
   parse_argument(argc, argv, "--image_base_path", image_base_path);
   parse_argument(argc, argv, "--state_path", state_path);
   parse_argument(argc, argv, "--output_folder_path", output_folder_path);
-  parse_argument(argc, argv, "--camera_ids_to_ignore", camera_ids_to_ignore_string);
   parse_argument(argc, argv, "--source_image", source_image);
   parse_argument(argc, argv, "--target_images", target_images);
   bool transfer_eval_obs = false, in_place = false;
@@ -95,10 +68,8 @@ static int run_tool(int argc, char** argv) {
   }
 
   // the state, the images of the transfer and the source's mask: everything that can be refused is refused before the scans are read
-  std::unordered_set<int> camera_ids_to_ignore;
-  for (const std::string& id : SplitStringIntoSet(',', camera_ids_to_ignore_string)) camera_ids_to_ignore.insert(atoi(id.c_str()));
-  if (!problem.InitializeStateFromColmapModel(state_path, image_base_path, camera_ids_to_ignore)) return EXIT_FAILURE;
-  const int source_id = find_image(problem, image_base_path, source_image);
+  if (!problem.InitializeStateFromColmapModel(state_path, image_base_path, parse_camera_ids_to_ignore(argc, argv))) return EXIT_FAILURE;
+  const int source_id = problem.FindImage(image_base_path, source_image);
   if (source_id < 0) { std::cerr << "--source_image " << source_image << " is not an image of the state." << std::endl; return EXIT_FAILURE; }
   std::vector<int> targets;
   if (target_images.empty()) {
@@ -110,7 +81,7 @@ static int run_tool(int argc, char** argv) {
       const std::string key = target_images.substr(begin, end - begin);
       begin = end + 1;
       if (key.empty()) continue;
-      const int id = find_image(problem, image_base_path, key);
+      const int id = problem.FindImage(image_base_path, key);
       if (id < 0) { std::cerr << "--target_images: " << key << " is not an image of the state." << std::endl; return EXIT_FAILURE; }
       bool seen = false;
       for (int t : targets) seen = seen || t == id;
@@ -119,7 +90,7 @@ static int run_tool(int argc, char** argv) {
   }
   if (targets.empty()) { std::cerr << "No target images." << std::endl; return EXIT_FAILURE; }
   const HostImage& source = problem.images[source_id];
-  const std::string source_mask_path = own_mask_path(source);
+  const std::string source_mask_path = own_image_mask_path(source);
   if (!file_exists(source_mask_path)) {
     std::cerr << "The source image " << source.file_path << " has no mask (" << source_mask_path << "): nothing to transfer." << std::endl;
     return EXIT_FAILURE;
@@ -127,7 +98,7 @@ static int run_tool(int argc, char** argv) {
   GrayImage source_mask;
   if (!load_mask_file(source_mask_path, problem.intrinsics_list[source.intrinsics_id], &source_mask)) return EXIT_FAILURE;
 
-  // opt::LoadPointClouds: scans in the global frame
+  // opt::LoadPointClouds: scans in the global frame, concatenated (an empty scan adds nothing); a project without meshes is refused
   std::vector<MeshInfo> scan_infos;
   if (!ReadMeshLabProject(scan_alignment_path, &scan_infos) || scan_infos.empty()) {
     std::cerr << "Cannot read scan poses from " << scan_alignment_path << std::endl;
@@ -137,28 +108,17 @@ static int run_tool(int argc, char** argv) {
   const std::string project_dir = parent_path(scan_alignment_path);
   std::vector<float> all_points;
   for (const MeshInfo& info : scan_infos) {
-    PointCloud local;
-    const std::string filename = (!info.filename.empty() && info.filename[0] == '/') ? info.filename : join_path(project_dir, info.filename);
-    if (loadPLYFile(filename, local, false) < 0) { std::cerr << "Cannot load scan point clouds." << std::endl; return EXIT_FAILURE; }
-    if (local.xyz.empty()) continue;
-    float T[12], bmin[3], bmax[3];
-    info.global_T_mesh.matrix3x4(T);
-    std::vector<float> global(local.xyz.size());
-    if (api().e3d_transform_cloud(local.xyz.data(), nullptr, local.xyz.size() / 3, T, global.data(), nullptr, bmin, bmax) < 0) {
-      std::cerr << "transform failed: " << api().e3d_last_error() << std::endl;
-      return EXIT_FAILURE;
-    }
-    all_points.insert(all_points.end(), global.begin(), global.end());
+    PointCloud global;
+    if (!load_scan(info, project_dir, /*want_rgb=*/false, /*announce_unreadable=*/true, &global)) return EXIT_FAILURE;
+    all_points.insert(all_points.end(), global.xyz.begin(), global.xyz.end());
   }
   std::cout << "Done." << std::endl;
   if (all_points.empty()) { std::cerr << "Point cloud is empty." << std::endl; return EXIT_FAILURE; }
 
-  problem.occlusion_mesh_path = occlusion_mesh_path;
-  problem.occlusion_splats_path = occlusion_mesh_path.empty() ? std::string() : occlusion_splats_path;   // splats only with a mesh
   if (!problem.InitializeImages()) return EXIT_FAILURE;
   if (!occlusion_mesh_path.empty()) std::cout << "Loading Occlusion mesh" << std::endl;
-  if (!problem.SetOcclusionGeometry(all_points, nullptr)) return EXIT_FAILURE;
-  if (api().e3d_reg_set_scan_points(problem.reg, all_points.data(), all_points.size() / 3) < 0) { std::cerr << api().e3d_last_error() << std::endl; return EXIT_FAILURE; }
+  if (!problem.SetScanToolOcclusionGeometry(occlusion_mesh_path, occlusion_splats_path, all_points, nullptr)) return EXIT_FAILURE;
+  if (!problem.SetScanPoints(all_points)) return EXIT_FAILURE;
 
   const int64_t labelled = api().e3d_reg_mask_transfer_source(problem.reg, source_id, source_mask.data.data(), transfer_eval_obs ? 1 : 0);
   if (labelled < 0) { std::cerr << "label transfer failed: " << api().e3d_last_error() << std::endl; return EXIT_FAILURE; }
@@ -169,7 +129,7 @@ static int run_tool(int argc, char** argv) {
   for (int target_id : targets) {
     const HostImage& im = problem.images[target_id];
     const HostIntrinsics& in = problem.intrinsics_list[im.intrinsics_id];
-    const std::string existing_path = own_mask_path(im);
+    const std::string existing_path = own_image_mask_path(im);
     GrayImage existing;
     if (file_exists(existing_path) && !load_mask_file(existing_path, in, &existing)) return EXIT_FAILURE;
     GrayImage merged;
@@ -182,7 +142,7 @@ static int run_tool(int argc, char** argv) {
     }
     std::cout << "Target image " << target_id << " " << im.file_path << ": point_pass " << stats[0] << " filled " << stats[1] << " changed " << stats[2];
     if (stats[2] == 0) { std::cout << " -- unchanged, not written" << std::endl; continue; }
-    const std::string out_path = in_place ? existing_path : mask_path_in(output_folder_path, im);
+    const std::string out_path = in_place ? existing_path : image_mask_path(output_folder_path, im);
     create_directories(parent_path(out_path));
     std::string err;
     if (!imwrite_gray(out_path, merged, &err)) { std::cout << std::endl; std::cerr << err << std::endl; return EXIT_FAILURE; }
@@ -193,12 +153,4 @@ static int run_tool(int argc, char** argv) {
   return EXIT_SUCCESS;
 }
 
-// library errors (no device, out of memory, ...) arrive as exceptions of the host classes: report, EXIT_FAILURE
-int main(int argc, char** argv) {
-  try {
-    return run_tool(argc, argv);
-  } catch (const std::exception& e) {
-    std::cerr << "MaskTransfer: " << e.what() << std::endl;
-    return EXIT_FAILURE;
-  }
-}
+int main(int argc, char** argv) { return run_main("MaskTransfer", run_tool, argc, argv); }

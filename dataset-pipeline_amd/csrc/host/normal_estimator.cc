@@ -14,6 +14,7 @@
 #include "io_ply.h"
 #include "io_scans.h"
 #include "normal_estimation.h"
+#include "scan_loader.h"
 #include "util.h"
 
 using namespace e3d_host;
@@ -39,26 +40,14 @@ int main(int argc, char** argv) {
     return EXIT_FAILURE;
   }
 
-  // load every scan and transform it into the global frame (pcl::transformPointCloud, f32, on the GPU)
+  // load every scan and transform it into the global frame (pcl::transformPointCloud, f32, on the GPU).  Nothing is printed around
+  // the loop, an unreadable scan gets the PLY reader's line only, and a project without meshes gives an empty output file
   std::vector<PointCloud::Ptr> global_clouds(scan_infos.size());
   size_t total = 0;
   for (size_t i = 0; i < scan_infos.size(); ++i) {
-    const MeshInfo& info = scan_infos[i];
-    PointCloud local;
-    const std::string filename = (info.filename[0] == '/') ? info.filename : join_path(project_dir, info.filename);
-    if (loadPLYFile(filename, local, /*want_rgb=*/true) < 0) return EXIT_FAILURE;
-    float T[12];
-    info.global_T_mesh.matrix3x4(T);
     global_clouds[i].reset(new PointCloud());
-    global_clouds[i]->xyz.resize(local.xyz.size());
-    global_clouds[i]->rgb.swap(local.rgb);
-    float bmin[3], bmax[3];
-    if (local.size() > 0 &&
-        api().e3d_transform_cloud(local.xyz.data(), nullptr, local.size(), T, global_clouds[i]->xyz.data(), nullptr, bmin, bmax) < 0) {
-      std::cerr << "transform failed: " << api().e3d_last_error() << std::endl;
-      return EXIT_FAILURE;
-    }
-    total += local.size();
+    if (!load_scan(scan_infos[i], project_dir, /*want_rgb=*/true, /*announce_unreadable=*/false, global_clouds[i].get())) return EXIT_FAILURE;
+    total += global_clouds[i]->size();
   }
 
   std::vector<unsigned char> out(total * 27);

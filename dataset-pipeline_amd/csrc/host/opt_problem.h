@@ -12,6 +12,8 @@
 //   fixed descriptors                       src/opt/problem.cc:549-572
 //   io::ExportProblemToColmap / ExportRigs  src/io/colmap_model.cc:286-516
 //   Problem::DebugWriteColoredPointCloud    src/opt/problem.cc:642-704 (visibility and colour sampling on the GPU)
+// and what the tools around ImageRegistrator share on top of it: image_mask_path / own_image_mask_path (Image::GetImageMaskPath),
+// Problem::FindImage, Problem::SetScanToolOcclusionGeometry and Problem::SetScanPoints.  The scans themselves: scan_loader.h.
 #pragma once
 
 #include <sys/stat.h>
@@ -34,6 +36,7 @@
 #include "io_image.h"
 #include "io_ply.h"
 #include "io_scans.h"
+#include "scan_loader.h"
 #include "util.h"
 
 namespace e3d_host {
@@ -214,6 +217,19 @@ struct HostImage {
 struct HostRig { int rig_id = 0; std::vector<std::string> folder_names; std::vector<Pose7> image_T_rig; };
 struct HostRigImages { int rig_images_id = 0, rig_id = 0; std::vector<int> image_ids; };
 
+// Image::GetImageMaskPath (image.cc): <dataset>/masks_for_images/<camera dir>/<name>.png next to <dataset>/<images>/<camera dir>/<name>;
+// the image's own mask, and the same place under another dataset directory (MaskTransfer's --output_folder_path)
+inline std::string image_mask_path(const std::string& dataset_dir, const HostImage& im) {
+  return dataset_dir + "/masks_for_images/" + path_filename(path_parent(im.file_path)) + "/" + replace_extension(path_filename(im.file_path), "png");
+}
+inline std::string own_image_mask_path(const HostImage& im) { return image_mask_path(path_parent(path_parent(im.file_path)), im); }
+
+inline bool all_digits(const std::string& s) {
+  if (s.empty()) return false;
+  for (char c : s) if (c < '0' || c > '9') return false;
+  return true;
+}
+
 inline int camera_model_from_name(const std::string& name) {
   if (name == "PINHOLE") return E3D_CAMERA_PINHOLE;
   if (name == "OPENCV") return E3D_CAMERA_OPENCV;
@@ -338,6 +354,18 @@ class Problem {
     }
     if (images.size() < 2) return fail("Less than 2 images defined.");
     return true;
+  }
+
+  // an image by its name in images.txt (relative to image_base_path, or absolute) or by its image id; -1 if there is none
+  int FindImage(const std::string& image_base_path, const std::string& key) const {
+    const std::string full = (!key.empty() && key[0] == '/') ? key : join_path(image_base_path, key);
+    for (const auto& kv : images)
+      if (kv.second.file_path == full) return kv.first;
+    if (all_digits(key) && key.size() < 10) {
+      const int id = atoi(key.c_str());
+      if (images.count(id)) return id;
+    }
+    return -1;
   }
 
   // opt::AssignRigs
@@ -536,8 +564,7 @@ class Problem {
       for (const MeshInfo& info : infos) {
         float T[12];
         info.global_T_mesh.matrix3x4(T);
-        const std::string file = (!info.filename.empty() && info.filename[0] == '/') ? info.filename : join_path(parent_path(path), info.filename);
-        if (!add(file, T)) return false;
+        if (!add(scan_file_path(parent_path(path), info), T)) return false;
       }
       std::cout << "Done." << std::endl;
       return true;
@@ -773,8 +800,7 @@ class Problem {
           d.g = imread_gray(wim.file_path, &d.err);
           if (d.g.empty() || d.g.width != win.width || d.g.height != win.height) continue;
           d.pyr = build_image_pyramid(d.g, wlevels);
-          const std::string wdir = path_parent(wim.file_path);
-          d.mask_path = path_parent(wdir) + "/masks_for_images/" + path_filename(wdir) + "/" + replace_extension(path_filename(wim.file_path), "png");
+          d.mask_path = own_image_mask_path(wim);
           if (file_exists(d.mask_path)) {
             std::string merr;
             GrayImage m = imread_gray(d.mask_path, &merr);
@@ -867,6 +893,19 @@ class Problem {
       if (!occlusion_mesh_path.empty() && !AddOcclusionMesh(occlusion_mesh_path, true, left)) return false;
       if (!occlusion_splats_path.empty() && !AddOcclusionMesh(occlusion_splats_path, false, left)) return false;
     }
+    return true;
+  }
+
+  // The occlusion geometry of the tools that work on the scans themselves (GroundTruthCreator, MaskTransfer, ImageLocalizer), after
+  // InitializeImages: as above, but occlusion splats count only with a mesh (ground_truth_creator.cc:314-319)
+  bool SetScanToolOcclusionGeometry(const std::string& mesh_path, const std::string& splats_path, const std::vector<float>& scan_points, const float* left) {
+    occlusion_mesh_path = mesh_path;
+    occlusion_splats_path = mesh_path.empty() ? std::string() : splats_path;
+    return SetOcclusionGeometry(scan_points, left);
+  }
+  // ... and the scan points (n x 3, global frame) whose visibility those tools ask the device problem about
+  bool SetScanPoints(const std::vector<float>& scan_points) {
+    if (api().e3d_reg_set_scan_points(reg, scan_points.data(), scan_points.size() / 3) < 0) return fail(api().e3d_last_error());
     return true;
   }
 

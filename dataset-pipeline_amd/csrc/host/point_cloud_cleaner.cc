@@ -91,12 +91,4 @@ static int run_tool(int argc, char** argv) {
   return EXIT_SUCCESS;
 }
 
-// library errors (no device, out of memory, ...) arrive as exceptions of the host classes: report, EXIT_FAILURE
-int main(int argc, char** argv) {
-  try {
-    return run_tool(argc, argv);
-  } catch (const std::exception& e) {
-    std::cerr << "PointCloudCleaner: " << e.what() << std::endl;
-    return EXIT_FAILURE;
-  }
-}
+int main(int argc, char** argv) { return run_main("PointCloudCleaner", run_tool, argc, argv); }

@@ -588,12 +588,4 @@ int run_tool(int argc, char** argv) {
 
 }  // namespace
 
-// library errors (no device, out of memory, ...) arrive as exceptions of the host classes: report, EXIT_FAILURE
-int main(int argc, char** argv) {
-  try {
-    return run_tool(argc, argv);
-  } catch (const std::exception& e) {
-    std::cerr << "PointCloudEditor: " << e.what() << std::endl;
-    return EXIT_FAILURE;
-  }
-}
+int main(int argc, char** argv) { return run_main("PointCloudEditor", run_tool, argc, argv); }

@@ -1,10 +1,12 @@
 // util.h -- command-line and string helpers with the semantics the reference's tools rely on:
 // pcl::console::parse_argument ("--flag value" pairs in any order, first occurrence wins, unknown flags ignored)
-// and util::SplitStringIntoSet (src/base/util.cc:85-105).
+// and util::SplitStringIntoSet (src/base/util.cc:85-105); the --camera_ids_to_ignore parse and the main() wrapper of the tools.
 #pragma once
 
 #include <cstdlib>
 #include <cstring>
+#include <exception>
+#include <iostream>
 #include <string>
 #include <unordered_set>
 
@@ -48,6 +50,25 @@ inline std::unordered_set<std::string> SplitStringIntoSet(char character, const 
     if (new_index == std::string::npos || index >= input.size()) break;
   }
   return result;
+}
+
+// --camera_ids_to_ignore 3,7 of the tools that read a COLMAP state
+inline std::unordered_set<int> parse_camera_ids_to_ignore(int argc, char** argv) {
+  std::string list;
+  parse_argument(argc, argv, "--camera_ids_to_ignore", list);
+  std::unordered_set<int> ids;
+  for (const std::string& id : SplitStringIntoSet(',', list)) ids.insert(atoi(id.c_str()));
+  return ids;
+}
+
+// main() of a tool: library errors (no device, out of memory, ...) arrive as exceptions of the host classes: report, EXIT_FAILURE
+inline int run_main(const char* tool_name, int (*run_tool)(int, char**), int argc, char** argv) {
+  try {
+    return run_tool(argc, argv);
+  } catch (const std::exception& e) {
+    std::cerr << tool_name << ": " << e.what() << std::endl;
+    return EXIT_FAILURE;
+  }
 }
 
 }  // namespace e3d_host
