@@ -95,6 +95,8 @@ SIGNATURES = {
     "e3d_reg_get_variable_descriptors": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "e3d_reg_set_camera_mask": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
     "e3d_reg_set_depth_maps": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p]),
+    "e3d_reg_set_depth_map_level0": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "e3d_reg_get_depth_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "e3d_reg_set_rig_depth_residuals": (C.c_int, [C.c_void_p, C.c_int]),
     "e3d_reg_depth_accumulate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_depth_cost": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
@@ -674,6 +676,7 @@ class PointCloudEdit:
 
 # ---- (B) image registration kernels ------------------------------------------------------------------------------------
 CAMERA_PINHOLE, CAMERA_OPENCV, CAMERA_THIN_PRISM_FISHEYE, CAMERA_OPENCV_FISHEYE, CAMERA_FOV = 0, 1, 2, 3, 4
+DEPTH_HOLES_AVERAGE, DEPTH_HOLES_STRICT = 0, 1      # e3d_reg_set_depth_map_level0
 
 
 def determine_point_neighbors(xyz, neighbor_count, candidate_count, scan_indices=None, scan_count=1):
@@ -812,6 +815,32 @@ class RegProblem:
         keep = [np.ascontiguousarray(l, np.float32) for l in levels]
         arr = (C.c_void_p * len(keep))(*[l.ctypes.data for l in keep])
         self._chk(lib().e3d_reg_set_depth_maps(self._h, image_id, arr), "e3d_reg_set_depth_maps")
+
+    def set_depth_map_level0(self, image_id, depth, hole_mode=DEPTH_HOLES_STRICT):
+        """One full-resolution (height, width) f32 depth map; the library sanitises it (invalid pixels -> 0) and builds every further
+        level of the camera pyramid on the device.  hole_mode: DEPTH_HOLES_AVERAGE (plain 2x2 box mean) or DEPTH_HOLES_STRICT (a 2x2
+        block with an invalid pixel gives an invalid pixel)."""
+        intr = self._image_intr.get(image_id)
+        d = np.ascontiguousarray(depth, np.float32)
+        if intr is not None:
+            w, h, _, _ = self.intrinsics_level(intr, 0)
+            if d.shape != (h, w):
+                raise E3DError("set_depth_map_level0: depth map %s for a %d x %d camera" % (tuple(d.shape), w, h))
+        self._chk(lib().e3d_reg_set_depth_map_level0(self._h, image_id, C.c_void_p(d.ctypes.data), int(hole_mode)), "e3d_reg_set_depth_map_level0")
+
+    def get_depth_map(self, image_id, level):
+        """One level of an image's depth maps as the device holds it, (h, w) f32; an error without depth maps or beyond the pyramid."""
+        intr = self._image_intr.get(image_id)
+        w = h = 1                        # an unknown image or level: the library reports it before it writes
+        if intr is not None and 0 <= level < self._levels[intr]:
+            w, h, _, _ = self.intrinsics_level(intr, level)
+        m = np.zeros((h, w), np.float32)
+        self._chk(lib().e3d_reg_get_depth_map(self._h, image_id, level, C.c_void_p(m.ctypes.data)), "e3d_reg_get_depth_map")
+        return m
+
+    def get_depth_maps(self, image_id):
+        """All levels: a list of (h, w) f32 arrays, one per pyramid level of the image's camera."""
+        return [self.get_depth_map(image_id, l) for l in range(self._levels.get(self._image_intr.get(image_id), 1))]
 
     def set_rig_depth_residuals(self, enable=True):
         """Depth residuals of the non-reference images of a rig (an error by default, as the reference aborts on them); kept by set_params."""

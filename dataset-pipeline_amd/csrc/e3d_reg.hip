@@ -2593,6 +2593,67 @@ __global__ __launch_bounds__(kBlock) void k_depth_merge(float* __restrict__ a, c
   const float x = a[i], y = b[i];
   a[i] = (x == 0.f) ? y : ((y == 0.f) ? x : fminf(x, y));
 }
+// ---- depth-map pyramid (e3d_reg_set_depth_map_level0) ------------------------------------------------------------------------------
+// a depth is valid iff it is finite and > 0; everything else (NaN, +-inf, negative, -0) becomes +0, the "no depth" of the depth kernels
+__device__ __forceinline__ float depth_sanitise(float v) { return (v > 0.f && v < INFINITY) ? v : 0.f; }
+// one pixel of level l + 1 from a 2 x 2 block of level l: the box mean, summed in f64 in reading order and rounded to f32 once
+template <bool STRICT>
+__device__ __forceinline__ float depth_box(float a, float b, float c, float d) {
+  if (STRICT && (a == 0.f || b == 0.f || c == 0.f || d == 0.f)) return 0.f;
+  return (float)(0.25 * ((((double)a + (double)b) + (double)c) + (double)d));
+}
+// Level l + 1 (wd x hd) from level l (ws x hs), source coordinates clamped to the last row and column (edge replication).  A thread
+// takes a 4 x 2 block of the source and writes two pixels; blockIdx.y is the destination row.  VEC (ws % 4 == 0, so wd = ws / 2 is
+// even): one 16-byte load per source row and one 8-byte store; otherwise pixel by pixel with the clamp.  FIRST: the source is the
+// uploaded level 0, which is sanitised here and written back in place (every pixel is read and written by the same thread only, so
+// the pointer is not __restrict__); dst == nullptr then means a one-level pyramid.  Plain streams: each byte is touched once.
+template <bool VEC, bool FIRST, bool STRICT>
+__global__ __launch_bounds__(kBlock) void k_depth_down(float* src, int ws, int hs, float* dst, int wd, int hd) {
+  const int qx = blockIdx.x * kBlock + threadIdx.x, qy = blockIdx.y;      // source columns 4 qx .. 4 qx + 3, rows 2 qy and 2 qy + 1
+  if (4 * qx >= ws) return;
+  const int y0 = 2 * qy, y1 = min(2 * qy + 1, hs - 1);
+  float r0[4], r1[4];
+  if constexpr (VEC) {
+    const float4 u = ld_stream(reinterpret_cast<const float4*>(src + (size_t)y0 * ws) + qx);
+    const float4 v = (y1 != y0) ? ld_stream(reinterpret_cast<const float4*>(src + (size_t)y1 * ws) + qx) : u;
+    r0[0] = u.x; r0[1] = u.y; r0[2] = u.z; r0[3] = u.w;
+    r1[0] = v.x; r1[1] = v.y; r1[2] = v.z; r1[3] = v.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int x = min(4 * qx + k, ws - 1);
+      r0[k] = ld_stream(src + (size_t)y0 * ws + x);
+      r1[k] = ld_stream(src + (size_t)y1 * ws + x);
+    }
+  }
+  if constexpr (FIRST) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { r0[k] = depth_sanitise(r0[k]); r1[k] = depth_sanitise(r1[k]); }
+    if constexpr (VEC) {
+      st_stream(reinterpret_cast<float4*>(src + (size_t)y0 * ws) + qx, make_float4(r0[0], r0[1], r0[2], r0[3]));
+      if (y1 != y0) st_stream(reinterpret_cast<float4*>(src + (size_t)y1 * ws) + qx, make_float4(r1[0], r1[1], r1[2], r1[3]));
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        if (4 * qx + k >= ws) break;
+        st_stream(src + (size_t)y0 * ws + 4 * qx + k, r0[k]);
+        if (y1 != y0) st_stream(src + (size_t)y1 * ws + 4 * qx + k, r1[k]);
+      }
+    }
+  }
+  if (!dst || qy >= hd) return;
+  const float o0 = depth_box<STRICT>(r0[0], r0[1], r1[0], r1[1]), o1 = depth_box<STRICT>(r0[2], r0[3], r1[2], r1[3]);
+  float* out = dst + (size_t)qy * wd + 2 * qx;
+  if constexpr (VEC) {
+    typedef float v2f __attribute__((ext_vector_type(2)));
+    const v2f w = {o0, o1};
+    if constexpr (E3D_NT >= 2) __builtin_nontemporal_store(w, reinterpret_cast<v2f*>(out)); else *reinterpret_cast<v2f*>(out) = w;
+  } else {
+    if (2 * qx < wd) st_stream(out, o0);
+    if (2 * qx + 1 < wd) st_stream(out + 1, o1);
+  }
+}
+
 __global__ __launch_bounds__(kBlock) void k_fill_i32(int* p, size_t n, int v) {
   const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) p[i] = v;
@@ -2865,6 +2926,15 @@ struct Phase {
   }
 };
 static unsigned nblk(size_t n) { return (unsigned)div_up(n ? n : 1, kBlock); }
+// one level of the depth pyramid (k_depth_down); 16-byte path where the row pitch allows
+template <bool FIRST, bool STRICT>
+static void depth_down_launch(e3d_reg* h, float* src, const CamLevel& s, float* dst, int wd, int hd) {
+  const dim3 grid((unsigned)div_up(div_up((size_t)s.width, 4), kBlock), (unsigned)div_up((size_t)s.height, 2));
+  const bool vec = s.width % 4 == 0 && (!dst || wd == s.width / 2);
+  if (vec) hipLaunchKernelGGL((k_depth_down<true, FIRST, STRICT>), grid, dim3(kBlock), 0, h->stream, src, s.width, s.height, dst, wd, hd);
+  else hipLaunchKernelGGL((k_depth_down<false, FIRST, STRICT>), grid, dim3(kBlock), 0, h->stream, src, s.width, s.height, dst, wd, hd);
+}
+
 // workgroups of a kernel that leaves one partial result per group: four observations per thread, at most `cap` groups
 static int partial_blocks(size_t n, size_t cap) { return (int)std::min<size_t>(std::max<size_t>(div_up(n, kBlock * 4), 1), cap); }
 static RegWeights reg_weights(const e3d_reg* h) {
@@ -3536,6 +3606,10 @@ static void depth_accumulate(e3d_reg* h, int image_id, int point_scale, double* 
   const int V = local_unknowns(h, im), slot = reg_slot(V);
   O.drows.reserve((size_t)rows4(V) * std::max<size_t>(O.n, 1));
   const float4 quat = make_float4(im.pose_q.q.w, im.pose_q.q.x, im.pose_q.q.y, im.pose_q.q.z);
+  const int nb = partial_blocks(O.n, 1024);
+  h->partial.reserve((size_t)nb * slot); h->red.reserve(slot);
+  {
+  KT kt(h, "depth_residuals.accumulate", (double)O.n);
   if (O.n) {
     const RigLink L = rig_link(h, im);
     if (im.dependent()) {
@@ -3546,8 +3620,6 @@ static void depth_accumulate(e3d_reg* h, int image_id, int point_scale, double* 
                                                make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p, O.s.p, O.n, L, O.drows.p));
     }
   }
-  const int nb = partial_blocks(O.n, 1024);
-  h->partial.reserve((size_t)nb * slot); h->red.reserve(slot);
   const int rt = h->prm.depth_robust_weighting_type;
   const float rp = h->prm.depth_robust_weighting_parameter, dw = h->prm.depth_residuals_weight;
 #define E3D_DEPTH(V_, R0_, R1_, B_) \
@@ -3561,6 +3633,7 @@ static void depth_accumulate(e3d_reg* h, int image_id, int point_scale, double* 
   }
 #undef E3D_DEPTH
   hipLaunchKernelGGL(k_reg_reduce, dim3(slot), dim3(kWave), 0, s, h->partial.p, nb, slot, h->red.p);
+  }
   std::vector<double> r(slot);
   read_back(h, r.data(), h->red.p, sizeof(double) * slot);
   double sums[2]; int64_t counts[2];      // {depth, unused}
@@ -3578,9 +3651,12 @@ static void depth_cost(e3d_reg* h, int image_id, int point_scale, double* sum, i
   const int nb = partial_blocks(O.n, 1024);
   h->partial.reserve((size_t)nb * 2); h->red.reserve(2);
   const float4 quat = make_float4(im.pose_q.q.w, im.pose_q.q.x, im.pose_q.q.y, im.pose_q.q.z);
-  hipLaunchKernelGGL(k_reg_depth_cost, dim3(nb), dim3(kBlock), 0, s, S.pts.p, im.pose, quat, make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p,
-                     O.s.p, O.n, h->prm.depth_robust_weighting_type, h->prm.depth_robust_weighting_parameter, h->partial.p);
-  hipLaunchKernelGGL(k_reg_reduce, dim3(2), dim3(kWave), 0, s, h->partial.p, nb, 2, h->red.p);
+  {
+    KT kt(h, "depth_residuals.cost", (double)O.n);
+    hipLaunchKernelGGL(k_reg_depth_cost, dim3(nb), dim3(kBlock), 0, s, S.pts.p, im.pose, quat, make_pyramid(h, im), D, O.idx.p, O.x.p, O.y.p,
+                       O.s.p, O.n, h->prm.depth_robust_weighting_type, h->prm.depth_robust_weighting_parameter, h->partial.p);
+    hipLaunchKernelGGL(k_reg_reduce, dim3(2), dim3(kWave), 0, s, h->partial.p, nb, 2, h->red.p);
+  }
   double r[2];
   read_back(h, r, h->red.p, sizeof r);
   *sum = r[0]; *count = (int64_t)r[1];
@@ -4534,6 +4610,52 @@ int e3d_reg_set_depth_maps(e3d_reg_t* h, int image_id, const float* const* level
     copy_in(im.depth_maps[l].p, level_depths[l], sizeof(float) * px, h->stream);
   }
   rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+/* The same buffers from one full-resolution map (width x height of the image's camera, host or device memory): level 0 is sanitised
+ * and every further level of the camera pyramid is built on the device (k_depth_down). */
+int e3d_reg_set_depth_map_level0(e3d_reg_t* h, int image_id, const float* depth, int hole_mode) {
+  E3D_TRY_ON(h)
+  if (!h || !depth) throw Error(E3D_ERR_INVALID, "null argument");
+  if (hole_mode != E3D_DEPTH_HOLES_AVERAGE && hole_mode != E3D_DEPTH_HOLES_STRICT)
+    throw Error(E3D_ERR_INVALID, fmt("e3d_reg_set_depth_map_level0: unknown hole mode %d", hole_mode));
+  ImageDev& im = get_image(h, image_id);
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  const size_t n_levels = in.levels.size();
+  if (n_levels == 0 || div_up((size_t)in.levels[0].height, 2) > 65535)      // (grid.y is the destination row)
+    throw Error(E3D_ERR_INVALID, "e3d_reg_set_depth_map_level0: camera without pyramid or taller than 131070 rows");
+  im.depth_maps.clear();
+  im.depth_maps.resize(n_levels);
+  for (size_t l = 0; l < n_levels; ++l) im.depth_maps[l].reserve((size_t)in.levels[l].width * (size_t)in.levels[l].height);
+  copy_in(im.depth_maps[0].p, depth, sizeof(float) * (size_t)in.levels[0].width * (size_t)in.levels[0].height, h->stream);
+  const bool strict = hole_mode == E3D_DEPTH_HOLES_STRICT;
+  KT kt(h, "depth_pyramid.build", (double)in.levels[0].width * (double)in.levels[0].height);      // (the kernels, not the upload)
+  for (size_t l = 0; l == 0 || l + 1 < n_levels; ++l) {
+    const CamLevel& s = in.levels[l];
+    float* dst = l + 1 < n_levels ? im.depth_maps[l + 1].p : nullptr;
+    const int wd = dst ? in.levels[l + 1].width : 0, hd = dst ? in.levels[l + 1].height : 0;
+    // a level that does not halve (rounding up) its parent would leave pixels unwritten
+    if (dst && (wd != (s.width + 1) / 2 || hd != (s.height + 1) / 2)) throw Error(E3D_ERR_INVALID, "e3d_reg_set_depth_map_level0: unexpected pyramid geometry");
+    if (l == 0) { if (strict) depth_down_launch<true, true>(h, im.depth_maps[0].p, s, dst, wd, hd); else depth_down_launch<true, false>(h, im.depth_maps[0].p, s, dst, wd, hd); }
+    else { if (strict) depth_down_launch<false, true>(h, im.depth_maps[l].p, s, dst, wd, hd); else depth_down_launch<false, false>(h, im.depth_maps[l].p, s, dst, wd, hd); }
+  }
+  rsync(h);
+  return 0;
+  E3D_CATCH()
+}
+
+/* One level of an image's depth maps back to the host (width_l x height_l floats). */
+int e3d_reg_get_depth_map(e3d_reg_t* h, int image_id, int level, float* out) {
+  E3D_TRY_ON(h)
+  if (!h || !out) throw Error(E3D_ERR_INVALID, "null argument");
+  ImageDev& im = get_image(h, image_id);
+  const Intrin& in = h->intr.at(im.intrinsics_id);
+  if (im.depth_maps.empty() || im.depth_maps.size() != in.levels.size())
+    throw Error(E3D_ERR_INVALID, fmt("e3d_reg_get_depth_map: image %d has no depth maps", image_id));
+  if (level < 0 || level >= (int)in.levels.size()) throw Error(E3D_ERR_INDEX, "e3d_reg_get_depth_map: level beyond the pyramid");
+  read_back(h, out, im.depth_maps[level].p, sizeof(float) * (size_t)in.levels[level].width * (size_t)in.levels[level].height);
   return 0;
   E3D_CATCH()
 }

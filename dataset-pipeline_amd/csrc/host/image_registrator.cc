@@ -6,6 +6,9 @@
 // Occlusion meshes (--occlusion_mesh_path / --occlusion_splats_path) are rasterised on the GPU by the library instead of OpenGL.
 // Observations are cached like in the reference: from the second image scale on (or from the first with
 // --cache_observations 1) the visible point lists are fixed and kept in --observations_cache_path.
+// --depth_residuals_weight W > 0 needs --depth_maps_path DIR: one raw or gzip-compressed f32 map per image in the layout
+// GroundTruthCreator writes as ground_truth_depth/ (io_depth.h); --depth_hole_mode average|strict (default strict) says how the depth
+// pyramid, built on the GPU, treats invalid pixels; --rig_depth_residuals 1 allows depth residuals for the dependent images of a rig.
 // --write_debug_point_clouds 1 writes the scans coloured by the images (initial_point_cloud.ply, scale_<factor>_final_point_cloud.ply).
 #include <cmath>
 #include <cstdlib>
@@ -41,6 +44,13 @@ static int run_tool(int argc, char** argv) {
   parse_argument(argc, argv, "--cache_observations", cache_observations);
   bool write_debug_point_clouds = false;
   parse_argument(argc, argv, "--write_debug_point_clouds", write_debug_point_clouds);
+  // not flags of the reference (it has no way to load depth maps): the folder GroundTruthCreator writes as ground_truth_depth/ (raw or
+  // gzip-compressed f32 maps, io_depth.h), how the depth pyramid treats invalid pixels, and depth residuals for dependent rig images
+  std::string depth_maps_path, depth_hole_mode_string = "strict";
+  parse_argument(argc, argv, "--depth_maps_path", depth_maps_path);
+  parse_argument(argc, argv, "--depth_hole_mode", depth_hole_mode_string);
+  bool rig_depth_residuals = false;
+  parse_argument(argc, argv, "--rig_depth_residuals", rig_depth_residuals);
   int gpus = 1;     // not a flag of the reference: GPUs of this node to shard the images over (image id mod N)
   parse_argument(argc, argv, "--gpus", gpus);
   if (gpus > 1 && !set_gpu_count(gpus)) return EXIT_FAILURE;
@@ -56,10 +66,24 @@ static int run_tool(int argc, char** argv) {
   }
   problem.occlusion_mesh_path = occlusion_mesh_path;
   problem.occlusion_splats_path = occlusion_splats_path;
-  if (problem.prm.depth_residuals_weight > 0) {
+  if (depth_hole_mode_string != "average" && depth_hole_mode_string != "strict") {
+    std::cerr << "--depth_hole_mode " << depth_hole_mode_string << ": expected average or strict." << std::endl;
+    return EXIT_FAILURE;
+  }
+  const int depth_hole_mode = depth_hole_mode_string == "average" ? E3D_DEPTH_HOLES_AVERAGE : E3D_DEPTH_HOLES_STRICT;
+  if (!depth_maps_path.empty()) {
+    struct stat st;
+    if (stat(depth_maps_path.c_str(), &st) != 0 || !S_ISDIR(st.st_mode)) {
+      std::cerr << "--depth_maps_path " << depth_maps_path << " is not a directory." << std::endl;
+      return EXIT_FAILURE;
+    }
+  }
+  if (problem.prm.depth_residuals_weight > 0 && depth_maps_path.empty()) {
     std::cerr << "--depth_residuals_weight > 0: the tool has no way to load depth maps (nor has the reference's: only Problem::SetFixedDepthMaps / e3d_reg_set_depth_maps feed them)." << std::endl;
     return EXIT_FAILURE;
   }
+  const bool use_depth_maps = !depth_maps_path.empty() && problem.prm.depth_residuals_weight > 0;
+  if (!depth_maps_path.empty() && !use_depth_maps) std::cout << "--depth_residuals_weight is 0: the depth maps in " << depth_maps_path << " are ignored." << std::endl;
   if (occlusion_mesh_path.empty() && occlusion_splats_path.empty()) std::cout << "No occlusion meshes given, using 2D splats." << std::endl;
   create_directories(output_folder_path);
 
@@ -103,6 +127,8 @@ static int run_tool(int argc, char** argv) {
   std::vector<ColmapRig> rig_vector;
   if (ReadColmapRigs(state_path + "/rigs.json", &rig_vector) && !problem.AssignRigs(rig_vector)) return EXIT_FAILURE;
   if (!problem.SetScanGeometryAndInitialize(colored_scans, occlusion_points, multi_res_point_cloud_directory_path)) return EXIT_FAILURE;
+  if (rig_depth_residuals && !problem.all_regs([&](e3d_reg_t* r) { return api().e3d_reg_set_rig_depth_residuals(r, 1); }, "e3d_reg_set_rig_depth_residuals")) return EXIT_FAILURE;
+  if (use_depth_maps && !problem.LoadDepthMaps(depth_maps_path, depth_hole_mode)) return EXIT_FAILURE;
 
   // Debug: the scans coloured by the images at the initial state, unless the file exists (image_registrator.cc:200-215)
   if (write_debug_point_clouds) {
@@ -166,6 +192,10 @@ static int run_tool(int argc, char** argv) {
     metadata_stream << "initial_scaling_factor " << initial_scaling_factor << std::endl;
     metadata_stream << "target_scaling_factor " << target_scaling_factor << std::endl;
     metadata_stream << "camera_ids_to_ignore " << camera_ids_to_ignore_string << std::endl;
+    if (!depth_maps_path.empty()) {
+      metadata_stream << "depth_maps_path " << depth_maps_path << std::endl;
+      metadata_stream << "depth_hole_mode " << depth_hole_mode_string << std::endl;
+    }
     problem.prm.OutputValues(metadata_stream);
     metadata_stream << std::endl;
     metadata_stream << "optimum_cost " << optimum_cost << std::endl;

@@ -33,6 +33,7 @@
 
 #include "e3d_loader.h"
 #include "io_colmap.h"
+#include "io_depth.h"
 #include "io_image.h"
 #include "io_ply.h"
 #include "io_scans.h"
@@ -754,6 +755,9 @@ class Problem {
     rp.splat_radius = prm.splat_radius;
     rp.current_image_scale = 0;
     rp.image_scale_count = image_scale_count;
+    rp.depth_residuals_weight = prm.depth_residuals_weight;
+    rp.depth_robust_weighting_type = prm.depth_robust_weighting_type;
+    rp.depth_robust_weighting_parameter = prm.depth_robust_weighting_parameter;
     const int n_gpus = gpu_count_setting();
     if (n_gpus > 1) {
       comms.assign((size_t)n_gpus, nullptr);
@@ -880,6 +884,43 @@ class Problem {
     for (const HostRigImages& f : rig_images)
       if (!all_regs([&](e3d_reg_t* r) { return api().e3d_reg_add_rig_images(r, f.rig_id, f.image_ids.data(), (int)f.image_ids.size()); }, "e3d_reg_add_rig_images")) return false;
 
+    return true;
+  }
+
+  // Problem::SetFixedDepthMaps from files: one map per image under `dir` in GroundTruthCreator's layout (io_depth.h), after
+  // InitializeImages.  Like pixels, a map goes to the image's owner only, which builds the pyramid on the device
+  // (e3d_reg_set_depth_map_level0; hole_mode E3D_DEPTH_HOLES_*).  Read and inflated on up to 16 host threads, a batch of 16 maps at a
+  // time; messages and uploads happen in image order.
+  bool LoadDepthMaps(const std::string& dir, int hole_mode) {
+    std::cout << "LoadDepthMaps(): Reading depth maps ..." << std::endl;
+    struct Decoded { std::vector<float> map; std::string err; bool ok = false; };
+    std::vector<const HostImage*> order;
+    for (const auto& kv : images) order.push_back(&kv.second);
+    const size_t kBatch = 16;      // (a 24 MP map is 97 MB of f32)
+    const unsigned n_threads = std::max(1u, std::min(16u, std::thread::hardware_concurrency()));
+    for (size_t b0 = 0; b0 < order.size(); b0 += kBatch) {
+      const size_t nb = std::min(kBatch, order.size() - b0);
+      std::vector<Decoded> decoded(nb);
+      std::atomic<size_t> next{0};
+      auto work = [&]() {
+        for (;;) {
+          const size_t j = next++;
+          if (j >= nb) break;
+          const HostImage& wim = *order[b0 + j];
+          const HostIntrinsics& win = intrinsics_list[wim.intrinsics_id];
+          decoded[j].ok = read_depth_map(dir, wim.file_path, win.width, win.height, &decoded[j].map, &decoded[j].err);
+        }
+      };
+      std::vector<std::thread> pool;
+      for (unsigned t = 1; t < n_threads && t < nb; ++t) pool.emplace_back(work);
+      work();
+      for (std::thread& t : pool) t.join();
+      for (size_t j = 0; j < nb; ++j) {
+        if (!decoded[j].ok) return fail(decoded[j].err);
+        const int id = order[b0 + j]->image_id;
+        if (api().e3d_reg_set_depth_map_level0(owner(id), id, decoded[j].map.data(), hole_mode) < 0) return lib_fail("e3d_reg_set_depth_map_level0");
+      }
+    }
     return true;
   }
 

@@ -391,11 +391,28 @@ int e3d_reg_set_camera_mask(e3d_reg_t* reg, int intrinsics_id, const uint8_t* co
  *     R_image_rig [I | -[G]x], T = image_T_global * point, G = rig_T_global * point), and every call below accepts such images.
  *   e3d_reg_set_depth_maps: Problem::SetFixedDepthMaps for one image, one f32 map per pyramid level of its camera (caller-built
  *     pyramid, like the test's cv::resize INTER_AREA chain); NULL removes them.  Required for every image once the weight is > 0.
+ *   e3d_reg_set_depth_map_level0: the same buffers from one full-resolution map (width x height floats of the image's camera,
+ *     row-major, host or device memory); the pyramid is built on the device, one level per level of the camera pyramid (level sizes
+ *     as e3d_reg_get_intrinsics_level reports them: int(0.5 w + 0.5)).  Afterwards every depth call behaves as if that pyramid had
+ *     been passed to e3d_reg_set_depth_maps.  Arithmetic (bit-exact, so that a restatement can be compared with ==):
+ *       level 0: a pixel is valid iff it is finite and > 0; every other pixel (NaN, +-inf, negative, -0) becomes +0.0f, the
+ *         "no depth" of the depth kernels (ground-truth maps hold +inf where nothing was drawn);
+ *       level l + 1 from level l: with a, b, c, d the pixels (2y, 2x), (2y, 2x+1), (2y+1, 2x), (2y+1, 2x+1) of level l, coordinates
+ *         clamped to the last row and column, pixel (y, x) = (float)(0.25 * ((((double)a + b) + c) + d));
+ *       E3D_DEPTH_HOLES_STRICT: if any of the four (clamped) source pixels is 0 the result is +0.0f;
+ *       E3D_DEPTH_HOLES_AVERAGE: the plain box mean (holes count as depth 0 and pull the mean down).
+ *     Errors: null handle or pointer, unknown image, unknown hole_mode.
+ *   e3d_reg_get_depth_map: one level of an image's depth maps (width_l x height_l floats) back to the host, whichever call set
+ *     them; an error if the image has none or the level is out of range.
  *   e3d_reg_depth_accumulate / e3d_reg_depth_cost: the depth part of AccumulateHAndBForImage / ComputeResidualsForImage for one
  *     (image, point scale); e3d_reg_apply, e3d_reg_compute_cost and e3d_reg_run_on_current_scale include them by themselves.
  *     H is the V x V upper triangle (row-major) and b has V entries, V = the image's local unknowns as in e3d_reg_accumulate:
  *     I + 6 [intrinsics, pose], or I + 12 [intrinsics, rig extrinsics, rig pose] for a non-reference rig image. */
 int e3d_reg_set_depth_maps(e3d_reg_t* reg, int image_id, const float* const* level_depths);
+#define E3D_DEPTH_HOLES_AVERAGE 0   /* plain 2x2 box mean: the cv::resize INTER_AREA chain of test_alignment.cc:485-489 */
+#define E3D_DEPTH_HOLES_STRICT  1   /* a 2x2 block with an invalid pixel gives an invalid pixel */
+int e3d_reg_set_depth_map_level0(e3d_reg_t* reg, int image_id, const float* depth, int hole_mode);
+int e3d_reg_get_depth_map(e3d_reg_t* reg, int image_id, int level, float* out);
 int e3d_reg_set_rig_depth_residuals(e3d_reg_t* reg, int enable);
 int e3d_reg_depth_accumulate(e3d_reg_t* reg, int image_id, int point_scale, double* H, double* b, double* sum, int64_t* count);
 int e3d_reg_depth_cost(e3d_reg_t* reg, int image_id, int point_scale, double* sum, int64_t* count);
