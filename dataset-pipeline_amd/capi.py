@@ -175,6 +175,13 @@ SIGNATURES = {
     "e3d_edit_delete_selected": (C.c_int64, [C.c_void_p]),
     "e3d_edit_extract_selected": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "e3d_edit_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # SurfaceReconstructor: an occlusion mesh from an oriented point cloud
+    "e3d_surface_reconstruct": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float]),
+    "e3d_surface_destroy": (None, [C.c_void_p]),
+    "e3d_surface_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_surface_get_corners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_surface_get_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_surface_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
 }
 
 
@@ -542,6 +549,44 @@ def create_splats(xyz, normals, vertices, triangles, distance_threshold=0.02, ma
     s = np.arange(m, dtype=np.int32)[:, None] * 4
     faces = np.concatenate([np.concatenate([s + 2, s + 1, s], 1), np.concatenate([s, s + 3, s + 2], 1)], 1).reshape(-1, 3)
     return out[:m].reshape(-1, 3).copy(), faces, flag.astype(bool), rad
+
+
+def reconstruct_surface(xyz, normals, voxel_size, support_radius=None, return_corners=False, timings=None):
+    """SurfaceReconstructor (include/e3d_hip.h, e3d_surface_reconstruct) -> (vertices[v, 3] f32, triangles[t, 3] uint32), and with
+    return_corners a dict of the defined corners in ascending (k, j, i): ijk[c, 3] int32, f[c], weight[c] f64, count[c] int32, plus
+    the vertices' cells cell_ijk[v, 3] int32.  support_radius defaults to 2 x voxel_size (in f32).  timings: a dict that receives the
+    HIP-event time of every kernel group as <group>_ms."""
+    keep = []
+    n = int(xyz.shape[0])
+    h = np.float32(voxel_size)
+    r = np.float32(2) * h if support_radius is None else np.float32(support_radius)
+    handle = lib().e3d_surface_reconstruct(_ptr(xyz, np.float32, keep) if n else None, _ptr(normals, np.float32, keep) if n else None, n,
+                                           float(h), float(r))
+    if not handle:
+        _err("e3d_surface_reconstruct")
+    try:
+        nc, nv, nt = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        lib().e3d_surface_counts(handle, C.byref(nc), C.byref(nv), C.byref(nt))
+        vertices = np.zeros((nv.value, 3), np.float32)
+        cells = np.zeros((nv.value, 3), np.int32)
+        triangles = np.zeros((nt.value, 3), np.uint32)
+        if lib().e3d_surface_get_mesh(handle, C.c_void_p(vertices.ctypes.data), C.c_void_p(cells.ctypes.data), C.c_void_p(triangles.ctypes.data)) < 0:
+            _err("e3d_surface_get_mesh")
+        corners = None
+        if return_corners:
+            corners = {"ijk": np.zeros((nc.value, 3), np.int32), "f": np.zeros(nc.value, np.float64), "weight": np.zeros(nc.value, np.float64),
+                       "count": np.zeros(nc.value, np.int32), "cell_ijk": cells}
+            if lib().e3d_surface_get_corners(handle, *(C.c_void_p(corners[k].ctypes.data) for k in ("ijk", "f", "weight", "count"))) < 0:
+                _err("e3d_surface_get_corners")
+        if timings is not None:
+            ms = (C.c_float * 16)()
+            names = (C.c_char_p * 16)()
+            g = lib().e3d_surface_kernel_ms(handle, ms, names, 16)
+            for i in range(min(g, 16)):
+                timings[names[i].decode() + "_ms"] = float(ms[i])
+    finally:
+        lib().e3d_surface_destroy(handle)
+    return (vertices, triangles, corners) if return_corners else (vertices, triangles)
 
 
 CUBE_MAP_FACES = ("front", "left", "back", "right", "down", "up")

@@ -218,6 +218,8 @@ void launch_dense_counts(const unsigned long long* keys, size_t n, const QueryRa
 // n_reserve: the temporary storage is sized for a sort of that many elements (a later sort of the same arrays; 0: for n)
 void sort_pairs_u32_u32(unsigned* keys_in, unsigned* keys_out, unsigned* vals_in, unsigned* vals_out, size_t n,
                         int end_bit, DevBuf<char>& temp, hipStream_t s, size_t n_reserve = 0);
+// radix sort of 64-bit keys alone (rocPRIM, e3d_sort.hip): the voxel, brick and cell lists of the surface reconstruction
+void sort_keys_u64(unsigned long long* keys_in, unsigned long long* keys_out, size_t n, int end_bit, DevBuf<char>& temp, hipStream_t s);
 // in-place exclusive MAX scan of n unsigned values (rocPRIM, e3d_sort.hip); one-off per grid build
 void exclusive_max_scan_u32(unsigned* data, size_t n, DevBuf<char>& temp, hipStream_t s);
 // exclusive prefix sum of n 0/1 flags into 32-bit offsets (rocPRIM, e3d_sort.hip): the splat compaction

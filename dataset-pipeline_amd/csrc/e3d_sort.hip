@@ -44,6 +44,14 @@ void sort_pairs_u32_u32(unsigned* keys_in, unsigned* keys_out, unsigned* vals_in
   sort_pairs_impl(keys_in, keys_out, vals_in, vals_out, n, end_bit, temp, s, n_reserve);
 }
 
+void sort_keys_u64(unsigned long long* keys_in, unsigned long long* keys_out, size_t n, int end_bit, DevBuf<char>& temp, hipStream_t s) {
+  if (n == 0) return;
+  size_t bytes = 0;
+  E3D_HIP(rocprim::radix_sort_keys(nullptr, bytes, keys_in, keys_out, n, 0u, (unsigned)end_bit, s));
+  temp.reserve(bytes);
+  E3D_HIP(rocprim::radix_sort_keys(temp.p, bytes, keys_in, keys_out, n, 0u, (unsigned)end_bit, s));
+}
+
 void exclusive_max_scan_u32(unsigned* data, size_t n, DevBuf<char>& temp, hipStream_t s) {
   if (n == 0) return;
   size_t bytes = 0;

@@ -1,0 +1,639 @@
+// e3d_surface.hip -- SurfaceReconstructor: an occlusion mesh from an oriented point cloud on the MI355X.
+//
+// The reference leaves this step to MeshLab / PoissonRecon.  Here a signed field f = sum w n.(x - p) / sum w with the compact weight
+// w = (1 - d^2 / R^2)^2 is evaluated at the corners of a lattice of edge h that is anchored at the world origin, and one vertex per
+// cell with a sign change plus one quad per crossing lattice edge are written (the rules: include/e3d_hip.h, e3d_surface_reconstruct).
+// Everything the result depends on is f64; f32 only carries the input and the final vertices.
+//
+//  grid        the contributing points sorted into a hashed grid of cell max(R, h) (HashEntry / cell_key / launch_build_table)
+//  candidates  the occupied h-voxels (sort + unique), dilated to BRICKS of 4 x 4 x 4 corners (sort + unique).  A brick is the unit of
+//              the field kernel: any superset of the defined corners is correct, corners where no point counts drop out
+//  field       k_surf_field: one wave per brick, one corner per lane.  The grid cells that can hold a counting point of the brick are
+//              looked up 64 at a time (one per lane); each non-empty cell's run of points is staged through LDS as f64, 64 points per
+//              step, and every lane adds the staged points that count for its corner.  A corner's sums live in one lane and are
+//              formed in grid order: no atomics, and the launch order cannot show
+//  corners     the defined corners compacted and sorted by (k, j, i)
+//  extract     crossing flags per (corner, axis) from a brick lookup, stable compaction to the edge list (= quad order); the four
+//              cells of every edge sorted + unique = the vertices in (k, j, i); vertex positions and triangles
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <vector>
+
+#include "../../include/e3d_hip.h"
+#include "e3d_icp_kernels.hpp"
+
+#pragma clang fp contract(off)
+
+namespace e3d {
+
+constexpr int kSurfBlock = 256;
+constexpr int kSurfOrgMargin = 16;                 // lattice units kept free below the lowest occupied voxel: dilation (<= 9) + a cell
+constexpr int kSurfGridBias = 1 << 20;             // grid-cell coordinates are in [-2^20, 2^20): cell >= h and |p| / h < 2^20
+constexpr int kSurfGroups = 5;
+static const char* const kSurfGroupNames[kSurfGroups] = {"grid", "candidates", "field", "corners", "extract"};
+
+struct SurfParams {
+  double h, R, R2;
+  double cell, pad;                                // point grid: cell edge max(R, h) (1 + 1e-6); slack of a brick's search bounds
+  int org[3];                                      // lattice coordinate of relative coordinate 0 (a multiple of 4)
+  int D;                                           // ceil(R / h)
+  unsigned mask;                                   // point grid's hash table size - 1
+};
+
+// the grid cell of a coordinate: ONE monotone function for the points and for the bounds of a brick's search
+__device__ __forceinline__ int surf_grid_coord(double v, double cell) { return (int)floor(v / cell); }
+
+__device__ __forceinline__ bool surf_contributes(const float* __restrict__ xyz, const float* __restrict__ nrm, size_t i) {
+  const float x = xyz[3 * i], y = xyz[3 * i + 1], z = xyz[3 * i + 2], a = nrm[3 * i], b = nrm[3 * i + 1], c = nrm[3 * i + 2];
+  const bool finite = isfinite(x) && isfinite(y) && isfinite(z) && isfinite(a) && isfinite(b) && isfinite(c);
+  return finite && !(a == 0.f && b == 0.f && c == 0.f);
+}
+
+__device__ __forceinline__ int wave_min_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_max_i(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
+  return v;
+}
+
+// Per point: does it contribute, is it in range, its h-voxel; the voxels' bounding box in box[0..5] (min xyz, max xyz), box[6] =
+// a contributing point out of range, box[7] = number of contributing points.  A fixed grid strides over the points and every block
+// ends in one set of atomics (one per wave took 25 ms for 20 M points: 2 M atomics on eight words).
+constexpr unsigned kSurfClassifyBlocks = 2048;
+__global__ __launch_bounds__(kSurfBlock) void k_surf_classify(const float* __restrict__ xyz, const float* __restrict__ nrm, size_t n, double h,
+                                                              int* __restrict__ box) {
+  int lo[3] = {INT_MAX, INT_MAX, INT_MAX}, hi[3] = {INT_MIN, INT_MIN, INT_MIN};
+  int bad = 0, count = 0;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+    if (!surf_contributes(xyz, nrm, i)) continue;
+    ++count;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      const double q = (double)xyz[3 * i + a] / h;
+      if (!(fabs(q) < 1048576.0)) bad = 1;
+      else { const int v = (int)floor(q); lo[a] = min(lo[a], v); hi[a] = max(hi[a], v); }
+    }
+  }
+  __shared__ int part[kSurfBlock / kWave][8];
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) { lo[a] = wave_min_i(lo[a]); hi[a] = wave_max_i(hi[a]); }
+  bad = wave_max_i(bad);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) count += __shfl_xor(count, o, 64);
+  if (lane == 0) {
+#pragma unroll
+    for (int a = 0; a < 3; ++a) { part[wv][a] = lo[a]; part[wv][3 + a] = hi[a]; }
+    part[wv][6] = bad; part[wv][7] = count;
+  }
+  __syncthreads();
+  if (threadIdx.x < 8) {
+    const int t = threadIdx.x;
+    int v = part[0][t];
+    for (int k = 1; k < kSurfBlock / kWave; ++k) v = t < 3 ? min(v, part[k][t]) : t < 7 ? max(v, part[k][t]) : v + part[k][t];
+    if (t < 3) { if (v != INT_MAX) atomicMin(&box[t], v); }
+    else if (t < 6) { if (v != INT_MIN) atomicMax(&box[t], v); }
+    else if (t == 6) { if (v) atomicOr(&box[6], 1); }
+    else if (v) atomicAdd(&box[7], v);
+  }
+}
+
+// Sort keys of the points: the point grid's cell (vals = point index) and the h-voxel relative to org; kEmptyKey for a point that
+// does not contribute, which the sorts move to the end.
+__global__ __launch_bounds__(kSurfBlock) void k_surf_point_keys(const float* __restrict__ xyz, const float* __restrict__ nrm, size_t n, SurfParams P,
+                                                                unsigned long long* __restrict__ grid_keys, unsigned* __restrict__ vals,
+                                                                unsigned long long* __restrict__ voxel_keys) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  unsigned long long gk = kEmptyKey, vk = kEmptyKey;
+  if (surf_contributes(xyz, nrm, i)) {
+    const double x = (double)xyz[3 * i], y = (double)xyz[3 * i + 1], z = (double)xyz[3 * i + 2];
+    gk = cell_key(surf_grid_coord(x, P.cell) + kSurfGridBias, surf_grid_coord(y, P.cell) + kSurfGridBias, surf_grid_coord(z, P.cell) + kSurfGridBias);
+    vk = cell_key((int)floor(x / P.h) - P.org[0], (int)floor(y / P.h) - P.org[1], (int)floor(z / P.h) - P.org[2]);
+  }
+  grid_keys[i] = gk;
+  vals[i] = (unsigned)i;
+  voxel_keys[i] = vk;
+}
+
+// flags of the first element of every run of equal keys (sorted keys): the unique keys after a stable compaction
+__global__ __launch_bounds__(kSurfBlock) void k_surf_flag_first(const unsigned long long* __restrict__ keys, size_t n, unsigned char* __restrict__ flags) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) flags[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1 : 0;
+}
+__global__ __launch_bounds__(kSurfBlock) void k_surf_scatter_keys(const unsigned long long* __restrict__ keys, const unsigned char* __restrict__ flags,
+                                                                  const unsigned* __restrict__ offsets, size_t n, unsigned long long* __restrict__ out) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n && flags[j]) out[offsets[j]] = keys[j];
+}
+
+// Every brick a voxel's corners can fall into: corners [v - D, v + D + 1] per axis count a point of voxel v at most (one step of
+// margin each side for the rounding of p / h), M bricks per axis at most; slots beyond the range repeat its last brick.
+__global__ __launch_bounds__(kSurfBlock) void k_surf_brick_keys(const unsigned long long* __restrict__ voxels, size_t n_voxels, int D, int M,
+                                                                unsigned long long* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const size_t per = (size_t)M * M * M;
+  if (t >= n_voxels * per) return;
+  const unsigned long long v = voxels[t / per];
+  const int slot = (int)(t % per);
+  const int s[3] = {slot % M, (slot / M) % M, slot / (M * M)};
+  int b[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int c = (int)((v >> (21 * a)) & 0x1FFFFF);
+    const int lo = (c - D) >> 2, hi = (c + D + 1) >> 2;
+    b[a] = min(lo + s[a], hi);
+  }
+  out[t] = cell_key(b[0], b[1], b[2]);
+}
+
+__device__ __forceinline__ void surf_cell_range(const HashEntry* __restrict__ table, unsigned mask, int x, int y, int z, unsigned& s, unsigned& e) {
+  s = 0; e = 0;
+  constexpr int kMaxC = (1 << 21) - 1;
+  if (x < 0 || y < 0 || z < 0 || x > kMaxC || y > kMaxC || z > kMaxC) return;
+  const unsigned long long key = cell_key(x, y, z);
+  unsigned h = hash_key(key) & mask;
+  for (;;) {
+    const HashEntry en = table[h];
+    if (en.key == key) { s = en.start; e = en.end; return; }
+    if (en.key == kEmptyKey) return;
+    h = (h + 1) & mask;
+  }
+}
+
+// The field at the 64 corners of one brick per wave (block = one wave, so the barriers are the wave's own).
+__global__ __launch_bounds__(64) void k_surf_field(const unsigned long long* __restrict__ bricks, const float4* __restrict__ P4, const float4* __restrict__ N4,
+                                                   const HashEntry* __restrict__ table, SurfParams P, double* __restrict__ f_out, double* __restrict__ w_out,
+                                                   int* __restrict__ count_out) {
+  __shared__ double stage[64][6];
+  const int lane = threadIdx.x;
+  const unsigned long long bk = bricks[blockIdx.x];
+  const int b[3] = {(int)(bk & 0x1FFFFF), (int)((bk >> 21) & 0x1FFFFF), (int)((bk >> 42) & 0x1FFFFF)};
+  const double x = P.h * (double)(P.org[0] + 4 * b[0] + (lane & 3));
+  const double y = P.h * (double)(P.org[1] + 4 * b[1] + ((lane >> 2) & 3));
+  const double z = P.h * (double)(P.org[2] + 4 * b[2] + (lane >> 4));
+  // grid cells that can hold a point within R of a corner of the brick
+  int c0[3], nc[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double lo = P.h * (double)(P.org[a] + 4 * b[a]) - P.R - P.pad, hi = P.h * (double)(P.org[a] + 4 * b[a] + 3) + P.R + P.pad;
+    c0[a] = surf_grid_coord(lo, P.cell) + kSurfGridBias;
+    nc[a] = surf_grid_coord(hi, P.cell) + kSurfGridBias - c0[a] + 1;
+  }
+  const int ncell = nc[0] * nc[1] * nc[2];
+  double S = 0.0, W = 0.0;
+  int cnt = 0;
+  for (int base = 0; base < ncell; base += 64) {
+    const int idx = base + lane;
+    unsigned s = 0, e = 0;
+    if (idx < ncell) surf_cell_range(table, P.mask, c0[0] + idx % nc[0], c0[1] + (idx / nc[0]) % nc[1], c0[2] + idx / (nc[0] * nc[1]), s, e);
+    unsigned long long nonempty = __ballot(e > s);
+    while (nonempty) {
+      const int src = __ffsll((long long)nonempty) - 1;
+      nonempty &= nonempty - 1;
+      const unsigned cs = __shfl(s, src, 64), ce = __shfl(e, src, 64);
+      for (unsigned m = cs; m < ce; m += 64) {
+        __syncthreads();
+        if (m + lane < ce) {
+          const float4 p = P4[m + lane], q = N4[m + lane];
+          stage[lane][0] = (double)p.x; stage[lane][1] = (double)p.y; stage[lane][2] = (double)p.z;
+          stage[lane][3] = (double)q.x; stage[lane][4] = (double)q.y; stage[lane][5] = (double)q.z;
+        }
+        __syncthreads();
+        const int chunk = (int)min(64u, ce - m);
+        for (int t = 0; t < chunk; ++t) {
+          const double dx = x - stage[t][0], dy = y - stage[t][1], dz = z - stage[t][2];
+          const double d2 = (dx * dx + dy * dy) + dz * dz;
+          if (d2 < P.R2) {
+            const double om = 1.0 - d2 / P.R2;
+            const double w = om * om;
+            S += w * ((stage[t][3] * dx + stage[t][4] * dy) + stage[t][5] * dz);
+            W += w;
+            ++cnt;
+          }
+        }
+      }
+    }
+  }
+  const size_t o = (size_t)blockIdx.x * 64 + lane;
+  f_out[o] = cnt ? S / W : 0.0;
+  w_out[o] = W;
+  count_out[o] = cnt;
+}
+
+// keys (k, j, i) of the defined corners and their slots, flagged for compaction
+__global__ __launch_bounds__(kSurfBlock) void k_surf_corner_flags(const int* __restrict__ count, size_t n_slots, unsigned char* __restrict__ flags) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n_slots) flags[j] = count[j] > 0 ? 1 : 0;
+}
+__global__ __launch_bounds__(kSurfBlock) void k_surf_corner_keys(const unsigned long long* __restrict__ bricks, const unsigned char* __restrict__ flags,
+                                                                 const unsigned* __restrict__ offsets, size_t n_slots, unsigned long long* __restrict__ keys,
+                                                                 unsigned* __restrict__ slots) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_slots || !flags[j]) return;
+  const unsigned long long bk = bricks[j >> 6];
+  const int l = (int)(j & 63);
+  const unsigned o = offsets[j];
+  keys[o] = cell_key(4 * (int)(bk & 0x1FFFFF) + (l & 3), 4 * (int)((bk >> 21) & 0x1FFFFF) + ((l >> 2) & 3), 4 * (int)((bk >> 42) & 0x1FFFFF) + (l >> 4));
+  slots[o] = (unsigned)j;
+}
+
+// position of a key in a sorted array of unique keys, or -1
+__device__ __forceinline__ long long surf_find(const unsigned long long* __restrict__ keys, size_t n, unsigned long long key) {
+  size_t lo = 0, hi = n;
+  while (lo < hi) {
+    const size_t mid = (lo + hi) >> 1;
+    if (keys[mid] < key) lo = mid + 1; else hi = mid;
+  }
+  return (lo < n && keys[lo] == key) ? (long long)lo : -1;
+}
+// slot of a corner (relative coordinates) in the field arrays, or -1 if no brick holds it
+__device__ __forceinline__ long long surf_corner_slot(const unsigned long long* __restrict__ bricks, size_t n_bricks, int i, int j, int k) {
+  if (i < 0 || j < 0 || k < 0) return -1;
+  const long long b = surf_find(bricks, n_bricks, cell_key(i >> 2, j >> 2, k >> 2));
+  return b < 0 ? -1 : b * 64 + ((k & 3) << 4 | (j & 3) << 2 | (i & 3));
+}
+
+struct SurfField {
+  const unsigned long long* bricks; size_t n_bricks;
+  const double* f; const int* count;
+};
+// does the edge from corner a (defined, field fa) along axis d cross; its parameter t
+__device__ __forceinline__ bool surf_edge(const SurfField& F, int i, int j, int k, int d, double& t, bool& a_negative) {
+  const long long sa = surf_corner_slot(F.bricks, F.n_bricks, i, j, k);
+  if (sa < 0 || F.count[sa] <= 0) return false;
+  const long long sb = surf_corner_slot(F.bricks, F.n_bricks, i + (d == 0), j + (d == 1), k + (d == 2));
+  if (sb < 0 || F.count[sb] <= 0) return false;
+  const double fa = F.f[sa], fb = F.f[sb];
+  a_negative = fa < 0.0;
+  if (a_negative == (fb < 0.0)) return false;
+  t = fa / (fa - fb);
+  return true;
+}
+
+// the sorted corners' public record and the crossing flags of their three edges
+__global__ __launch_bounds__(kSurfBlock) void k_surf_corner_out(const unsigned long long* __restrict__ keys, const unsigned* __restrict__ slots, size_t n_corners,
+                                                                SurfParams P, SurfField F, const double* __restrict__ w, int* __restrict__ ijk,
+                                                                double* __restrict__ f_out, double* __restrict__ w_out, int* __restrict__ count_out,
+                                                                unsigned char* __restrict__ cross) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_corners) return;
+  const unsigned long long key = keys[c];
+  const int i = (int)(key & 0x1FFFFF), j = (int)((key >> 21) & 0x1FFFFF), k = (int)((key >> 42) & 0x1FFFFF);
+  const unsigned s = slots[c];
+  ijk[3 * c] = i + P.org[0]; ijk[3 * c + 1] = j + P.org[1]; ijk[3 * c + 2] = k + P.org[2];
+  f_out[c] = F.f[s]; w_out[c] = w[s]; count_out[c] = F.count[s];
+#pragma unroll
+  for (int d = 0; d < 3; ++d) {
+    double t; bool neg;
+    cross[3 * c + d] = surf_edge(F, i, j, k, d, t, neg) ? 1 : 0;
+  }
+}
+
+// the four cells around edge (a, d): offsets (-1, -1), (0, -1), (0, 0), (-1, 0) in (u, v) = ((d + 1) % 3, (d + 2) % 3)
+__device__ __forceinline__ unsigned long long surf_quad_cell(int i, int j, int k, int d, int q) {
+  int c[3] = {i, j, k};
+  const int u = (d + 1) % 3, v = (d + 2) % 3;
+  c[u] += (q == 0 || q == 3) ? -1 : 0;
+  c[v] += (q == 0 || q == 1) ? -1 : 0;
+  return cell_key(c[0], c[1], c[2]);
+}
+
+// crossing edges in quad order (compacted from the flags): edge e = (corner, axis), and the keys of its four cells
+__global__ __launch_bounds__(kSurfBlock) void k_surf_edges(const unsigned long long* __restrict__ corner_keys, const unsigned char* __restrict__ cross,
+                                                           const unsigned* __restrict__ offsets, size_t n_flags, unsigned* __restrict__ edges,
+                                                           unsigned long long* __restrict__ cell_keys) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_flags || !cross[t]) return;
+  const unsigned e = offsets[t];
+  edges[e] = (unsigned)t;
+  const unsigned long long key = corner_keys[t / 3];
+  const int i = (int)(key & 0x1FFFFF), j = (int)((key >> 21) & 0x1FFFFF), k = (int)((key >> 42) & 0x1FFFFF), d = (int)(t % 3);
+#pragma unroll
+  for (int q = 0; q < 4; ++q) cell_keys[4 * (size_t)e + q] = surf_quad_cell(i, j, k, d, q);
+}
+
+// one vertex per active cell: the mean of the crossing points of its 12 edges (axis, then v, then u), rounded to f32 at the end
+__global__ __launch_bounds__(kSurfBlock) void k_surf_vertices(const unsigned long long* __restrict__ cells, size_t n_cells, SurfParams P, SurfField F,
+                                                              float* __restrict__ vertices, int* __restrict__ cell_ijk) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_cells) return;
+  const unsigned long long key = cells[c];
+  const int o[3] = {(int)(key & 0x1FFFFF), (int)((key >> 21) & 0x1FFFFF), (int)((key >> 42) & 0x1FFFFF)};
+  double sum[3] = {0.0, 0.0, 0.0};
+  int m = 0;
+  for (int d = 0; d < 3; ++d) {
+    const int u = (d + 1) % 3, v = (d + 2) % 3;
+    for (int dv = 0; dv < 2; ++dv)
+      for (int du = 0; du < 2; ++du) {
+        int a[3] = {o[0], o[1], o[2]};
+        a[u] += du; a[v] += dv;
+        double t; bool neg;
+        if (!surf_edge(F, a[0], a[1], a[2], d, t, neg)) continue;
+        double p[3];
+#pragma unroll
+        for (int x = 0; x < 3; ++x) p[x] = P.h * (double)(a[x] + P.org[x]);
+        p[d] = p[d] + t * P.h;
+        sum[0] += p[0]; sum[1] += p[1]; sum[2] += p[2];
+        ++m;
+      }
+  }
+#pragma unroll
+  for (int x = 0; x < 3; ++x) {
+    vertices[3 * c + x] = (float)(sum[x] / (double)m);
+    cell_ijk[3 * c + x] = o[x] + P.org[x];
+  }
+}
+
+// two triangles per crossing edge: (q0, q1, q2), (q0, q2, q3) of the cells' vertices, the four in reverse if a is not negative
+__global__ __launch_bounds__(kSurfBlock) void k_surf_triangles(const unsigned* __restrict__ edges, size_t n_edges, const unsigned long long* __restrict__ corner_keys,
+                                                               const unsigned* __restrict__ slots, const double* __restrict__ f,
+                                                               const unsigned long long* __restrict__ cells, size_t n_cells, unsigned* __restrict__ tri) {
+  const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= n_edges) return;
+  const unsigned t = edges[e];
+  const unsigned long long key = corner_keys[t / 3];
+  const int i = (int)(key & 0x1FFFFF), j = (int)((key >> 21) & 0x1FFFFF), k = (int)((key >> 42) & 0x1FFFFF), d = (int)(t % 3);
+  const bool a_negative = f[slots[t / 3]] < 0.0;
+  unsigned q[4];
+#pragma unroll
+  for (int x = 0; x < 4; ++x) q[a_negative ? x : 3 - x] = (unsigned)surf_find(cells, n_cells, surf_quad_cell(i, j, k, d, x));
+  unsigned* o = tri + 6 * e;
+  o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[0]; o[4] = q[2]; o[5] = q[3];
+}
+
+static int bits_for(unsigned v) { int b = 0; while (b < 32 && (v >> b)) ++b; return b; }
+
+}  // namespace e3d
+
+using namespace e3d;
+
+struct e3d_surface {
+  std::vector<int32_t> corner_ijk, corner_count, cell_ijk;
+  std::vector<double> corner_f, corner_w;
+  std::vector<float> vertices;
+  std::vector<uint32_t> triangles;
+  float ms[kSurfGroups] = {0, 0, 0, 0, 0};
+};
+
+namespace {
+
+struct SurfRun {
+  hipStream_t s = nullptr;
+  DevBuf<char> temp;
+  DevBuf<unsigned char> flags;
+  DevBuf<unsigned> offsets;
+  ~SurfRun() { if (s) (void)hipStreamDestroy(s); }
+
+  // exclusive offsets of n flags; the number set
+  size_t scan(size_t n) {
+    if (n == 0) return 0;
+    offsets.reserve(n);
+    exclusive_sum_u8_u32(flags.p, offsets.p, n, temp, s);
+    unsigned last = 0; unsigned char lf = 0;
+    copy_out(&last, offsets.p + (n - 1), sizeof last, s);
+    copy_out(&lf, flags.p + (n - 1), 1, s);
+    E3D_HIP(hipStreamSynchronize(s));
+    return (size_t)last + (lf ? 1 : 0);
+  }
+  // sorts keys[0, n) (into `sorted`) and leaves their unique values in `out`; the number of unique keys
+  size_t sort_unique(DevBuf<unsigned long long>& keys, DevBuf<unsigned long long>& sorted, DevBuf<unsigned long long>& out, size_t n, int end_bit) {
+    if (n == 0) return 0;
+    sorted.reserve(n);
+    sort_keys_u64(keys.p, sorted.p, n, end_bit, temp, s);
+    flags.reserve(n);
+    const unsigned nb = (unsigned)div_up(n, kSurfBlock);
+    hipLaunchKernelGGL(k_surf_flag_first, dim3(nb), dim3(kSurfBlock), 0, s, sorted.p, n, flags.p);
+    const size_t m = scan(n);
+    out.reserve(m);
+    hipLaunchKernelGGL(k_surf_scatter_keys, dim3(nb), dim3(kSurfBlock), 0, s, sorted.p, flags.p, offsets.p, n, out.p);
+    return m;
+  }
+};
+
+void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius) {
+  const double h = (double)voxel_size, R = (double)support_radius;
+  if (!std::isfinite(h) || !(h > 0.0)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the voxel size must be positive and finite");
+  if (!std::isfinite(R) || !(R > 0.0)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the support radius must be positive and finite");
+  if (R / h > 8.0) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct: support radius / voxel size = %g, at most 8", R / h));
+  if (n && (!xyz || !normals)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: null argument");
+  if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: more than 2^31-1 points");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
+  if (n == 0) return;
+
+  SurfRun run;
+  E3D_HIP(hipStreamCreateWithFlags(&run.s, hipStreamNonBlocking));
+  hipStream_t s = run.s;
+  EventTimer timer[kSurfGroups];
+  const auto blocks = [](size_t m) { return dim3((unsigned)div_up(m, kSurfBlock)); };
+  const size_t kMaxItems = ((size_t)1 << 32) - 64;        // the compactions use 32-bit offsets
+
+  // ---- grid ----------------------------------------------------------------------------------------------------------------------
+  DevBuf<float> d_xyz, d_nrm;
+  DevBuf<int> box;
+  d_xyz.reserve(3 * n); d_nrm.reserve(3 * n); box.reserve(8);
+  copy_in(d_xyz.p, xyz, sizeof(float) * 3 * n, s);
+  copy_in(d_nrm.p, normals, sizeof(float) * 3 * n, s);
+  const int box0[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
+  int hb[8];
+  E3D_HIP(hipMemcpyAsync(box.p, box0, sizeof box0, hipMemcpyHostToDevice, s));
+  timer[0].start(s);
+  hipLaunchKernelGGL(k_surf_classify, dim3((unsigned)std::min<size_t>(div_up(n, kSurfBlock), kSurfClassifyBlocks)), dim3(kSurfBlock), 0, s, d_xyz.p, d_nrm.p, n, h, box.p);
+  copy_out(hb, box.p, sizeof hb, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  E3D_HIP(hipGetLastError());
+  if (hb[6]) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: a point lies at |coordinate| / voxel size >= 2^20");
+  const size_t m = (size_t)hb[7];
+  if (m == 0) return;
+
+  SurfParams P{};
+  P.h = h; P.R = R; P.R2 = R * R;
+  P.cell = std::max(R, h) * (1.0 + 1e-6);
+  P.pad = 1e-6 * P.cell;
+  P.D = (int)std::ceil(R / h);
+  unsigned ext[3];
+  for (int a = 0; a < 3; ++a) {
+    P.org[a] = (int)(std::floor((double)(hb[a] - kSurfOrgMargin) / 4.0) * 4.0);
+    ext[a] = (unsigned)(hb[3 + a] - P.org[a] + kSurfOrgMargin);
+    if (ext[a] >= (1u << 21)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the cloud spans more than 2^21 - 36 voxels along an axis");
+  }
+  const int key_bits = 42 + bits_for(ext[2]);
+
+  DevBuf<unsigned long long> ka, kb, vk;
+  DevBuf<unsigned> va, vb, counter;
+  ka.reserve(n); kb.reserve(n); vk.reserve(n); va.reserve(n); vb.reserve(n); counter.reserve(2);
+  hipLaunchKernelGGL(k_surf_point_keys, blocks(n), dim3(kSurfBlock), 0, s, d_xyz.p, d_nrm.p, n, P, ka.p, va.p, vk.p);
+  sort_pairs_u64_u32(ka.p, kb.p, va.p, vb.p, n, 64, run.temp, s);
+  DevBuf<float4> P4, N4;
+  P4.reserve(m); N4.reserve(m);
+  launch_permute(d_xyz.p, d_nrm.p, vb.p, m, P4.p, N4.p, s);
+  E3D_HIP(hipMemsetAsync(counter.p, 0, 2 * sizeof(unsigned), s));
+  launch_count_cells(kb.p, m, counter.p, s);
+  unsigned n_grid_cells = 0;
+  copy_out(&n_grid_cells, counter.p, sizeof(unsigned), s);
+  E3D_HIP(hipStreamSynchronize(s));
+  size_t tsize = 64;
+  while (tsize < 2 * (size_t)n_grid_cells) tsize <<= 1;
+  DevBuf<HashEntry> table;
+  table.reserve(tsize);
+  P.mask = (unsigned)(tsize - 1);
+  E3D_HIP(hipMemsetAsync(table.p, 0xFF, sizeof(HashEntry) * tsize, s));
+  launch_build_table(kb.p, m, table.p, P.mask, s);
+  timer[0].stop(s);
+
+  // ---- candidates: occupied voxels -> bricks ---------------------------------------------------------------------------------------
+  timer[1].start(s);
+  DevBuf<unsigned long long> voxels, bricks;
+  // (the sort moves the keys of the points that do not contribute, kEmptyKey, behind the m others only with all 64 bits)
+  const size_t n_sorted_voxels = run.sort_unique(vk, ka, voxels, n, 64);
+  const size_t n_voxels = n_sorted_voxels - (m < n ? 1 : 0);          // kEmptyKey is the last unique key if any point was dropped
+  const int M = ((2 * P.D + 4) >> 2) + 1;
+  const size_t n_brick_keys = n_voxels * (size_t)M * M * M;
+  if (n_brick_keys > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many occupied voxels for one call");
+  kb.reserve(n_brick_keys);
+  hipLaunchKernelGGL(k_surf_brick_keys, blocks(n_brick_keys), dim3(kSurfBlock), 0, s, voxels.p, n_voxels, P.D, M, kb.p);
+  const size_t n_bricks = run.sort_unique(kb, ka, bricks, n_brick_keys, key_bits);
+  timer[1].stop(s);
+  const size_t n_slots = n_bricks * 64;
+  if (n_slots > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many candidate corners for one call");
+
+  // ---- field -------------------------------------------------------------------------------------------------------------------------
+  DevBuf<double> f, w;
+  DevBuf<int> count;
+  f.reserve(n_slots); w.reserve(n_slots); count.reserve(n_slots);
+  timer[2].start(s);
+  hipLaunchKernelGGL(k_surf_field, dim3((unsigned)n_bricks), dim3(64), 0, s, bricks.p, P4.p, N4.p, table.p, P, f.p, w.p, count.p);
+  timer[2].stop(s);
+  E3D_HIP(hipGetLastError());
+
+  // ---- corners: the defined ones in (k, j, i) ------------------------------------------------------------------------------------------
+  timer[3].start(s);
+  run.flags.reserve(n_slots);
+  hipLaunchKernelGGL(k_surf_corner_flags, blocks(n_slots), dim3(kSurfBlock), 0, s, count.p, n_slots, run.flags.p);
+  const size_t n_corners = run.scan(n_slots);
+  if (3 * n_corners > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many corners for one call");
+  DevBuf<unsigned long long> ck;
+  DevBuf<unsigned> cs;
+  DevBuf<int> o_ijk, o_count;
+  DevBuf<double> o_f, o_w;
+  DevBuf<unsigned char> cross;
+  const SurfField F{bricks.p, n_bricks, f.p, count.p};
+  if (n_corners) {
+    ka.reserve(n_corners); ck.reserve(n_corners); va.reserve(n_corners); cs.reserve(n_corners);
+    hipLaunchKernelGGL(k_surf_corner_keys, blocks(n_slots), dim3(kSurfBlock), 0, s, bricks.p, run.flags.p, run.offsets.p, n_slots, ka.p, va.p);
+    sort_pairs_u64_u32(ka.p, ck.p, va.p, cs.p, n_corners, key_bits, run.temp, s);
+    o_ijk.reserve(3 * n_corners); o_count.reserve(n_corners); o_f.reserve(n_corners); o_w.reserve(n_corners); cross.reserve(3 * n_corners);
+    hipLaunchKernelGGL(k_surf_corner_out, blocks(n_corners), dim3(kSurfBlock), 0, s, ck.p, cs.p, n_corners, P, F, w.p, o_ijk.p, o_f.p, o_w.p, o_count.p,
+                       cross.p);
+  }
+  timer[3].stop(s);
+  out.corner_ijk.resize(3 * n_corners); out.corner_count.resize(n_corners); out.corner_f.resize(n_corners); out.corner_w.resize(n_corners);
+  copy_out(out.corner_ijk.data(), o_ijk.p, sizeof(int32_t) * 3 * n_corners, s);
+  copy_out(out.corner_count.data(), o_count.p, sizeof(int32_t) * n_corners, s);
+  copy_out(out.corner_f.data(), o_f.p, sizeof(double) * n_corners, s);
+  copy_out(out.corner_w.data(), o_w.p, sizeof(double) * n_corners, s);
+
+  // ---- extract -------------------------------------------------------------------------------------------------------------------------
+  timer[4].start(s);
+  size_t n_edges = 0, n_cells = 0;
+  DevBuf<unsigned> edges, tri;
+  DevBuf<unsigned long long> cells;
+  DevBuf<float> vertices;
+  DevBuf<int> cell_ijk;
+  if (n_corners) {
+    std::swap(run.flags, cross);                                       // the crossing flags are what is scanned next
+    n_edges = run.scan(3 * n_corners);
+  }
+  if (n_edges) {
+    if (4 * n_edges > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many crossing edges for one call");
+    edges.reserve(n_edges); kb.reserve(4 * n_edges);
+    hipLaunchKernelGGL(k_surf_edges, blocks(3 * n_corners), dim3(kSurfBlock), 0, s, ck.p, run.flags.p, run.offsets.p, 3 * n_corners, edges.p, kb.p);
+    n_cells = run.sort_unique(kb, ka, cells, 4 * n_edges, key_bits);
+    vertices.reserve(3 * n_cells); cell_ijk.reserve(3 * n_cells); tri.reserve(6 * n_edges);
+    hipLaunchKernelGGL(k_surf_vertices, blocks(n_cells), dim3(kSurfBlock), 0, s, cells.p, n_cells, P, F, vertices.p, cell_ijk.p);
+    hipLaunchKernelGGL(k_surf_triangles, blocks(n_edges), dim3(kSurfBlock), 0, s, edges.p, n_edges, ck.p, cs.p, f.p, cells.p, n_cells, tri.p);
+  }
+  timer[4].stop(s);
+  out.vertices.resize(3 * n_cells); out.cell_ijk.resize(3 * n_cells); out.triangles.resize(6 * n_edges);
+  copy_out(out.vertices.data(), vertices.p, sizeof(float) * 3 * n_cells, s);
+  copy_out(out.cell_ijk.data(), cell_ijk.p, sizeof(int32_t) * 3 * n_cells, s);
+  copy_out(out.triangles.data(), tri.p, sizeof(uint32_t) * 6 * n_edges, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  E3D_HIP(hipGetLastError());
+  for (int g = 0; g < kSurfGroups; ++g) out.ms[g] = timer[g].ms();
+  static const bool trace = env_default_off("E3D_SURFACE_TRACE");
+  if (trace)
+    fprintf(stderr, "[surface] %zu points, %zu contribute, %zu voxels, %zu bricks (%zu candidate corners), %zu grid cells, %zu corners, %zu crossing edges, %zu vertices\n",
+            n, m, n_voxels, n_bricks, n_slots, (size_t)n_grid_cells, n_corners, n_edges, n_cells);
+}
+
+}  // namespace
+
+extern "C" {
+
+e3d_surface_t* e3d_surface_reconstruct(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius) {
+  e3d_surface* h = nullptr;
+  try {
+    h = new e3d_surface;
+    reconstruct(*h, xyz, normals, n, voxel_size, support_radius);
+    return h;
+  } catch (const std::exception& e) {
+    e3d::set_last_error(e.what());
+    delete h;
+    return nullptr;
+  }
+}
+
+void e3d_surface_destroy(e3d_surface_t* h) { delete h; }
+
+int e3d_surface_counts(e3d_surface_t* h, int64_t* n_corners, int64_t* n_vertices, int64_t* n_triangles) {
+  E3D_TRY
+  if (!h) throw Error(E3D_ERR_INVALID, "e3d_surface_counts: null handle");
+  if (n_corners) *n_corners = (int64_t)h->corner_count.size();
+  if (n_vertices) *n_vertices = (int64_t)(h->vertices.size() / 3);
+  if (n_triangles) *n_triangles = (int64_t)(h->triangles.size() / 3);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_surface_get_corners(e3d_surface_t* h, int32_t* ijk, double* f, double* weight, int32_t* count) {
+  E3D_TRY
+  if (!h) throw Error(E3D_ERR_INVALID, "e3d_surface_get_corners: null handle");
+  const size_t c = h->corner_count.size();
+  if (ijk && c) memcpy(ijk, h->corner_ijk.data(), sizeof(int32_t) * 3 * c);
+  if (f && c) memcpy(f, h->corner_f.data(), sizeof(double) * c);
+  if (weight && c) memcpy(weight, h->corner_w.data(), sizeof(double) * c);
+  if (count && c) memcpy(count, h->corner_count.data(), sizeof(int32_t) * c);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_surface_get_mesh(e3d_surface_t* h, float* vertices, int32_t* cell_ijk, uint32_t* triangles) {
+  E3D_TRY
+  if (!h) throw Error(E3D_ERR_INVALID, "e3d_surface_get_mesh: null handle");
+  if ((!vertices && !h->vertices.empty()) || (!triangles && !h->triangles.empty())) throw Error(E3D_ERR_INVALID, "e3d_surface_get_mesh: null argument");
+  if (!h->vertices.empty()) memcpy(vertices, h->vertices.data(), sizeof(float) * h->vertices.size());
+  if (cell_ijk && !h->cell_ijk.empty()) memcpy(cell_ijk, h->cell_ijk.data(), sizeof(int32_t) * h->cell_ijk.size());
+  if (!h->triangles.empty()) memcpy(triangles, h->triangles.data(), sizeof(uint32_t) * h->triangles.size());
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_surface_kernel_ms(e3d_surface_t* h, float* ms, const char** names, int capacity) {
+  E3D_TRY
+  if (!h) throw Error(E3D_ERR_INVALID, "e3d_surface_kernel_ms: null handle");
+  for (int g = 0; g < kSurfGroups && g < capacity; ++g) {
+    if (ms) ms[g] = h->ms[g];
+    if (names) names[g] = kSurfGroupNames[g];
+  }
+  return kSurfGroups;
+  E3D_CATCH()
+}
+
+}  // extern "C"

@@ -41,7 +41,9 @@ namespace e3d_host {
   X(e3d_edit_create) X(e3d_edit_destroy) X(e3d_edit_size) X(e3d_edit_get_points)                                       \
   X(e3d_edit_get_selection) X(e3d_edit_set_selection) X(e3d_edit_selection_count)                                      \
   X(e3d_edit_lasso) X(e3d_edit_beyond_plane) X(e3d_edit_pick)                                                          \
-  X(e3d_edit_delete_selected) X(e3d_edit_extract_selected) X(e3d_edit_kernel_ms)
+  X(e3d_edit_delete_selected) X(e3d_edit_extract_selected) X(e3d_edit_kernel_ms)                                       \
+  X(e3d_surface_reconstruct) X(e3d_surface_destroy) X(e3d_surface_counts) X(e3d_surface_get_corners)                   \
+  X(e3d_surface_get_mesh) X(e3d_surface_kernel_ms)
 
 struct Api {
   void* handle = nullptr;

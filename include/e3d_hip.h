@@ -753,6 +753,48 @@ int64_t e3d_edit_extract_selected(e3d_edit_t* edit, float* xyz_out, size_t capac
 /* HIP-event time of the kernels of the last selection, pick, extract or delete call on this handle, in ms. */
 int e3d_edit_kernel_ms(e3d_edit_t* edit, float* ms);
 
+/* ---- SurfaceReconstructor: an occlusion mesh from an oriented point cloud ------------------------------------------------
+ * The reference sends its user to MeshLab / PoissonRecon for this step (its README, "External Surface Reconstruction": any
+ * suited method may be used; the mesh should be strongly subdivided).  This is a uniform-lattice extraction of a signed
+ * field, a capability of this library alone; it restates nothing of the reference.  h = voxel size, R = support radius.
+ * All arithmetic is f64: points, normals, h and R arrive as f32 and are converted first.  Sums may be formed in any order.
+ *
+ * Lattice.  Corner (i, j, k) (int32) lies at (h i, h j, h k): the lattice is anchored at the world origin, so the result
+ * does not depend on a bounding box.  Cell (i, j, k) is the cube between corners (i, j, k) and (i + 1, j + 1, k + 1).
+ * Contributing points.  A point contributes nothing if a component of its position or normal is not finite or if its normal
+ * is (0, 0, 0) (NormalEstimator writes NaN normals for degenerate neighbourhoods).
+ * Field.  For a corner x and a contributing point p with normal n: d2 = (dx dx + dy dy) + dz dz with (dx, dy, dz) = x - p.
+ * The point counts iff d2 < R R (strict).  Its weight is w = (1 - d2 / (R R))^2, S = sum w ((nx dx + ny dy) + nz dz),
+ * W = sum w.  A corner is defined iff at least one point counts; then f = S / W, and it is negative iff f < 0 (f == 0 is
+ * not).  Scan normals face the scanner: negative = inside the surface.
+ * Crossing edge.  The edge from corner a to b = a + e_d (d = 0, 1, 2) crosses iff both corners are defined and exactly one
+ * is negative; its crossing point is a + t h e_d with t = f_a / (f_a - f_b).  An edge with an undefined corner never
+ * crosses: the mesh ends where the data ends, and no sheet appears behind a wall seen from one side.
+ * Vertices.  A cell is active iff one of its 12 edges crosses.  Its vertex is the mean of the crossing points of its crossing
+ * edges (summed by axis d, then by the edge's offset along (d + 2) % 3, then along (d + 1) % 3), rounded to f32 at the end.
+ * Vertices are in ascending (k, j, i) of their cell.
+ * Triangles.  Each crossing edge (a, d) gives one quad over the four cells that contain it: with u = (d + 1) % 3 and
+ * v = (d + 2) % 3 the cells a + (-1, -1), a + (0, -1), a + (0, 0), a + (-1, 0) in (u, v) are q0..q3, counter-clockwise seen
+ * from +e_d.  If a is not negative the four are taken in reverse (q3, q2, q1, q0 become q0..q3), so face normals point from
+ * negative to positive.  The triangles are (q0, q1, q2) and (q0, q2, q3).  Quads are in ascending (k, j, i) of a, then d.
+ * Refused (NULL; E3D_ERR_INVALID's message in e3d_last_error): h or R not finite or <= 0; R / h > 8; a contributing point
+ * with |coordinate| / h >= 2^20 (the 21-bit cell key of the grid); contributing points whose voxels span more than
+ * 2^21 - 36 along one axis (both ends of that range at once); n >= 2^31.  n == 0 or no contributing point: an empty mesh.
+ * xyz, normals: n x 3 f32, host or device.  The result is a host-side handle; the call returns after all device work. */
+typedef struct e3d_surface e3d_surface_t;
+e3d_surface_t* e3d_surface_reconstruct(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius);
+void e3d_surface_destroy(e3d_surface_t* surface);
+/* The numbers of defined corners, vertices and triangles (each pointer may be NULL). */
+int e3d_surface_counts(e3d_surface_t* surface, int64_t* n_corners, int64_t* n_vertices, int64_t* n_triangles);
+/* The defined corners in ascending (k, j, i): lattice coordinates ijk[3 c], f[c], W[c] and the number of points that count
+ * [c], so that a field error can be told from an extraction error.  Each pointer may be NULL. */
+int e3d_surface_get_corners(e3d_surface_t* surface, int32_t* ijk, double* f, double* weight, int32_t* count);
+/* The mesh: vertices[3 v] f32, the vertices' cells cell_ijk[3 v] (may be NULL), triangles[3 t] as vertex indices. */
+int e3d_surface_get_mesh(e3d_surface_t* surface, float* vertices, int32_t* cell_ijk, uint32_t* triangles);
+/* HIP-event times of the call's kernel groups in ms and their names (static strings), at most capacity of each (either
+ * array may be NULL); returns the number of groups: grid, candidates, field, corners, extract. */
+int e3d_surface_kernel_ms(e3d_surface_t* surface, float* ms, const char** names, int capacity);
+
 #ifdef __cplusplus
 }
 #endif

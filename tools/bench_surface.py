@@ -1,0 +1,68 @@
+"""SurfaceReconstructor measurement: one synthetic room scan (synth.make_scan) with normals from the GPU estimator,
+e3d_surface_reconstruct end to end.  Reports, per kernel group (HIP events inside the call) and for the whole call (wall time,
+host copies of the cloud and of the result included), the median (min - max) over --reps calls after two warm-up calls, with the
+point, corner, vertex and triangle counts beside them.
+
+    python tools/bench_surface.py [--points 20000000] [--voxel_size 0.02] [--support_radius 0.04] [--reps 7]
+Prints one JSON line.  Not a bench.py line; numbers go to DESIGN.md section 19."""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+GROUPS = ("grid", "candidates", "field", "corners", "extract")
+
+
+def summary(values):
+    return {"median": round(float(np.median(values)), 3), "min": round(float(np.min(values)), 3), "max": round(float(np.max(values)), 3)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--points", type=int, default=20_000_000)
+    ap.add_argument("--voxel_size", type=float, default=0.02)
+    ap.add_argument("--support_radius", type=float, default=None, help="default: 2 x voxel_size")
+    ap.add_argument("--reps", type=int, default=7)
+    a = ap.parse_args()
+    e3d = importlib.import_module("dataset-pipeline_amd")
+    synth = importlib.import_module("dataset-pipeline_amd.synth")
+    dev = torch.device("cuda:0")
+    xyz, _, _ = synth.make_scan(a.points, (5.0, 5.0, 1.5), 0.0, 5, device=dev)
+    nrm, _ = e3d.normals_knn(xyz, 8)
+    xyz_h = xyz.cpu().numpy()
+    del xyz
+    torch.cuda.empty_cache()
+    runs = []
+    counts = None
+    for rep in range(2 + a.reps):
+        tm = {}
+        t0 = time.perf_counter()
+        v, t, c = e3d.reconstruct_surface(xyz_h, nrm, a.voxel_size, a.support_radius, return_corners=True, timings=tm)
+        wall = (time.perf_counter() - t0) * 1e3
+        if rep >= 2:
+            runs.append([tm[g + "_ms"] for g in GROUPS] + [wall])
+        counts = (len(c["ijk"]), len(v), len(t), int(c["count"].max(initial=0)), float(c["count"].mean()) if len(c["count"]) else 0.0)
+    runs = np.array(runs)
+    out = {"points": a.points, "contributing_points": int((~np.isnan(nrm).any(1)).sum()), "voxel_size": a.voxel_size,
+           "support_radius": a.support_radius if a.support_radius is not None else 2 * a.voxel_size,
+           "corners": counts[0], "vertices": counts[1], "triangles": counts[2], "max_contributors": counts[3],
+           "mean_contributors": round(counts[4], 1), "reps": a.reps}
+    for i, g in enumerate(GROUPS):
+        out[g + "_ms"] = summary(runs[:, i])
+    out["kernels_ms"] = summary(runs[:, :len(GROUPS)].sum(1))
+    out["call_wall_ms"] = summary(runs[:, -1])
+    evals = counts[0] * counts[4]
+    out["counting_point_evaluations_per_s"] = round(evals / (out["field_ms"]["median"] * 1e-3), 1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
