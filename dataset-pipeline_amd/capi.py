@@ -182,6 +182,14 @@ SIGNATURES = {
     "e3d_surface_get_corners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_surface_get_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_surface_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    # ReconstructionEvaluator: accuracy and completeness of a reconstruction against the scans
+    "e3d_evaluate_reconstruction": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int]),
+    "e3d_eval_destroy": (None, [C.c_void_p]),
+    "e3d_eval_counts": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_eval_get_scores": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_eval_get_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_eval_get_voxels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_eval_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
 }
 
 
@@ -587,6 +595,63 @@ def reconstruct_surface(xyz, normals, voxel_size, support_radius=None, return_co
     finally:
         lib().e3d_surface_destroy(handle)
     return (vertices, triangles, corners) if return_corners else (vertices, triangles)
+
+
+def evaluate_reconstruction(rec, scans, origins, tolerances=(0.01, 0.02, 0.05, 0.1, 0.2, 0.5), voxel_size=0.01, cube_map_size=2048,
+                            return_classes=False, return_voxels=False, timings=None):
+    """ReconstructionEvaluator (include/e3d_hip.h, e3d_evaluate_reconstruction).  rec[n, 3] f32 (numpy or torch, host or device); scans:
+    a sequence of [n_s, 3] f32 arrays in the global frame; origins[S, 3] f32: the scanner positions.  Returns a dict: tolerances[T] f32,
+    completeness[T], accuracy[T], f1[T] f64, n_scan_voxels, n_rec_voxels, evaluated_voxels[T] int64; with return_classes near_rec[n],
+    free[n], near_scan[sum n_s] uint8 (255 = ignored point); with return_voxels scan_voxels and rec_voxels: dicts of ijk[v, 3],
+    n_points[v], count_a[v, T] (# complete / # accurate), count_b[v, T] (# inaccurate) int32 in ascending (k, j, i).  timings: a dict
+    that receives the HIP-event time of every kernel group as <group>_ms."""
+    keep = []
+    scans = [s.detach().cpu().numpy() if _is_torch(s) else s for s in scans]
+    parts = [np.ascontiguousarray(s, np.float32).reshape(-1, 3) for s in scans]
+    scan_xyz = np.concatenate(parts) if parts else np.zeros((0, 3), np.float32)
+    offsets = np.zeros(len(parts) + 1, np.int64)
+    offsets[1:] = np.cumsum([len(p) for p in parts])
+    origins = np.ascontiguousarray(origins, np.float32).reshape(-1, 3)
+    if len(origins) != len(parts):
+        raise E3DError("evaluate_reconstruction: %d scans but %d origins" % (len(parts), len(origins)))
+    tol = np.ascontiguousarray(tolerances, np.float32).reshape(-1)
+    T = len(tol)
+    n = int(rec.shape[0])
+    handle = lib().e3d_evaluate_reconstruction(_ptr(rec, np.float32, keep) if n else None, n, C.c_void_p(scan_xyz.ctypes.data) if len(scan_xyz) else None,
+                                               C.c_void_p(offsets.ctypes.data), C.c_void_p(origins.ctypes.data), len(parts), C.c_void_p(tol.ctypes.data), T,
+                                               float(np.float32(voxel_size)), int(cube_map_size))
+    if not handle:
+        _err("e3d_evaluate_reconstruction")
+    try:
+        nsv, nrv = C.c_int64(0), C.c_int64(0)
+        evaluated = np.zeros(T, np.int64)
+        scores = np.zeros((3, T), np.float64)
+        if lib().e3d_eval_counts(handle, C.byref(nsv), C.byref(nrv), C.c_void_p(evaluated.ctypes.data)) < 0:
+            _err("e3d_eval_counts")
+        if lib().e3d_eval_get_scores(handle, C.c_void_p(scores.ctypes.data)) < 0:
+            _err("e3d_eval_get_scores")
+        out = {"tolerances": tol, "completeness": scores[0], "accuracy": scores[1], "f1": scores[2], "n_scan_voxels": nsv.value,
+               "n_rec_voxels": nrv.value, "evaluated_voxels": evaluated}
+        if return_classes:
+            out["near_rec"] = np.zeros(n, np.uint8); out["free"] = np.zeros(n, np.uint8); out["near_scan"] = np.zeros(len(scan_xyz), np.uint8)
+            if lib().e3d_eval_get_classes(handle, *(C.c_void_p(out[k].ctypes.data) for k in ("near_rec", "free", "near_scan"))) < 0:
+                _err("e3d_eval_get_classes")
+        if return_voxels:
+            for kind, name, nv in ((0, "scan_voxels", nsv.value), (1, "rec_voxels", nrv.value)):
+                v = {"ijk": np.zeros((nv, 3), np.int32), "n_points": np.zeros(nv, np.int32), "count_a": np.zeros((nv, T), np.int32),
+                     "count_b": np.zeros((nv, T), np.int32)}
+                if lib().e3d_eval_get_voxels(handle, kind, *(C.c_void_p(v[k].ctypes.data) for k in ("ijk", "n_points", "count_a", "count_b"))) < 0:
+                    _err("e3d_eval_get_voxels")
+                out[name] = v
+        if timings is not None:
+            ms = (C.c_float * 16)()
+            names = (C.c_char_p * 16)()
+            g = lib().e3d_eval_kernel_ms(handle, ms, names, 16)
+            for i in range(min(g, 16)):
+                timings[names[i].decode() + "_ms"] = float(ms[i])
+    finally:
+        lib().e3d_eval_destroy(handle)
+    return out
 
 
 CUBE_MAP_FACES = ("front", "left", "back", "right", "down", "up")

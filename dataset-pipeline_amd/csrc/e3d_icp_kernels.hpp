@@ -224,6 +224,10 @@ void sort_keys_u64(unsigned long long* keys_in, unsigned long long* keys_out, si
 void exclusive_max_scan_u32(unsigned* data, size_t n, DevBuf<char>& temp, hipStream_t s);
 // exclusive prefix sum of n 0/1 flags into 32-bit offsets (rocPRIM, e3d_sort.hip): the splat compaction
 void exclusive_sum_u8_u32(const unsigned char* in, unsigned* out, size_t n, DevBuf<char>& temp, hipStream_t s);
+// a stable compaction's first half: the exclusive offsets of n 0/1 flags and, after a synchronisation of s, the number of flags set
+size_t compaction_offsets(const unsigned char* flags, size_t n, DevBuf<unsigned>& offsets, DevBuf<char>& temp, hipStream_t s);
+// flags[j] = 1 where keys[j] is the first of a run of equal keys (sorted keys): compacted, the unique keys / the runs' starts
+void launch_flag_run_starts(const unsigned long long* keys, size_t n, unsigned char* flags, hipStream_t s);
 // the exact kNN (e3d_normals.hip) of a finite cloud (host or device xyz) with each query's k-th squared distance (input order)
 // left on the device; `use(kth, query_order, stream)` runs while the kNN workspace is held: query_order lists the queries in
 // the pass's grid-cell order (w = input index as bits)

@@ -78,6 +78,22 @@ __device__ __forceinline__ unsigned hash_key(unsigned long long k) {
   return (unsigned)k;
 }
 
+// the run [s, e) of the points of cell (x, y, z) in a hashed grid (k_build_table); empty for a cell without points or outside the
+// key's 21 bits per axis
+__device__ __forceinline__ void hash_cell_range(const HashEntry* __restrict__ table, unsigned mask, int x, int y, int z, unsigned& s, unsigned& e) {
+  s = 0; e = 0;
+  constexpr int kMaxC = (1 << 21) - 1;
+  if (x < 0 || y < 0 || z < 0 || x > kMaxC || y > kMaxC || z > kMaxC) return;
+  const unsigned long long key = cell_key(x, y, z);
+  unsigned h = hash_key(key) & mask;
+  for (;;) {
+    const HashEntry en = table[h];
+    if (en.key == key) { s = en.start; e = en.end; return; }
+    if (en.key == kEmptyKey) return;
+    h = (h + 1) & mask;
+  }
+}
+
 // ---- wave / block reductions ---------------------------------------------------------------------
 __device__ __forceinline__ double wave_sum(double v) {
 #pragma unroll

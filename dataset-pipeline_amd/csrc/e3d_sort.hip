@@ -68,4 +68,25 @@ void exclusive_sum_u8_u32(const unsigned char* in, unsigned* out, size_t n, DevB
   E3D_HIP(rocprim::exclusive_scan(temp.p, bytes, in, out, 0u, n, rocprim::plus<unsigned>(), s));
 }
 
+size_t compaction_offsets(const unsigned char* flags, size_t n, DevBuf<unsigned>& offsets, DevBuf<char>& temp, hipStream_t s) {
+  if (n == 0) return 0;
+  offsets.reserve(n);
+  exclusive_sum_u8_u32(flags, offsets.p, n, temp, s);
+  unsigned last = 0; unsigned char lf = 0;
+  copy_out(&last, offsets.p + (n - 1), sizeof last, s);
+  copy_out(&lf, flags + (n - 1), 1, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  return (size_t)last + (lf ? 1 : 0);
+}
+
+__global__ __launch_bounds__(kBlock) void k_flag_run_starts(const unsigned long long* __restrict__ keys, size_t n, unsigned char* __restrict__ flags) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j < n) flags[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1 : 0;
+}
+
+void launch_flag_run_starts(const unsigned long long* keys, size_t n, unsigned char* flags, hipStream_t s) {
+  if (n == 0) return;
+  hipLaunchKernelGGL(k_flag_run_starts, dim3((unsigned)div_up(n, kBlock)), dim3(kBlock), 0, s, keys, n, flags);
+}
+
 }  // namespace e3d

@@ -121,11 +121,7 @@ __global__ __launch_bounds__(kSurfBlock) void k_surf_point_keys(const float* __r
   voxel_keys[i] = vk;
 }
 
-// flags of the first element of every run of equal keys (sorted keys): the unique keys after a stable compaction
-__global__ __launch_bounds__(kSurfBlock) void k_surf_flag_first(const unsigned long long* __restrict__ keys, size_t n, unsigned char* __restrict__ flags) {
-  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (j < n) flags[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1 : 0;
-}
+// the unique keys of sorted keys: those flagged by launch_flag_run_starts, compacted
 __global__ __launch_bounds__(kSurfBlock) void k_surf_scatter_keys(const unsigned long long* __restrict__ keys, const unsigned char* __restrict__ flags,
                                                                   const unsigned* __restrict__ offsets, size_t n, unsigned long long* __restrict__ out) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -150,20 +146,6 @@ __global__ __launch_bounds__(kSurfBlock) void k_surf_brick_keys(const unsigned l
     b[a] = min(lo + s[a], hi);
   }
   out[t] = cell_key(b[0], b[1], b[2]);
-}
-
-__device__ __forceinline__ void surf_cell_range(const HashEntry* __restrict__ table, unsigned mask, int x, int y, int z, unsigned& s, unsigned& e) {
-  s = 0; e = 0;
-  constexpr int kMaxC = (1 << 21) - 1;
-  if (x < 0 || y < 0 || z < 0 || x > kMaxC || y > kMaxC || z > kMaxC) return;
-  const unsigned long long key = cell_key(x, y, z);
-  unsigned h = hash_key(key) & mask;
-  for (;;) {
-    const HashEntry en = table[h];
-    if (en.key == key) { s = en.start; e = en.end; return; }
-    if (en.key == kEmptyKey) return;
-    h = (h + 1) & mask;
-  }
 }
 
 // The field at the 64 corners of one brick per wave (block = one wave, so the barriers are the wave's own).
@@ -191,7 +173,7 @@ __global__ __launch_bounds__(64) void k_surf_field(const unsigned long long* __r
   for (int base = 0; base < ncell; base += 64) {
     const int idx = base + lane;
     unsigned s = 0, e = 0;
-    if (idx < ncell) surf_cell_range(table, P.mask, c0[0] + idx % nc[0], c0[1] + (idx / nc[0]) % nc[1], c0[2] + idx / (nc[0] * nc[1]), s, e);
+    if (idx < ncell) hash_cell_range(table, P.mask, c0[0] + idx % nc[0], c0[1] + (idx / nc[0]) % nc[1], c0[2] + idx / (nc[0] * nc[1]), s, e);
     unsigned long long nonempty = __ballot(e > s);
     while (nonempty) {
       const int src = __ffsll((long long)nonempty) - 1;
@@ -391,16 +373,7 @@ struct SurfRun {
   ~SurfRun() { if (s) (void)hipStreamDestroy(s); }
 
   // exclusive offsets of n flags; the number set
-  size_t scan(size_t n) {
-    if (n == 0) return 0;
-    offsets.reserve(n);
-    exclusive_sum_u8_u32(flags.p, offsets.p, n, temp, s);
-    unsigned last = 0; unsigned char lf = 0;
-    copy_out(&last, offsets.p + (n - 1), sizeof last, s);
-    copy_out(&lf, flags.p + (n - 1), 1, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    return (size_t)last + (lf ? 1 : 0);
-  }
+  size_t scan(size_t n) { return compaction_offsets(flags.p, n, offsets, temp, s); }
   // sorts keys[0, n) (into `sorted`) and leaves their unique values in `out`; the number of unique keys
   size_t sort_unique(DevBuf<unsigned long long>& keys, DevBuf<unsigned long long>& sorted, DevBuf<unsigned long long>& out, size_t n, int end_bit) {
     if (n == 0) return 0;
@@ -408,7 +381,7 @@ struct SurfRun {
     sort_keys_u64(keys.p, sorted.p, n, end_bit, temp, s);
     flags.reserve(n);
     const unsigned nb = (unsigned)div_up(n, kSurfBlock);
-    hipLaunchKernelGGL(k_surf_flag_first, dim3(nb), dim3(kSurfBlock), 0, s, sorted.p, n, flags.p);
+    launch_flag_run_starts(sorted.p, n, flags.p, s);
     const size_t m = scan(n);
     out.reserve(m);
     hipLaunchKernelGGL(k_surf_scatter_keys, dim3(nb), dim3(kSurfBlock), 0, s, sorted.p, flags.p, offsets.p, n, out.p);

@@ -795,6 +795,66 @@ int e3d_surface_get_mesh(e3d_surface_t* surface, float* vertices, int32_t* cell_
  * array may be NULL); returns the number of groups: grid, candidates, field, corners, extract. */
 int e3d_surface_kernel_ms(e3d_surface_t* surface, float* ms, const char** names, int capacity);
 
+/* ---- ReconstructionEvaluator: accuracy and completeness of a reconstruction against the scans ----------------------------
+ * The ETH3D evaluation scheme the reference's README describes and neither tree computes: a reconstruction point within a
+ * tolerance of the scans is accurate, one in the free space between a scanner and what it measured is wrong, everything else
+ * is unobserved and not judged.  The rules are this library's; they restate nothing of the reference.
+ *
+ * Inputs: reconstruction points r (n_rec x 3 f32); S >= 1 scans, scan s with points q (f32, global frame; the scans are
+ * concatenated, scan s is rows [scan_offsets[s], scan_offsets[s + 1]) with scan_offsets[0] == 0) and scanner origin o_s
+ * (3 f32); T tolerances t_0 < ... < t_{T-1}, 1 <= T <= 8, finite and > 0 (f32); voxel size h > 0; cube-map size N, even,
+ * 2 <= N <= 8192.  All arithmetic is f32 with the stated order and no contraction, except where f64 is named.
+ *
+ * 1. Ignored points.  A point with a non-finite coordinate is ignored: it is neighbour of nothing, lands in no pixel and no
+ *    voxel, and its classes are 255.
+ * 2. Near class (both directions).  d2(a, b) = ((dx dx) + dy dy) + dz dz with dx = a.x - b.x ... .  thr_i = (float)((double)
+ *    t_i t_i).  near(a | B) is the smallest i with min_{b in B} d2(a, b) <= thr_i (inclusive), or T if there is none.
+ *    near_scan[q] = near(q | reconstruction), near_rec[r] = near(r | all scans together).  Only the class is public, not the
+ *    distance or the partner.
+ * 3. Range image of scan s.  For d = p - o_s (componentwise f32): m = max(|dx|, |dy|, |dz|); there is no pixel if m == 0 or
+ *    d is not finite.  Axis is the first of x, y, z with |d_axis| == m, face = 2 axis + (d_axis < 0), (a, b) are the other
+ *    two components in cyclic order: x -> (y, z), y -> (z, x), z -> (x, y).  col = min(N - 1, (int)floorf((a / m + 1.0f) *
+ *    (float)(N / 2))), row the same from b.  range(p) = sqrtf(d2(p, o_s)).  rmin_s[face, row, col] is the minimum of range(q)
+ *    over the scan's non-ignored points in that pixel; the pixel is empty without one.
+ * 4. Free class.  free_s[r] is the number of i with range(r) + t_i < rmin_s[pixel_s(r)] (f32 addition), 0 if r has no pixel
+ *    or the pixel is empty.  The addition is monotone in t, so these i are a prefix of the tolerances.  free[r] = max_s
+ *    free_s[r].  Using the pixel's minimum never calls anything behind the nearest return of a pixel free space.
+ * 5. Verdict at tolerance i.  r is accurate iff near_rec[r] <= i, otherwise inaccurate iff i < free[r], otherwise unobserved.
+ *    q is complete iff near_scan[q] <= i.
+ * 6. Voxels.  v = (int)floorf(c / h) per coordinate (f32 division).  Scan voxels are over all scans' non-ignored points
+ *    together, reconstruction voxels over the non-ignored r.  A non-ignored point with fabsf(c) / h >= 2^20 is refused, as
+ *    in e3d_surface_reconstruct; v + 2^20 is then the 21-bit key field of its axis, so no accepted cloud spans too many
+ *    voxels for the key.  Voxels are listed in ascending (k, j, i).
+ * 7. Scores, f64.  completeness_i is the mean over the scan voxels of (# complete at i) / (# points); accuracy_i is the mean,
+ *    over the reconstruction voxels with acc + inacc > 0 at i (the evaluated voxels), of acc / (acc + inacc); f1_i =
+ *    ((2 a) c) / (a + c).  Each of the three is 0 where its denominator is 0.  Per-voxel ratios are single f64 divisions of
+ *    integers; the sums are formed on the GPU in a fixed order, so two calls return identical bytes.
+ *
+ * Refused (NULL; E3D_ERR_INVALID's message in e3d_last_error): S < 1; scan_offsets not starting at 0 or descending; T
+ * outside 1 .. 8; a tolerance not finite, <= 0 or not above its predecessor; h not finite or <= 0; N odd or outside
+ * 2 .. 8192; a point of rule 6; n_rec or the number of scan points >= 2^31.
+ * rec_xyz, scan_xyz: host or device; scan_offsets (S + 1), scan_origins (S x 3), tolerances (T): host.  The result is a
+ * host-side handle; the call returns after all device work, and no device memory is kept. */
+typedef struct e3d_eval e3d_eval_t;
+e3d_eval_t* e3d_evaluate_reconstruction(const float* rec_xyz, size_t n_rec, const float* scan_xyz, const int64_t* scan_offsets,
+                                        const float* scan_origins, int n_scans, const float* tolerances, int n_tolerances,
+                                        float voxel_size, int cube_map_size);
+void e3d_eval_destroy(e3d_eval_t* eval);
+/* The numbers of scan voxels and reconstruction voxels and, per tolerance, of evaluated reconstruction voxels
+ * (evaluated_voxels[T]).  Each pointer may be NULL. */
+int e3d_eval_counts(e3d_eval_t* eval, int64_t* n_scan_voxels, int64_t* n_rec_voxels, int64_t* evaluated_voxels);
+/* scores[3 T]: completeness[T], accuracy[T], f1[T]. */
+int e3d_eval_get_scores(e3d_eval_t* eval, double* scores);
+/* near_rec[n_rec], free[n_rec], near_scan[number of scan points].  Each pointer may be NULL. */
+int e3d_eval_get_classes(e3d_eval_t* eval, uint8_t* near_rec, uint8_t* free_class, uint8_t* near_scan);
+/* The voxels of one kind (0: scan, 1: reconstruction) in ascending (k, j, i): ijk[3 v], the number of points n_points[v],
+ * and per tolerance count_a[T v + i] = # complete (scan) or # accurate (reconstruction) and count_b[T v + i] = # inaccurate
+ * (reconstruction; zeros for the scan voxels).  Each pointer may be NULL. */
+int e3d_eval_get_voxels(e3d_eval_t* eval, int kind, int32_t* ijk, int32_t* n_points, int32_t* count_a, int32_t* count_b);
+/* HIP-event times of the call's kernel groups in ms and their names (static strings), at most capacity of each (either
+ * array may be NULL); returns the number of groups: grid, search, range, voxels. */
+int e3d_eval_kernel_ms(e3d_eval_t* eval, float* ms, const char** names, int capacity);
+
 #ifdef __cplusplus
 }
 #endif
