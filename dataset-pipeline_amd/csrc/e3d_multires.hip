@@ -220,6 +220,15 @@ extern "C" int64_t e3d_merge_close_points(float merge_distance, int num_scans, c
     if (!(merge_distance > 0.f) || !std::isfinite(merge_distance)) throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: merge distance must be positive");
     if (num_scans < 1 || num_scans > kMergeMaxScans) throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: 1..%d scans supported", kMergeMaxScans));
     if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: more than 2^31-1 points");
+    // Inputs the reference does not define are refused on the host, before anything is launched.  A NaN point would become a centre
+    // without neighbours (mean 0 / 0); one infinite coordinate makes the bounding box infinite, the cell size grows to inf and every
+    // point lands in ONE cell -- quadratic work inside the wait loop of k_merge_decide; a scan index >= num_scans is counted but can
+    // never win the majority (colour divided by a zero count).
+    for (size_t i = 0; i < 3 * n; ++i)
+      if (!std::isfinite(xyz[i])) throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: point %zu has a non-finite coordinate", i / 3));
+    for (size_t i = 0; i < n; ++i)
+      if ((int)scan_indices[i] >= num_scans)
+        throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: point %zu has scan index %d, but there are %d scans", i, (int)scan_indices[i], num_scans));
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
     if (n == 0) return 0;

@@ -647,7 +647,9 @@ int e3d_reg_point_radius_minmax(e3d_reg_t* reg, const float* xyz, size_t n, floa
 /* MergeClosePoints (src/opt/multi_scale_point_cloud.cc:44-124): greedy merge in point order -- every point not yet absorbed
  * becomes a centre and absorbs all points strictly within merge_distance -- computed in parallel (the centres are the
  * lexicographically first maximal independent set).  Outputs (capacity n each) in centre order: mean position, mean colour of
- * the scan with most merged points, that scan's index, maximum of max_radius.  Returns the number of output points. */
+ * the scan with most merged points, that scan's index, maximum of max_radius.  Returns the number of output points.
+ * The inputs are host arrays.  Refused with E3D_ERR_INVALID before anything runs on the device: a point with a NaN or infinite
+ * coordinate, and a scan index >= num_scans (the reference defines neither; 1 <= num_scans <= 16, merge_distance finite and > 0). */
 int64_t e3d_merge_close_points(float merge_distance, int num_scans, const float* xyz, const float* colors,
                                const uint8_t* scan_indices, const float* max_radius, size_t n, float* out_xyz,
                                float* out_colors, uint8_t* out_scan_indices, float* out_max_radius);

@@ -53,6 +53,8 @@ def merge_close_points(merge_distance, num_scans, pts, colors, scan_idx, max_rad
     pts = np.ascontiguousarray(pts, np.float32); colors = np.ascontiguousarray(colors, np.float32)
     scan_idx = np.ascontiguousarray(scan_idx, np.uint8); max_radius = np.ascontiguousarray(max_radius, np.float32)
     n = len(pts)
+    if n and (int(scan_idx.max()) >= num_scans or not np.isfinite(pts).all()):        # undefined in the reference; the C loop would index past count[]
+        raise ValueError("merge_close_points: a scan index >= num_scans or a non-finite coordinate")
     op = np.zeros((n + 1, 3), np.float32); oc = np.zeros(n + 1, np.float32); osc = np.zeros(n + 1, np.uint8); om = np.zeros(n + 1, np.float32)
     m = lib().oracle_merge_close_points(np.float32(merge_distance), num_scans, _p(pts, C.c_float), _p(colors, C.c_float), _p(scan_idx, C.c_uint8),
                                         _p(max_radius, C.c_float), n, _p(op, C.c_float), _p(oc, C.c_float), _p(osc, C.c_uint8), _p(om, C.c_float))

@@ -80,6 +80,166 @@ def test_point_radius_minmax_matches_oracle(e3d, mr, model):
     assert 0.5 * 2.5 / 210 / 2 < np.median(gmn[seen_o]) < 2 * 3.5 / 210 / 2
 
 
+# ---- MergeClosePoints against the brute-force restatement (tests/multires_ref.py) ---------------------------------------------------
+# tests/test_multires_host.py shows on the CPU that these inputs tell a closed radius, another tie rule and another absorption rule
+# apart, and that the restatement equals the oracle bit for bit on each of them.
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32 if a.dtype == np.float32 else a.dtype)
+
+
+def _check_against_restatement(e3d, name, exact):
+    """Always exact: the number of outputs, out_scan, out_max_radius (a wrong or reordered centre shows in them and in the means).
+    Means: bit for bit where the f32 sums are exact, else within g(m) max|x_j| (g(c) max|col_j|) of the f64 mean -- derived in
+    multires_ref.gamma, not measured."""
+    import multires_ref as ref
+    R = ref.reference(name)
+    g = e3d.merge_close_points(*ref.case(name))
+    assert [len(a) for a in g] == [len(R["m"])] * 4 and g[0].shape == (len(R["m"]), 3)
+    assert np.array_equal(g[2], R["scan"])
+    assert np.array_equal(_bits(g[3]), _bits(R["mxr"]))
+    rp, rc = ref.mean_deviation_ratios(g[0], g[1], R)
+    print("%s: %d centres, m <= %d, deviation / bound: position %.3g, colour %.3g" % (name, len(R["m"]), R["m"].max() if len(R["m"]) else 0, rp, rc))
+    assert rp <= 1.0 and rc <= 1.0
+    if exact:
+        assert np.array_equal(_bits(g[0]), _bits(R["xyz"])) and np.array_equal(_bits(g[1]), _bits(R["col"]))
+    return g, R
+
+
+@pytest.mark.parametrize("n", [0, 1, 2, 63, 64, 65, 255, 256, 257, 1000])
+def test_merge_sizes_at_wave_and_block_boundaries(e3d, n):
+    g, R = _check_against_restatement(e3d, "size_%d" % n, exact=False)
+    if n == 0:
+        assert g[0].shape == (0, 3) and g[1].shape == g[2].shape == g[3].shape == (0,)
+    if n >= 63:
+        assert 1 < len(g[0]) < n
+
+
+@pytest.mark.parametrize("name", ["lattice", "lattice_m64", "lattice_p4096"])
+def test_merge_lattice_exact(e3d, name):
+    """pairs at exactly the merge distance, duplicates, integer colours; also in negative coordinates and 4096 away from the origin"""
+    g, R = _check_against_restatement(e3d, name, exact=True)
+    assert R["m"].max() <= 32                  # the sums stay exact
+
+
+def test_merge_lattice_far_from_the_origin(e3d):
+    """the same sites around (2^17, -2^17, 2^17 - 3): the cell size is dominated by 16 FLT_EPSILON * magnitude, the sums round"""
+    import multires_ref as ref
+    g, R = _check_against_restatement(e3d, "lattice_far", exact=False)
+    assert np.array_equal(g[2], ref.reference("lattice")["scan"]) and len(g[0]) == len(ref.reference("lattice")["m"])
+
+
+@pytest.mark.parametrize("order", ["increasing", "decreasing", "shuffled"])
+def test_merge_chain(e3d, order):
+    """a line on which every decision waits for the one before it"""
+    import multires_ref as ref
+    g, R = _check_against_restatement(e3d, "chain_" + order, exact=True)
+    if order == "increasing":                  # closed form: the even positions, the ends aside each the mean of three points
+        P = ref.case("chain_increasing")[2]
+        assert len(g[0]) == ref.CHAIN_N // 2 and np.array_equal(g[0][1:], P[2::2]) and np.array_equal(g[0][0], (P[0] + P[1]) / 2)
+
+
+def test_merge_dense_neighbourhoods(e3d):
+    """more than kMergeList lower-index neighbours, the deciding centre in the own wave and in other blocks"""
+    g, R = _check_against_restatement(e3d, "dense", exact=False)
+    assert R["m"].max() > 300
+
+
+def test_merge_sixteen_scans(e3d):
+    g, R = _check_against_restatement(e3d, "scans16", exact=False)
+    assert len(set(g[2].tolist())) == 16
+    g, R = _check_against_restatement(e3d, "scans16_all15", exact=False)
+    assert (g[2] == 15).all()
+
+
+def test_merge_twice_same_bytes(e3d):
+    import multires_ref as ref
+    for name in ("size_1000", "dense", "scans16"):
+        a = e3d.merge_close_points(*ref.case(name)); b = e3d.merge_close_points(*ref.case(name))
+        assert all(x.tobytes() == y.tobytes() for x, y in zip(a, b))
+
+
+def _good_70():
+    import multires_ref as ref
+    dist, scans, P, col, sidx, mxr = ref.case("size_1000")
+    return dist, scans, P[:70].copy(), col[:70].copy(), sidx[:70].copy(), mxr[:70].copy()
+
+
+def _refused_then_good(e3d, bad_args, good_args, good_bytes):
+    with pytest.raises(e3d.E3DError):
+        e3d.merge_close_points(*bad_args)
+    assert [a.tobytes() for a in e3d.merge_close_points(*good_args)] == good_bytes
+
+
+def test_merge_refuses_non_finite_coordinates(e3d):
+    """the reference defines none of these; a NaN point would become a centre without neighbours, an infinite one collapses the grid"""
+    good = _good_70()
+    good_bytes = [a.tobytes() for a in e3d.merge_close_points(*good)]
+    for value in (np.nan, np.inf, -np.inf):
+        for axis in range(3):
+            for index in (0, 37, 69):
+                P = good[2].copy(); P[index, axis] = value
+                _refused_then_good(e3d, (good[0], good[1], P) + good[3:], good, good_bytes)
+
+
+def test_merge_refuses_scan_indices_beyond_num_scans(e3d):
+    good = _good_70()
+    good_bytes = [a.tobytes() for a in e3d.merge_close_points(*good)]
+    for value in (good[1], 255):
+        for index in (0, 37, 69):
+            sidx = good[4].copy(); sidx[index] = value
+            _refused_then_good(e3d, good[:4] + (sidx,) + good[5:], good, good_bytes)
+    sidx = np.full(70, 255, np.uint8)            # a whole neighbourhood without a valid scan
+    _refused_then_good(e3d, good[:4] + (sidx,) + good[5:], good, good_bytes)
+
+
+def test_merge_refuses_bad_merge_distance(e3d):
+    good = _good_70()
+    good_bytes = [a.tobytes() for a in e3d.merge_close_points(*good)]
+    for dist in (np.nan, np.inf, -np.inf, -0.05):
+        _refused_then_good(e3d, (dist,) + good[1:], good, good_bytes)
+
+
+# ---- point_radius_minmax at small sizes and on a handle without images ----------------------------------------------------------------
+@pytest.fixture(scope="module")
+def pinhole_scene(e3d):
+    from reg_util import make_multi_image_scene
+    M = make_multi_image_scene(n_points=8000, n_images=3, seed=21, model=0)
+    G = e3d.RegProblem(e3d.default_reg_params(image_scale_count=M["n_levels"], point_neighbor_count=M["K"]))
+    G.set_intrinsics(0, M["width"], M["height"], M["params"], 0, M["n_levels"], camera_type=0)
+    G.set_splat_points(M["pts"])
+    images = {}
+    for i, im in enumerate(M["images"]):
+        G.set_image(i, 0, im["pyr"]); G.set_image_pose(i, im["q_true"], im["t_true"])
+        images[i] = dict(intr=0, pyr=im["pyr"], masks=None, q=im["q_true"], t=im["t_true"])
+    intr = {0: dict(w=M["width"], h=M["height"], params=M["params"], min=0, n=M["n_levels"], model=0)}
+    return M, G, images, intr
+
+
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_point_radius_minmax_small_inputs(e3d, mr, pinhole_scene, n):
+    M, G, images, intr = pinhole_scene
+    pts = np.ascontiguousarray(M["pts"][:n])
+    gmn, gmx = G.point_radius_minmax(pts)
+    omn, omx = mr.point_radius_minmax(pts, images, intr, M["pts"], M["n_levels"])
+    assert gmn.shape == gmx.shape == (n,)
+    seen = np.isfinite(omn)
+    assert np.array_equal(np.isfinite(gmn), seen) and np.array_equal(np.isfinite(gmx), np.isfinite(omx)) and seen.sum() >= min(n, 1)
+    assert np.array_equal(gmn[~seen], omn[~seen]) and np.array_equal(gmx[~seen], omx[~seen])        # +inf / -inf kept
+    if n:
+        tol = 1e-6                      # as test_point_radius_minmax_matches_oracle: shared elementary functions
+        assert np.abs(gmn[seen] - omn[seen]).max() <= tol * omn[seen].max()
+        assert np.abs(gmx[seen] - omx[seen]).max() <= tol * omx[seen].max()
+
+
+@pytest.mark.parametrize("n", [0, 1, 65])
+def test_point_radius_minmax_without_images(e3d, pinhole_scene, n):
+    M = pinhole_scene[0]
+    G = e3d.RegProblem(e3d.default_reg_params(image_scale_count=M["n_levels"], point_neighbor_count=M["K"]))
+    G.set_intrinsics(0, M["width"], M["height"], M["params"], 0, M["n_levels"], camera_type=0)
+    mn, mx = G.point_radius_minmax(np.ascontiguousarray(M["pts"][:n]))
+    assert mn.shape == mx.shape == (n,) and (mn == np.inf).all() and (mx == -np.inf).all()
+
+
 # ---- the reference's own known-answer tests (src/opt/test/test_multi_scale_point_cloud.cc) through the HIP path -------------------
 def test_merge_close_points_reference_kat(e3d):
     from test_oracle_multires import MERGE_KAT as K, check_merge_kat
