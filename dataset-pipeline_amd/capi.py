@@ -26,6 +26,18 @@ class PairRecord(C.Structure):
                 ("count", C.c_int64), ("distance_sum", C.c_double)]
 
 
+class UndistortPlan(C.Structure):
+    """e3d_undistort_plan: a PINHOLE camera, (0, 0) = the centre of the top-left pixel."""
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float)]
+
+    def astuple(self):
+        return (self.width, self.height, self.fx, self.fy, self.cx, self.cy)
+
+
+UNDISTORT_U8, UNDISTORT_RGB, UNDISTORT_MASK, UNDISTORT_NEAREST = 0, 1, 2, 3
+_UNDISTORT_PIXEL = {0: (np.uint8, ()), 1: (np.uint8, (3,)), 2: (np.uint8, ()), 3: (np.float32, ())}
+
+
 class IterRecord(C.Structure):
     _fields_ = [("iteration", C.c_int32), ("inner_iterations", C.c_int32), ("full_passes", C.c_int32),
                 ("cost_passes", C.c_int32), ("multi_cost_passes", C.c_int32), ("multi_cost_poses", C.c_int32),
@@ -137,6 +149,9 @@ SIGNATURES = {
     "e3d_reg_pick_scan_points": (C.c_int64, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_image_bearings": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
     "e3d_reg_project_points": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "e3d_reg_undistort_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p]),
+    "e3d_reg_undistort": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_reg_undistort_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
     "e3d_pose_from_bearings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_set_cache_observations": (C.c_int, [C.c_void_p, C.c_int]),
     "e3d_reg_determine_observed_indices": (C.c_int, [C.c_void_p]),
@@ -862,6 +877,7 @@ class RegProblem:
         self._nparams = {}
         self._dependent = set()
         self._image_intr = {}
+        self._intr_size = {}
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -902,6 +918,7 @@ class RegProblem:
                                                min_image_scale, n_levels), "e3d_reg_set_intrinsics")
         self._levels[intrinsics_id] = n_levels
         self._nparams[intrinsics_id] = len(p)
+        self._intr_size[intrinsics_id] = (int(height), int(width))
 
     def intrinsics_level(self, intrinsics_id, level):
         w = C.c_int(); h = C.c_int(); p = np.zeros(self._nparams[intrinsics_id], np.float32); c = C.c_float()
@@ -1126,6 +1143,38 @@ class RegProblem:
         self._chk(lib().e3d_reg_project_points(self._h, int(image_id), C.c_void_p(xyz.ctypes.data), len(xyz), C.c_void_p(pixel.ctypes.data),
                                                C.c_void_p(state.ctypes.data)), "e3d_reg_project_points")
         return pixel, state
+
+    # ---- ImageUndistorter ------------------------------------------------------------------------------------------------------------
+    def undistort_plan(self, intrinsics_id, blank_pixels=0.0, max_image_size=-1):
+        """The PINHOLE camera the images of a camera are resampled to (e3d_reg_undistort_plan) -> UndistortPlan."""
+        plan = UndistortPlan()
+        self._chk(lib().e3d_reg_undistort_plan(self._h, int(intrinsics_id), float(blank_pixels), int(max_image_size), C.byref(plan)),
+                  "e3d_reg_undistort_plan")
+        return plan
+
+    def undistort(self, intrinsics_id, plan, kind, src, return_valid=False):
+        """One level-0 image of the camera through the plan.  kind 0: (H, W) uint8 bilinear, 1: (H, W, 3) uint8 bilinear, 2: (H, W) uint8
+        mask (bit-OR), 3: (H, W) float32 nearest (bits copied) -> the (plan.height, plan.width[, 3]) array, and with return_valid the
+        uint8 validity map as well."""
+        kind = int(kind)
+        if kind not in _UNDISTORT_PIXEL:
+            raise E3DError("e3d_reg_undistort: unknown kind %d" % kind)
+        dtype, tail = _UNDISTORT_PIXEL[kind]
+        src = np.ascontiguousarray(src, dtype)
+        size = self._intr_size.get(int(intrinsics_id))
+        if size is not None and src.shape != size + tail:
+            raise E3DError("e3d_reg_undistort: the source is %s, the camera's level 0 %s" % (src.shape, size + tail))
+        out = np.zeros((max(int(plan.height), 0), max(int(plan.width), 0)) + tail, dtype)
+        valid = np.zeros(out.shape[:2], np.uint8) if return_valid else None
+        self._chk(lib().e3d_reg_undistort(self._h, int(intrinsics_id), C.byref(plan), kind, C.c_void_p(src.ctypes.data), C.c_void_p(out.ctypes.data),
+                                          C.c_void_p(valid.ctypes.data) if return_valid else None), "e3d_reg_undistort")
+        return (out, valid) if return_valid else out
+
+    def undistort_kernel_ms(self):
+        """HIP-event time of the resampling kernel of the last undistort()."""
+        ms = C.c_float()
+        self._chk(lib().e3d_reg_undistort_kernel_ms(self._h, C.byref(ms)), "e3d_reg_undistort_kernel_ms")
+        return float(ms.value)
 
     @staticmethod
     def pose_from_bearings(points, bearings, q, t):

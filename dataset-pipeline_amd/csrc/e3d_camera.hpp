@@ -42,6 +42,26 @@ enum : int { kPinhole = 0, kOpenCV = 1, kThinPrismFisheye = 2, kOpenCVFisheye = 
              kRadial = 7, kPolynomial3 = 8, kFisheyePolyTang = 9, kFullOpenCV = 10, kRadialFisheye = 11, kSimpleRadialFisheye = 12,
              kNumCameraModels = 13 };
 
+// run `stmt` with the camera model as the compile-time constant M
+// (host code; the expansion throws e3d::Error of e3d_common.hpp with E3D_ERR_INVALID of e3d_hip.h)
+#define E3D_CAM_SWITCH(model, stmt)                                                        \
+  switch (model) {                                                                         \
+    case kPinhole: { constexpr int M = kPinhole; stmt; } break;                            \
+    case kOpenCV: { constexpr int M = kOpenCV; stmt; } break;                              \
+    case kThinPrismFisheye: { constexpr int M = kThinPrismFisheye; stmt; } break;          \
+    case kOpenCVFisheye: { constexpr int M = kOpenCVFisheye; stmt; } break;                \
+    case kFov: { constexpr int M = kFov; stmt; } break;                                    \
+    case kSimplePinhole: { constexpr int M = kSimplePinhole; stmt; } break;                \
+    case kSimpleRadial: { constexpr int M = kSimpleRadial; stmt; } break;                  \
+    case kRadial: { constexpr int M = kRadial; stmt; } break;                              \
+    case kPolynomial3: { constexpr int M = kPolynomial3; stmt; } break;                    \
+    case kFisheyePolyTang: { constexpr int M = kFisheyePolyTang; stmt; } break;            \
+    case kFullOpenCV: { constexpr int M = kFullOpenCV; stmt; } break;                      \
+    case kRadialFisheye: { constexpr int M = kRadialFisheye; stmt; } break;                \
+    case kSimpleRadialFisheye: { constexpr int M = kSimpleRadialFisheye; stmt; } break;    \
+    default: throw Error(E3D_ERR_INVALID, "unknown camera model");                         \
+  }
+
 __host__ __device__ constexpr int cam_param_count(int model) {
   return model == kPinhole ? 4 : model == kFov ? 5 : (model == kOpenCV || model == kOpenCVFisheye || model == kFisheyePolyTang) ? 8 :
          model == kSimplePinhole ? 3 : (model == kSimpleRadial || model == kSimpleRadialFisheye) ? 4 :

@@ -27,6 +27,7 @@
 #include "e3d_comm.hpp"
 #include "e3d_icp_kernels.hpp"
 #include "e3d_math.hpp"
+#include "e3d_undistort.hpp"
 
 #pragma clang fp contract(off)
 
@@ -2805,6 +2806,12 @@ struct e3d_reg {
   DevBuf<float2> pick_clicks;
   DevBuf<float> localize_in, localize_out;
   DevBuf<unsigned char> localize_state;
+  // ImageUndistorter (e3d_reg_undistort_plan, e3d_reg_undistort): the border samples and their normalized coordinates, the staging of
+  // one source image, its resampled copy and the validity map; HIP-event time of the last resampling kernel
+  DevBuf<float2> undistort_border;
+  DevBuf<unsigned char> undistort_src, undistort_dst, undistort_valid;
+  std::unique_ptr<EventTimer> t_undistort;
+  float undistort_ms = 0.f;
   // scratch
   DevBuf<int> valid;
   DevBuf<float> tx, ty, ts;
@@ -2968,25 +2975,6 @@ static void allreduce_device(e3d_reg* h, void* dev, size_t n, int dtype) {
   rsync(h);
   if (!h->allreduce_dev || h->allreduce_dev(dev, n, dtype, h->ar_user) != 0) throw Error(E3D_ERR_INVALID, "device all-reduce callback failed");
 }
-
-// run `stmt` with the camera model as the compile-time constant M
-#define E3D_CAM_SWITCH(model, stmt)                                                        \
-  switch (model) {                                                                         \
-    case kPinhole: { constexpr int M = kPinhole; stmt; } break;                            \
-    case kOpenCV: { constexpr int M = kOpenCV; stmt; } break;                              \
-    case kThinPrismFisheye: { constexpr int M = kThinPrismFisheye; stmt; } break;          \
-    case kOpenCVFisheye: { constexpr int M = kOpenCVFisheye; stmt; } break;                \
-    case kFov: { constexpr int M = kFov; stmt; } break;                                    \
-    case kSimplePinhole: { constexpr int M = kSimplePinhole; stmt; } break;                \
-    case kSimpleRadial: { constexpr int M = kSimpleRadial; stmt; } break;                  \
-    case kRadial: { constexpr int M = kRadial; stmt; } break;                              \
-    case kPolynomial3: { constexpr int M = kPolynomial3; stmt; } break;                    \
-    case kFisheyePolyTang: { constexpr int M = kFisheyePolyTang; stmt; } break;            \
-    case kFullOpenCV: { constexpr int M = kFullOpenCV; stmt; } break;                      \
-    case kRadialFisheye: { constexpr int M = kRadialFisheye; stmt; } break;                \
-    case kSimpleRadialFisheye: { constexpr int M = kSimpleRadialFisheye; stmt; } break;    \
-    default: throw Error(E3D_ERR_INVALID, "unknown camera model");                         \
-  }
 
 // RadialBase::InitCutoff of the Polynomial4Camera inside OPENCV_FISHEYE (camera_base_impl_radial.h:59-170): the farthest image
 // corner, ten start radii, a 1-D Gauss-Newton each -- a few hundred scalar operations, done on the host in the reference's f32 /
@@ -5088,6 +5076,118 @@ int e3d_reg_project_points(e3d_reg_t* h, int image_id, const float* xyz, size_t 
   copy_out(state_out, h->localize_state.p, n, h->stream);
   rsync(h);
   E3D_HIP(hipGetLastError());
+  return 0;
+  E3D_CATCH()
+}
+
+// ---- ImageUndistorter -----------------------------------------------------------------------------------------------------------------
+static const Intrin& undistort_intrinsics(e3d_reg* h, int intrinsics_id) {
+  auto it = h->intr.find(intrinsics_id);
+  if (it == h->intr.end()) throw Error(E3D_ERR_INDEX, fmt("no intrinsics with id %d (e3d_reg_set_intrinsics)", intrinsics_id));
+  return it->second;
+}
+
+int e3d_reg_undistort_plan(e3d_reg_t* h, int intrinsics_id, double blank_pixels, int max_image_size, e3d_undistort_plan* out) {
+  E3D_TRY_ON(h)
+  if (!h || !out) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!(blank_pixels >= 0.0 && blank_pixels <= 1.0)) throw Error(E3D_ERR_INVALID, fmt("blank_pixels = %g is outside [0, 1]", blank_pixels));
+  const Intrin& in = undistort_intrinsics(h, intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  const int W = cam.width, H = cam.height, n = 2 * W + 2 * H;
+  // border samples: the pixel centres (0, y), (W - 1, y) of every row, then (x, 0), (x, H - 1) of every column
+  std::vector<float2> px((size_t)n);
+  for (int y = 0; y < H; ++y) { px[2 * y] = make_float2(0.f, (float)y); px[2 * y + 1] = make_float2((float)(W - 1), (float)y); }
+  for (int x = 0; x < W; ++x) { px[2 * H + 2 * x] = make_float2((float)x, 0.f); px[2 * H + 2 * x + 1] = make_float2((float)x, (float)(H - 1)); }
+  h->undistort_border.reserve(2 * (size_t)n);
+  copy_in(h->undistort_border.p, px.data(), sizeof(float2) * n, h->stream);
+  E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_image_bearings<M>, dim3(nblk(n)), dim3(kBlock), 0, h->stream, cam, h->undistort_border.p, n,
+                                             h->undistort_border.p + n));
+  std::vector<float2> nxy((size_t)n);
+  copy_out(nxy.data(), h->undistort_border.p + n, sizeof(float2) * n, h->stream);
+  rsync(h);
+  E3D_HIP(hipGetLastError());
+  // per side: inner and outer extent of one coordinate of its samples
+  struct Side { double in, out; int count = 0; };
+  auto extent = [&](int first, int step, int count, bool x_coordinate, bool low_side) {
+    Side s{low_side ? -INFINITY : INFINITY, low_side ? INFINITY : -INFINITY};
+    for (int i = 0; i < count; ++i) {
+      const float2 v = nxy[first + (size_t)step * i];
+      if (!std::isfinite(v.x) || !std::isfinite(v.y)) {
+        if (blank_pixels > 0.0)
+          throw Error(E3D_ERR_INVALID, "a border pixel has no finite undistorted position (beyond the model's radius cut-off): "
+                                       "only blank_pixels = 0 is possible for this camera");
+        continue;
+      }
+      const double c = x_coordinate ? (double)v.x : (double)v.y;
+      if (low_side) { s.in = std::max(s.in, c); s.out = std::min(s.out, c); }
+      else { s.in = std::min(s.in, c); s.out = std::max(s.out, c); }
+      ++s.count;
+    }
+    if (!s.count) throw Error(E3D_ERR_INVALID, "no border pixel of one image side has a finite undistorted position");
+    return s;
+  };
+  const Side L = extent(0, 2, H, true, true), R = extent(1, 2, H, true, false);
+  const Side T = extent(2 * H, 2, W, false, true), B = extent(2 * H + 1, 2, W, false, false);
+  const double b = blank_pixels;
+  const double nL = b * L.out + (1.0 - b) * L.in, nR = b * R.out + (1.0 - b) * R.in;
+  const double nT = b * T.out + (1.0 - b) * T.in, nB = b * B.out + (1.0 - b) * B.in;
+  if (!(nL < nR) || !(nT < nB)) throw Error(E3D_ERR_INVALID, "the undistorted image is empty: its left / top extent is not below its right / bottom one");
+  // a blended bound may lie up to b pixels outside its extent (the outer bounds are rounded outwards): 2 b pixels of margin
+  double s = 1.0;
+  const double extent_px = std::max((double)cam.fx * (nR - nL), (double)cam.fy * (nB - nT)), margin = 1.0 + 2.0 * b;
+  if (max_image_size > 0 && extent_px + margin > (double)max_image_size) {
+    s = ((double)max_image_size - margin) / extent_px;
+    if (!(s > 0.0)) throw Error(E3D_ERR_INVALID, fmt("max_image_size = %d leaves no room for an image", max_image_size));
+  }
+  const float fx = (float)(s * (double)cam.fx), fy = (float)(s * (double)cam.fy);
+  // inner bounds rounded inwards, outer bounds outwards, blended as integers
+  auto low_bound = [&](double f, const Side& e) { return std::ceil(b * std::floor(f * e.out) + (1.0 - b) * std::ceil(f * e.in)); };
+  auto high_bound = [&](double f, const Side& e) { return std::floor(b * std::ceil(f * e.out) + (1.0 - b) * std::floor(f * e.in)); };
+  const double x0 = low_bound((double)fx, L), x1 = high_bound((double)fx, R);
+  const double y0 = low_bound((double)fy, T), y1 = high_bound((double)fy, B);
+  const double Wd = x1 - x0 + 1.0, Hd = y1 - y0 + 1.0;
+  if (!(Wd >= 2.0) || !(Hd >= 2.0)) throw Error(E3D_ERR_INVALID, "the undistorted image would be smaller than 2 x 2 pixels");
+  constexpr double kLimit = 16777216.0;          // integers a float holds exactly (the principal point)
+  if (!(std::fabs(x0) < kLimit && std::fabs(y0) < kLimit && Wd < kLimit && Hd < kLimit))
+    throw Error(E3D_ERR_INVALID, "the undistorted image would be larger than 2^24 pixels a side");
+  out->width = (int32_t)Wd; out->height = (int32_t)Hd;
+  out->fx = fx; out->fy = fy; out->cx = (float)(-x0); out->cy = (float)(-y0);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_undistort(e3d_reg_t* h, int intrinsics_id, const e3d_undistort_plan* plan, int kind, const void* src, void* dst, uint8_t* valid_out) {
+  E3D_TRY_ON(h)
+  if (!h || !plan || !src || !dst) throw Error(E3D_ERR_INVALID, "null argument");
+  if (kind < 0 || kind >= kNumUndistortKinds) throw Error(E3D_ERR_INVALID, "unknown kind (0 = u8, 1 = u8 x 3, 2 = mask, 3 = f32 nearest)");
+  const Intrin& in = undistort_intrinsics(h, intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  if (plan->width < 1 || plan->height < 1 || plan->width > (1 << 24) || plan->height > 65535 * 4 || !(plan->fx > 0.f) || !(plan->fy > 0.f) ||
+      !std::isfinite(plan->fx) || !std::isfinite(plan->fy) || !std::isfinite(plan->cx) || !std::isfinite(plan->cy))
+    throw Error(E3D_ERR_INVALID, "bad plan (e3d_reg_undistort_plan fills it)");
+  const size_t px_bytes = undistort_pixel_bytes(kind);
+  const size_t n_src = (size_t)cam.width * (size_t)cam.height, n_dst = (size_t)plan->width * (size_t)plan->height;
+  h->undistort_src.reserve(n_src * px_bytes); h->undistort_dst.reserve(n_dst * px_bytes);
+  if (valid_out) h->undistort_valid.reserve(n_dst);
+  copy_in(h->undistort_src.p, src, n_src * px_bytes, h->stream);
+  if (!h->t_undistort) h->t_undistort.reset(new EventTimer());
+  const UndistortTarget target{plan->width, plan->height, plan->fx, plan->fy, plan->cx, plan->cy};
+  h->t_undistort->start(h->stream);
+  undistort_launch(cam, target, kind, h->undistort_src.p, h->undistort_dst.p, valid_out ? h->undistort_valid.p : nullptr, h->stream);
+  h->t_undistort->stop(h->stream);
+  copy_out(dst, h->undistort_dst.p, n_dst * px_bytes, h->stream);
+  if (valid_out) copy_out(valid_out, h->undistort_valid.p, n_dst, h->stream);
+  rsync(h);
+  E3D_HIP(hipGetLastError());
+  h->undistort_ms = h->t_undistort->ms();
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_undistort_kernel_ms(e3d_reg_t* h, float* ms) {
+  E3D_TRY_ON(h)
+  if (!h || !ms) throw Error(E3D_ERR_INVALID, "null argument");
+  *ms = h->undistort_ms;
   return 0;
   E3D_CATCH()
 }

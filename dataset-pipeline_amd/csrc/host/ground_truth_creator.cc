@@ -19,26 +19,6 @@
 
 using namespace e3d_host;
 
-static bool write_float_map(const std::string& path, const std::vector<float>& map, bool compress) {
-  if (compress) {
-    gzFile f = gzopen((path + ".gz").c_str(), "w8b");
-    if (!f) return false;
-    const size_t bytes = map.size() * sizeof(float);
-    size_t done = 0;
-    while (done < bytes) {                                   // gzwrite takes an unsigned length
-      const unsigned chunk = (unsigned)std::min<size_t>(bytes - done, 1u << 30);
-      if (gzwrite(f, reinterpret_cast<const char*>(map.data()) + done, chunk) != (int)chunk) { gzclose(f); return false; }
-      done += chunk;
-    }
-    return gzclose(f) == Z_OK;
-  }
-  FILE* f = fopen(path.c_str(), "wb");
-  if (!f) return false;
-  const bool ok = fwrite(map.data(), sizeof(float), map.size(), f) == map.size();
-  fclose(f);
-  return ok;
-}
-
 static int run_tool(int argc, char** argv) {
   std::string scan_alignment_path, occlusion_mesh_path, occlusion_splats_path, image_base_path, state_path, output_folder_path;
   parse_argument(argc, argv, "--scan_alignment_path", scan_alignment_path);

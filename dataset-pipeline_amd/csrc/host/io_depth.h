@@ -1,4 +1,4 @@
-// io_depth.h -- reader of the depth maps GroundTruthCreator writes (ground_truth_creator.cc: write_float_map): width x height raw
+// io_depth.h -- the depth maps GroundTruthCreator writes (write_float_map below) and their reader: width x height raw
 // f32, row-major, no header, optionally gzip-compressed with ".gz" appended to the name, one file per image under
 // <dir>/<camera folder>/<image name>.  zlib's gz* functions read both: a file without the gzip magic is passed through unchanged.
 #pragma once
@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <cstdio>
 #include <string>
 #include <vector>
 
@@ -59,6 +60,27 @@ inline bool read_depth_map(const std::string& dir, const std::string& image_file
   *err = "Depth map " + used + " holds " + std::to_string(got + extra) + (extra >= (64u << 20) ? "+" : "") + " bytes, expected " +
          std::to_string(want) + " (" + std::to_string(width) + " x " + std::to_string(height) + " f32)" + (bad ? ": " + zmsg : std::string());
   return false;
+}
+
+// Writes one map the way read_depth_map finds it: raw f32 under `path`, or gzip-compressed under `path`.gz
+inline bool write_float_map(const std::string& path, const std::vector<float>& map, bool compress) {
+  if (compress) {
+    gzFile f = gzopen((path + ".gz").c_str(), "w8b");
+    if (!f) return false;
+    const size_t bytes = map.size() * sizeof(float);
+    size_t done = 0;
+    while (done < bytes) {                                   // gzwrite takes an unsigned length
+      const unsigned chunk = (unsigned)std::min<size_t>(bytes - done, 1u << 30);
+      if (gzwrite(f, reinterpret_cast<const char*>(map.data()) + done, chunk) != (int)chunk) { gzclose(f); return false; }
+      done += chunk;
+    }
+    return gzclose(f) == Z_OK;
+  }
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  const bool ok = fwrite(map.data(), sizeof(float), map.size(), f) == map.size();
+  fclose(f);
+  return ok;
 }
 
 }  // namespace e3d_host

@@ -1079,10 +1079,12 @@ class Problem {
     return true;
   }
 
-  // io::ExportProblemToColmap(problem, image_base_path, write_points = false, write_images = false, write_project = false, dir)
-  bool ExportToColmap(const std::string& image_base_path, const std::string& dir) const {
+  // io::ExportProblemToColmap(problem, image_base_path, write_points = false, write_images = false, write_project = false, dir);
+  // digits: significant digits of the numbers (the reference's streams keep the default 6; 9 round-trips an f32)
+  bool ExportToColmap(const std::string& image_base_path, const std::string& dir, int digits = 6) const {
     create_directories(dir);
     std::ofstream cf(dir + "/cameras.txt");
+    cf.precision(digits);
     cf << "# Camera list with one line of data per camera:" << std::endl;
     cf << "#   CAMERA_ID, MODEL, WIDTH, HEIGHT, PARAMS[]" << std::endl;
     cf << "# Number of cameras: " << intrinsics_list.size() << std::endl;
@@ -1098,6 +1100,7 @@ class Problem {
       cf << std::endl;
     }
     std::ofstream f(dir + "/images.txt");
+    f.precision(digits);
     f << "# Image list with two lines of data per image:" << std::endl;
     f << "#   IMAGE_ID, QW, QX, QY, QZ, TX, TY, TZ, CAMERA_ID, NAME" << std::endl;
     f << "#   POINTS2D[] as (X, Y, POINT3D_ID)" << std::endl;

@@ -603,6 +603,47 @@ int e3d_reg_image_bearings(e3d_reg_t* reg, int image_id, const float* pixels_xy,
 int e3d_reg_project_points(e3d_reg_t* reg, int image_id, const float* xyz, size_t n, float* pixel_out, uint8_t* state_out);
 int e3d_pose_from_bearings(const double* points, const double* bearings, int n, const float q_in[4], const float t_in[3], float q_out[4],
                            float t_out[3], double stats[4]);
+/* ImageUndistorter: PINHOLE copies of the images, masks and depth maps of a camera of any model.  The reference leaves this step to
+ * COLMAP's undistorter (its README); both rules below are this library's own and restate neither.  They need e3d_reg_set_intrinsics
+ * only: no image, no pose.  Pixel coordinates: (0, 0) is the centre of the top-left pixel, here and in the plan.
+ *   e3d_reg_undistort_plan: the output camera.  The level-0 model (W x H, focal lengths fx, fy; fx = fy = f for the models with one
+ *     focal length) is sampled at its border pixel centres (0, y), (W - 1, y) of every row and (x, 0), (x, H - 1) of every column;
+ *     each goes through the model's ImageToNormalized in f32 on the device, exactly as e3d_reg_image_bearings evaluates it before
+ *     normalising (camera_base_impl.h:188-211).  Per side the inner and the outer extent of the samples: left L_in = max, L_out = min
+ *     of their nx; right R_in = min, R_out = max of nx; top and bottom likewise with ny.  In f64, b = blank_pixels in [0, 1]:
+ *     nL = b * L_out + (1 - b) * L_in, likewise nR, nT, nB.  s = 1, or, if max_image_size > 0 and
+ *     e + 1 + 2 b exceeds it, e = max(fx * (nR - nL), fy * (nB - nT)): s = (max_image_size - 1 - 2 b) / e.  fx' = (float)(s * fx),
+ *     fy' = (float)(s * fy).  Inner bounds are rounded inwards, outer bounds outwards, and the two blended as integers:
+ *     x0 = ceil(b * floor(fx' * L_out) + (1 - b) * ceil(fx' * L_in)), x1 = floor(b * ceil(fx' * R_out) + (1 - b) * floor(fx' * R_in)),
+ *     width = x1 - x0 + 1, cx' = -x0; the same in y.  The principal point is integral: the output lattice is the undistorted lattice
+ *     cropped to a part every pixel of which has data (b = 0) or padded to hold every source pixel centre (b = 1), and without
+ *     max_image_size the focal length is kept; max(width, height) <= max_image_size.  Samples without a finite position (beyond a
+ *     model's radius cut-off) are skipped at b = 0.
+ *     Refused (E3D_ERR_INVALID, the message names the cause): such a sample at b > 0; a side without any finite sample; nL >= nR or
+ *     nT >= nB; width or height < 2 or beyond 2^24; a max_image_size that leaves s <= 0; blank_pixels outside [0, 1]; a null
+ *     handle or output; unknown intrinsics (E3D_ERR_INDEX).
+ *   e3d_reg_undistort: one image through the plan.  For the output pixel (x, y): nx = (float(x) - cx') / fx', ny = (float(y) - cy')
+ *     / fy', (sx, sy) = the level-0 model's NormalizedToImage(nx, ny) (camera_base_impl.h:155-164; +-inf past a cut-off), all f32
+ *     without contraction.  The pixel is valid iff sx and sy are finite, 0 <= sx <= W - 1 and 0 <= sy <= H - 1 -- a closed interval,
+ *     where InterpolateBilinear's test is half open (interpolate_bilinear.h:79-92): the plan's inner extents map to exactly these
+ *     borders.  For a valid pixel ix = min((int)sx, W - 2), iy = min((int)sy, H - 2), ax = sx - ix, ay = sy - iy and by kind
+ *       0 (u8) and 1 (u8 x 3, interleaved R G B, per channel): v = (1 - ay) * ((1 - ax) * p00 + ax * p10) + ay * ((1 - ax) * p01 +
+ *         ax * p11) in f32, InterpolateBilinearNoCheck's order (interpolate_bilinear.h:37-50); the output is (uint8)(int)(v + 0.5f);
+ *       2 (u8 mask): the bit-OR of the four pixels; the values are the flags kObs = 1, kEvalObs = 2 of image.h:43-47, so a masked
+ *         pixel that contributes masks the result;
+ *       3 (f32, nearest): the value at (min((int)(sx + 0.5f), W - 1), min((int)(sy + 0.5f), H - 1)) copied as bits: NaN, +-inf and the
+ *         0 of a hole survive unchanged (depth maps hold z-depth, which is constant along a ray).
+ *     An invalid pixel is 0 (kinds 0, 1, 3) or 3 (kind 2: both flags, there is no data).  src: W x H pixels of the kind, dst:
+ *     width x height pixels of the kind, valid_out (optional): width x height bytes, 1 = valid; host or device memory.  One output
+ *     pixel per thread and no sums: the result equals a serial loop bit for bit.
+ *     Refused: null handle, plan, src or dst; a kind outside 0..3; a plan with a size < 1 or a non-finite or non-positive focal
+ *     length; unknown intrinsics (E3D_ERR_INDEX).
+ *   e3d_reg_undistort_kernel_ms: HIP-event time of the resampling kernel of the last e3d_reg_undistort (tools/bench_undistort.py). */
+typedef struct { int32_t width, height; float fx, fy, cx, cy; } e3d_undistort_plan;   /* a PINHOLE camera, pixel-centre convention */
+int e3d_reg_undistort_plan(e3d_reg_t* reg, int intrinsics_id, double blank_pixels, int max_image_size, e3d_undistort_plan* out);
+int e3d_reg_undistort(e3d_reg_t* reg, int intrinsics_id, const e3d_undistort_plan* plan, int kind, const void* src, void* dst,
+                      uint8_t* valid_out);
+int e3d_reg_undistort_kernel_ms(e3d_reg_t* reg, float* ms);
 /* Observations cache (src/opt/observations_cache.{h,cc}; Optimizer::set_cache_observations, optimizer.h).  When enabled, the
  * observation update re-projects a fixed per-image list of point indices with the current state and applies only the
  * scale-fit and border tests (VisibilityEstimator::AppendObservationsForIndexedPointsVisibleInImage,
