@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-SOURCES = ["e3d_icp.hip", "e3d_comm.hip", "e3d_icp_kernels.hip", "e3d_sort.hip", "e3d_normals.hip", "e3d_reg.hip", "e3d_multires.hip", "e3d_splats.hip", "e3d_cubemap.hip", "e3d_edit.hip", "e3d_surface.hip", "e3d_eval.hip", "e3d_undistort.hip"]
+SOURCES = ["e3d_icp.hip", "e3d_comm.hip", "e3d_icp_kernels.hip", "e3d_sort.hip", "e3d_normals.hip", "e3d_reg.hip", "e3d_reg_depth.hip", "e3d_reg_scan.hip", "e3d_multires.hip", "e3d_splats.hip", "e3d_cubemap.hip", "e3d_edit.hip", "e3d_surface.hip", "e3d_eval.hip", "e3d_undistort.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
@@ -24,8 +24,10 @@ def lib_path():
 # per-file extras.  No SLP vectorisation for the ICP and registration kernels: the compiler otherwise packs adjacent scalar f32
 # operations of their long expression trees into v_pk_*_f32 and spends more on moves than it saves (measured on one MI355X:
 # k_lm_cost_multi 2.00 -> 1.67 ms, k_lm_pass<3> 0.97 -> 0.91 ms, k_reg_pass1 0.503 -> 0.447 ms; tools/micro/lm_variants.hip, DESIGN
-# 4.2).  The kNN kernels of e3d_normals.hip gain from it (1.72 vs 1.34 G normals/s) and keep it.  Rounding is the same either way.
-EXTRA_FLAGS = {"e3d_icp_kernels.hip": ["-fno-slp-vectorize"], "e3d_reg.hip": ["-fno-slp-vectorize"]}
+# 4.2); e3d_reg_depth.hip and e3d_reg_scan.hip were split off e3d_reg.hip and keep the flag their kernels were tuned and tested with.
+# The kNN kernels of e3d_normals.hip gain from it (1.72 vs 1.34 G normals/s) and keep it.  Rounding is the same either way.
+EXTRA_FLAGS = {"e3d_icp_kernels.hip": ["-fno-slp-vectorize"], "e3d_reg.hip": ["-fno-slp-vectorize"],
+               "e3d_reg_depth.hip": ["-fno-slp-vectorize"], "e3d_reg_scan.hip": ["-fno-slp-vectorize"]}
 
 
 def _newer(src, dst):

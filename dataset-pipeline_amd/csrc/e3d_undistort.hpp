@@ -1,4 +1,4 @@
-// e3d_undistort.hpp -- the resampling kernel of e3d_reg_undistort (e3d_undistort.hip) as e3d_reg.hip launches it.
+// e3d_undistort.hpp -- the resampling kernel of e3d_reg_undistort (e3d_undistort.hip) as e3d_reg_scan.hip launches it.
 #pragma once
 
 #include <stdint.h>
