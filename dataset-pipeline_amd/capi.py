@@ -197,6 +197,7 @@ SIGNATURES = {
     "e3d_surface_get_corners": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_surface_get_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_surface_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "e3d_surface_reconstruct_csg": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p, C.c_size_t]),
     # ReconstructionEvaluator: accuracy and completeness of a reconstruction against the scans
     "e3d_evaluate_reconstruction": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int]),
     "e3d_eval_destroy": (None, [C.c_void_p]),
@@ -574,17 +575,45 @@ def create_splats(xyz, normals, vertices, triangles, distance_threshold=0.02, ma
     return out[:m].reshape(-1, 3).copy(), faces, flag.astype(bool), rad
 
 
-def reconstruct_surface(xyz, normals, voxel_size, support_radius=None, return_corners=False, timings=None):
+class SurfaceSolid(C.Structure):
+    """e3d_surface_solid_t"""
+    _fields_ = [("kind", C.c_int32), ("centre", C.c_double * 3), ("rotation", C.c_double * 9), ("half_extent", C.c_double * 3)]
+
+
+SURFACE_SOLID_KINDS = {"union": 0, "subtract": 1}      # E3D_SURFACE_UNION, E3D_SURFACE_SUBTRACT
+
+
+def _surface_solids(solids):
+    ops = (SurfaceSolid * max(len(solids), 1))()
+    for op, (kind, centre, rotation, half_extent) in zip(ops, solids):
+        if isinstance(kind, str):
+            if kind not in SURFACE_SOLID_KINDS:
+                raise E3DError("reconstruct_surface: the kind of a solid is 'union' or 'subtract', not %r" % (kind,))
+            kind = SURFACE_SOLID_KINDS[kind]
+        op.kind = int(kind)                                  # a number goes to the library as it is
+        op.centre[:] = np.asarray(centre, np.float64).reshape(3).tolist()
+        op.rotation[:] = np.asarray(rotation, np.float64).reshape(9).tolist()
+        op.half_extent[:] = np.asarray(half_extent, np.float64).reshape(3).tolist()
+    return ops
+
+
+def reconstruct_surface(xyz, normals, voxel_size, support_radius=None, return_corners=False, timings=None, solids=None):
     """SurfaceReconstructor (include/e3d_hip.h, e3d_surface_reconstruct) -> (vertices[v, 3] f32, triangles[t, 3] uint32), and with
     return_corners a dict of the defined corners in ascending (k, j, i): ijk[c, 3] int32, f[c], weight[c] f64, count[c] int32, plus
     the vertices' cells cell_ijk[v, 3] int32.  support_radius defaults to 2 x voxel_size (in f32).  timings: a dict that receives the
-    HIP-event time of every kernel group as <group>_ms."""
+    HIP-event time of every kernel group as <group>_ms.  solids: a list of (kind, centre[3], rotation[3, 3], half_extent[3]) with kind
+    "union" or "subtract", applied in order to the scan field (e3d_surface_reconstruct_csg); None calls e3d_surface_reconstruct."""
     keep = []
     n = int(xyz.shape[0])
     h = np.float32(voxel_size)
     r = np.float32(2) * h if support_radius is None else np.float32(support_radius)
-    handle = lib().e3d_surface_reconstruct(_ptr(xyz, np.float32, keep) if n else None, _ptr(normals, np.float32, keep) if n else None, n,
-                                           float(h), float(r))
+    px, pn = (_ptr(xyz, np.float32, keep), _ptr(normals, np.float32, keep)) if n else (None, None)
+    if solids is None:
+        handle = lib().e3d_surface_reconstruct(px, pn, n, float(h), float(r))
+    else:
+        solids = list(solids)
+        ops = _surface_solids(solids)
+        handle = lib().e3d_surface_reconstruct_csg(px, pn, n, float(h), float(r), C.cast(ops, C.c_void_p), len(solids))
     if not handle:
         _err("e3d_surface_reconstruct")
     try:

@@ -12,12 +12,16 @@
 //              looked up 64 at a time (one per lane); each non-empty cell's run of points is staged through LDS as f64, 64 points per
 //              step, and every lane adds the staged points that count for its corner.  A corner's sums live in one lane and are
 //              formed in grid order: no atomics, and the launch order cannot show
+//  solids      (e3d_surface_reconstruct_csg only) oriented boxes united with or subtracted from the field before the corners are
+//              compacted: k_surf_solid_brick_keys adds the bricks of every union box's band to the candidates, k_surf_apply_solids
+//              applies the operation list per candidate corner and writes the defined flag
 //  corners     the defined corners compacted and sorted by (k, j, i)
 //  extract     crossing flags per (corner, axis) from a brick lookup, stable compaction to the edge list (= quad order); the four
 //              cells of every edge sorted + unique = the vertices in (k, j, i); vertex positions and triangles
 #include <algorithm>
 #include <climits>
 #include <cmath>
+#include <memory>
 #include <vector>
 
 #include "../../include/e3d_hip.h"
@@ -30,8 +34,10 @@ namespace e3d {
 constexpr int kSurfBlock = 256;
 constexpr int kSurfOrgMargin = 16;                 // lattice units kept free below the lowest occupied voxel: dilation (<= 9) + a cell
 constexpr int kSurfGridBias = 1 << 20;             // grid-cell coordinates are in [-2^20, 2^20): cell >= h and |p| / h < 2^20
-constexpr int kSurfGroups = 5;
-static const char* const kSurfGroupNames[kSurfGroups] = {"grid", "candidates", "field", "corners", "extract"};
+constexpr int kSurfGroups = 5;                     // of a call without solids; with solids one more, "solids", last
+constexpr int kSurfMaxGroups = 6;
+static const char* const kSurfGroupNames[kSurfMaxGroups] = {"grid", "candidates", "field", "corners", "extract", "solids"};
+constexpr int kSurfMaxOps = 256;
 
 struct SurfParams {
   double h, R, R2;
@@ -208,11 +214,90 @@ __global__ __launch_bounds__(64) void k_surf_field(const unsigned long long* __r
   count_out[o] = cnt;
 }
 
-// keys (k, j, i) of the defined corners and their slots, flagged for compaction
+// The function of an oriented box at x: negative inside, 0 on its surface, 1-Lipschitz (the rules: include/e3d_hip.h).  An operation
+// is 16 doubles on the device (128 B): o[0] kind, o[1..3] centre, o[4..12] rotation (row-major), o[13..15] half extents.
+__device__ __forceinline__ double surf_box_g(const double* o, double x, double y, double z) {
+  const double d0 = x - o[1], d1 = y - o[2], d2 = z - o[3];
+  const double q0 = fabs((o[4] * d0 + o[7] * d1) + o[10] * d2) - o[13];
+  const double q1 = fabs((o[5] * d0 + o[8] * d1) + o[11] * d2) - o[14];
+  const double q2 = fabs((o[6] * d0 + o[9] * d1) + o[12] * d2) - o[15];
+  const double m = q0 >= q1 ? q0 : q1;                               // max: the first argument on equality
+  return m >= q2 ? m : q2;
+}
+
+// The lattice box of a union solid's band |g| <= 2 h in bricks relative to org, and where its bricks start in the one list of all
+// union solids' bricks.
+struct SurfSolidBox {
+  unsigned long long first;
+  int b0[3], nb[3];
+  int op;
+  int pad;
+};
+
+// Candidates of the union solids: one thread per brick of every band's lattice box.  A brick is kept iff |g(brick centre)| <= thr =
+// 2 h + 1.5 sqrt(3) h (1 + 1e-6): g is 1-Lipschitz and no corner of a brick is farther than 1.5 sqrt(3) h from its centre, so every
+// corner with |g| <= 2 h lies in a kept brick.  out == nullptr: write the flags; otherwise scatter the kept bricks' keys.
+__global__ __launch_bounds__(kSurfBlock) void k_surf_solid_brick_keys(const SurfSolidBox* __restrict__ boxes, int n_boxes, const double* __restrict__ ops,
+                                                                      size_t n_total, SurfParams P, double thr, unsigned char* __restrict__ flags,
+                                                                      const unsigned* __restrict__ offsets, unsigned long long* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= n_total) return;
+  if (out && !flags[t]) return;
+  int lo = 0, hi = n_boxes - 1;                                       // the last box that starts at or before t
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (boxes[mid].first <= t) lo = mid; else hi = mid - 1;
+  }
+  const SurfSolidBox B = boxes[lo];
+  const size_t r = t - B.first;
+  const int b[3] = {B.b0[0] + (int)(r % (size_t)B.nb[0]), B.b0[1] + (int)((r / (size_t)B.nb[0]) % (size_t)B.nb[1]),
+                    B.b0[2] + (int)(r / ((size_t)B.nb[0] * (size_t)B.nb[1]))};
+  if (out) { out[offsets[t]] = cell_key(b[0], b[1], b[2]); return; }
+  const double x = P.h * ((double)(P.org[0] + 4 * b[0]) + 1.5), y = P.h * ((double)(P.org[1] + 4 * b[1]) + 1.5),
+               z = P.h * ((double)(P.org[2] + 4 * b[2]) + 1.5);
+  flags[t] = fabs(surf_box_g(ops + 16 * (size_t)B.op, x, y, z)) <= thr ? 1 : 0;
+}
+
+// The operation list applied to every candidate corner, in order: one lane per corner, the list staged once per block in LDS (16
+// doubles per operation; every lane reads the same entry, a broadcast).  f and the defined flag of a corner depend on that corner
+// alone: no atomics, no dependence on the launch order.
+__global__ __launch_bounds__(kSurfBlock) void k_surf_apply_solids(const unsigned long long* __restrict__ bricks, size_t n_slots, const double* __restrict__ ops,
+                                                                  int n_ops, SurfParams P, const int* __restrict__ count, double* __restrict__ f,
+                                                                  unsigned char* __restrict__ defined) {
+  extern __shared__ double surf_ops[];
+  for (int t = threadIdx.x; t < 16 * n_ops; t += kSurfBlock) surf_ops[t] = ops[t];
+  __syncthreads();
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_slots) return;
+  const unsigned long long bk = bricks[j >> 6];
+  const int l = (int)(j & 63);
+  const double x = P.h * (double)(P.org[0] + 4 * (int)(bk & 0x1FFFFF) + (l & 3));
+  const double y = P.h * (double)(P.org[1] + 4 * (int)((bk >> 21) & 0x1FFFFF) + ((l >> 2) & 3));
+  const double z = P.h * (double)(P.org[2] + 4 * (int)((bk >> 42) & 0x1FFFFF) + (l >> 4));
+  const double band = 2.0 * P.h;
+  bool def = count[j] > 0;
+  double v = f[j];
+  for (int o = 0; o < n_ops; ++o) {
+    const double* op = surf_ops + 16 * o;
+    const double g = surf_box_g(op, x, y, z);
+    if (op[0] == (double)E3D_SURFACE_UNION) {
+      if (def) v = g < v ? g : v;                                      // min: the first argument on equality
+      else if (fabs(g) <= band) { def = true; v = g; }
+    } else if (def) {
+      const double ng = -g;
+      v = ng > v ? ng : v;                                             // max
+    }
+  }
+  f[j] = v;
+  defined[j] = def ? 1 : 0;
+}
+
+// which candidate corners are defined: without solids those where a point counts
 __global__ __launch_bounds__(kSurfBlock) void k_surf_corner_flags(const int* __restrict__ count, size_t n_slots, unsigned char* __restrict__ flags) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j < n_slots) flags[j] = count[j] > 0 ? 1 : 0;
 }
+// keys (k, j, i) of the defined corners and their slots
 __global__ __launch_bounds__(kSurfBlock) void k_surf_corner_keys(const unsigned long long* __restrict__ bricks, const unsigned char* __restrict__ flags,
                                                                  const unsigned* __restrict__ offsets, size_t n_slots, unsigned long long* __restrict__ keys,
                                                                  unsigned* __restrict__ slots) {
@@ -244,13 +329,14 @@ __device__ __forceinline__ long long surf_corner_slot(const unsigned long long* 
 struct SurfField {
   const unsigned long long* bricks; size_t n_bricks;
   const double* f; const int* count;
+  const unsigned char* defined;                    // per slot: with solids a corner can be defined where no point counts
 };
 // does the edge from corner a (defined, field fa) along axis d cross; its parameter t
 __device__ __forceinline__ bool surf_edge(const SurfField& F, int i, int j, int k, int d, double& t, bool& a_negative) {
   const long long sa = surf_corner_slot(F.bricks, F.n_bricks, i, j, k);
-  if (sa < 0 || F.count[sa] <= 0) return false;
+  if (sa < 0 || !F.defined[sa]) return false;
   const long long sb = surf_corner_slot(F.bricks, F.n_bricks, i + (d == 0), j + (d == 1), k + (d == 2));
-  if (sb < 0 || F.count[sb] <= 0) return false;
+  if (sb < 0 || !F.defined[sb]) return false;
   const double fa = F.f[sa], fb = F.f[sb];
   a_negative = fa < 0.0;
   if (a_negative == (fb < 0.0)) return false;
@@ -360,7 +446,8 @@ struct e3d_surface {
   std::vector<double> corner_f, corner_w;
   std::vector<float> vertices;
   std::vector<uint32_t> triangles;
-  float ms[kSurfGroups] = {0, 0, 0, 0, 0};
+  float ms[kSurfMaxGroups] = {0, 0, 0, 0, 0, 0};
+  int groups = kSurfGroups;
 };
 
 namespace {
@@ -373,7 +460,8 @@ struct SurfRun {
   ~SurfRun() { if (s) (void)hipStreamDestroy(s); }
 
   // exclusive offsets of n flags; the number set
-  size_t scan(size_t n) { return compaction_offsets(flags.p, n, offsets, temp, s); }
+  size_t scan(const unsigned char* f, size_t n) { return compaction_offsets(f, n, offsets, temp, s); }
+  size_t scan(size_t n) { return scan(flags.p, n); }
   // sorts keys[0, n) (into `sorted`) and leaves their unique values in `out`; the number of unique keys
   size_t sort_unique(DevBuf<unsigned long long>& keys, DevBuf<unsigned long long>& sorted, DevBuf<unsigned long long>& out, size_t n, int end_bit) {
     if (n == 0) return 0;
@@ -389,16 +477,70 @@ struct SurfRun {
   }
 };
 
-void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius) {
+// The operation list checked on the host: the operations as the kernels read them (16 doubles each: kind, centre, rotation, half
+// extents) and the lattice bounding box of every solid's band |g| <= 2 h (corner coordinates, one step of margin each side).
+struct SurfSolids {
+  std::vector<double> ops;
+  std::vector<int> lo, hi;                          // 3 per solid
+  bool any_union = false;
+  size_t size() const { return ops.size() / 16; }
+};
+
+void check_solids(SurfSolids& S, const e3d_surface_solid_t* ops, size_t n_ops, double h) {
+  if (n_ops > (size_t)kSurfMaxOps) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: %zu operations, at most %d", n_ops, kSurfMaxOps));
+  if (n_ops && !ops) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct_csg: null argument");
+  for (size_t o = 0; o < n_ops; ++o) {
+    const e3d_surface_solid_t& B = ops[o];
+    if (B.kind != E3D_SURFACE_UNION && B.kind != E3D_SURFACE_SUBTRACT)
+      throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: operation %zu has the unknown kind %d", o, (int)B.kind));
+    bool finite = true;
+    for (int a = 0; a < 3; ++a) finite = finite && std::isfinite(B.centre[a]) && std::isfinite(B.half_extent[a]);
+    for (int a = 0; a < 9; ++a) finite = finite && std::isfinite(B.rotation[a]);
+    if (!finite) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: operation %zu has a centre, rotation or extent that is not finite", o));
+    for (int a = 0; a < 3; ++a)
+      if (!(B.half_extent[a] > 0.0)) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: operation %zu has a half extent <= 0", o));
+    const double* Q = B.rotation;
+    double dev = 0.0;
+    for (int a = 0; a < 3; ++a)
+      for (int b = 0; b < 3; ++b) {
+        const double dot = (Q[a] * Q[b] + Q[3 + a] * Q[3 + b]) + Q[6 + a] * Q[6 + b];
+        dev = std::max(dev, std::fabs(dot - (a == b ? 1.0 : 0.0)));
+      }
+    const double det = Q[0] * (Q[4] * Q[8] - Q[5] * Q[7]) - Q[1] * (Q[3] * Q[8] - Q[5] * Q[6]) + Q[2] * (Q[3] * Q[7] - Q[4] * Q[6]);
+    if (dev > 1e-9 || det < 0.0)
+      throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: the rotation of operation %zu is not a proper rotation (max |Q^T Q - I| = %g, det = %g)", o, dev, det));
+    // the band lies in the box's world bounding box grown by 2 h: |d_r| <= sum_m |Q[r][m]| (a_m + 2 h)
+    for (int r = 0; r < 3; ++r) {
+      double e = 0.0;
+      for (int m = 0; m < 3; ++m) e += std::fabs(Q[3 * r + m]) * (B.half_extent[m] + 2.0 * h);
+      if (!((std::fabs(B.centre[r]) + e) / h + 2.0 < 1048576.0))
+        throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: the band of operation %zu reaches |coordinate| / voxel size >= 2^20", o));
+      S.lo.push_back((int)std::floor((B.centre[r] - e) / h) - 1);
+      S.hi.push_back((int)std::ceil((B.centre[r] + e) / h) + 1);
+    }
+    S.ops.push_back((double)B.kind);
+    S.ops.insert(S.ops.end(), B.centre, B.centre + 3);
+    S.ops.insert(S.ops.end(), B.rotation, B.rotation + 9);
+    S.ops.insert(S.ops.end(), B.half_extent, B.half_extent + 3);
+    S.any_union = S.any_union || B.kind == E3D_SURFACE_UNION;
+  }
+}
+
+void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius,
+                 const e3d_surface_solid_t* ops, size_t n_ops) {
   const double h = (double)voxel_size, R = (double)support_radius;
   if (!std::isfinite(h) || !(h > 0.0)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the voxel size must be positive and finite");
   if (!std::isfinite(R) || !(R > 0.0)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the support radius must be positive and finite");
   if (R / h > 8.0) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct: support radius / voxel size = %g, at most 8", R / h));
   if (n && (!xyz || !normals)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: null argument");
   if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: more than 2^31-1 points");
+  SurfSolids solids;
+  check_solids(solids, ops, n_ops, h);
+  if (n_ops) out.groups = kSurfMaxGroups;
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-  if (n == 0) return;
+  // without a union nothing can be defined where no point counts: subtracting from nothing gives nothing
+  if (n == 0 && !solids.any_union) return;
 
   SurfRun run;
   E3D_HIP(hipStreamCreateWithFlags(&run.s, hipStreamNonBlocking));
@@ -410,71 +552,134 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   // ---- grid ----------------------------------------------------------------------------------------------------------------------
   DevBuf<float> d_xyz, d_nrm;
   DevBuf<int> box;
-  d_xyz.reserve(3 * n); d_nrm.reserve(3 * n); box.reserve(8);
-  copy_in(d_xyz.p, xyz, sizeof(float) * 3 * n, s);
-  copy_in(d_nrm.p, normals, sizeof(float) * 3 * n, s);
-  const int box0[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
-  int hb[8];
-  E3D_HIP(hipMemcpyAsync(box.p, box0, sizeof box0, hipMemcpyHostToDevice, s));
-  timer[0].start(s);
-  hipLaunchKernelGGL(k_surf_classify, dim3((unsigned)std::min<size_t>(div_up(n, kSurfBlock), kSurfClassifyBlocks)), dim3(kSurfBlock), 0, s, d_xyz.p, d_nrm.p, n, h, box.p);
-  copy_out(hb, box.p, sizeof hb, s);
-  E3D_HIP(hipStreamSynchronize(s));
-  E3D_HIP(hipGetLastError());
-  if (hb[6]) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: a point lies at |coordinate| / voxel size >= 2^20");
+  int hb[8] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN, 0, 0};
+  if (n) {
+    d_xyz.reserve(3 * n); d_nrm.reserve(3 * n); box.reserve(8);
+    copy_in(d_xyz.p, xyz, sizeof(float) * 3 * n, s);
+    copy_in(d_nrm.p, normals, sizeof(float) * 3 * n, s);
+    E3D_HIP(hipMemcpyAsync(box.p, hb, sizeof hb, hipMemcpyHostToDevice, s));
+  }
+  timer[0].start(s);                                                   // behind the copies of the cloud
+  if (n) {
+    hipLaunchKernelGGL(k_surf_classify, dim3((unsigned)std::min<size_t>(div_up(n, kSurfBlock), kSurfClassifyBlocks)), dim3(kSurfBlock), 0, s, d_xyz.p, d_nrm.p, n, h, box.p);
+    copy_out(hb, box.p, sizeof hb, s);
+    E3D_HIP(hipStreamSynchronize(s));
+    E3D_HIP(hipGetLastError());
+    if (hb[6]) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: a point lies at |coordinate| / voxel size >= 2^20");
+  }
   const size_t m = (size_t)hb[7];
-  if (m == 0) return;
+  if (m == 0 && !solids.any_union) return;
 
   SurfParams P{};
   P.h = h; P.R = R; P.R2 = R * R;
   P.cell = std::max(R, h) * (1.0 + 1e-6);
   P.pad = 1e-6 * P.cell;
   P.D = (int)std::ceil(R / h);
+  // the occupied voxels and the bands of the solids together
+  int lo[3], hi[3];
+  for (int a = 0; a < 3; ++a) {
+    lo[a] = m ? hb[a] : INT_MAX; hi[a] = m ? hb[3 + a] : INT_MIN;
+    for (size_t o = 0; o < solids.size(); ++o) { lo[a] = std::min(lo[a], solids.lo[3 * o + a]); hi[a] = std::max(hi[a], solids.hi[3 * o + a]); }
+  }
   unsigned ext[3];
   for (int a = 0; a < 3; ++a) {
-    P.org[a] = (int)(std::floor((double)(hb[a] - kSurfOrgMargin) / 4.0) * 4.0);
-    ext[a] = (unsigned)(hb[3 + a] - P.org[a] + kSurfOrgMargin);
-    if (ext[a] >= (1u << 21)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the cloud spans more than 2^21 - 36 voxels along an axis");
+    P.org[a] = (int)(std::floor((double)(lo[a] - kSurfOrgMargin) / 4.0) * 4.0);
+    ext[a] = (unsigned)(hi[a] - P.org[a] + kSurfOrgMargin);
+    if (ext[a] >= (1u << 21))
+      throw Error(E3D_ERR_INVALID, n_ops ? "e3d_surface_reconstruct: the cloud and the solids span more than 2^21 - 36 voxels along an axis"
+                                         : "e3d_surface_reconstruct: the cloud spans more than 2^21 - 36 voxels along an axis");
   }
   const int key_bits = 42 + bits_for(ext[2]);
 
   DevBuf<unsigned long long> ka, kb, vk;
   DevBuf<unsigned> va, vb, counter;
-  ka.reserve(n); kb.reserve(n); vk.reserve(n); va.reserve(n); vb.reserve(n); counter.reserve(2);
-  hipLaunchKernelGGL(k_surf_point_keys, blocks(n), dim3(kSurfBlock), 0, s, d_xyz.p, d_nrm.p, n, P, ka.p, va.p, vk.p);
-  sort_pairs_u64_u32(ka.p, kb.p, va.p, vb.p, n, 64, run.temp, s);
   DevBuf<float4> P4, N4;
-  P4.reserve(m); N4.reserve(m);
-  launch_permute(d_xyz.p, d_nrm.p, vb.p, m, P4.p, N4.p, s);
-  E3D_HIP(hipMemsetAsync(counter.p, 0, 2 * sizeof(unsigned), s));
-  launch_count_cells(kb.p, m, counter.p, s);
   unsigned n_grid_cells = 0;
-  copy_out(&n_grid_cells, counter.p, sizeof(unsigned), s);
-  E3D_HIP(hipStreamSynchronize(s));
+  P4.reserve(m); N4.reserve(m);
+  if (m) {
+    ka.reserve(n); kb.reserve(n); vk.reserve(n); va.reserve(n); vb.reserve(n); counter.reserve(2);
+    hipLaunchKernelGGL(k_surf_point_keys, blocks(n), dim3(kSurfBlock), 0, s, d_xyz.p, d_nrm.p, n, P, ka.p, va.p, vk.p);
+    sort_pairs_u64_u32(ka.p, kb.p, va.p, vb.p, n, 64, run.temp, s);
+    launch_permute(d_xyz.p, d_nrm.p, vb.p, m, P4.p, N4.p, s);
+    E3D_HIP(hipMemsetAsync(counter.p, 0, 2 * sizeof(unsigned), s));
+    launch_count_cells(kb.p, m, counter.p, s);
+    copy_out(&n_grid_cells, counter.p, sizeof(unsigned), s);
+    E3D_HIP(hipStreamSynchronize(s));
+  }
   size_t tsize = 64;
   while (tsize < 2 * (size_t)n_grid_cells) tsize <<= 1;
   DevBuf<HashEntry> table;
   table.reserve(tsize);
   P.mask = (unsigned)(tsize - 1);
   E3D_HIP(hipMemsetAsync(table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-  launch_build_table(kb.p, m, table.p, P.mask, s);
+  if (m) launch_build_table(kb.p, m, table.p, P.mask, s);
   timer[0].stop(s);
 
-  // ---- candidates: occupied voxels -> bricks ---------------------------------------------------------------------------------------
+  // ---- solids: the bricks of the union solids' bands ---------------------------------------------------------------------------------
+  std::unique_ptr<EventTimer> solid_timer[2];
+  DevBuf<double> d_ops;
+  DevBuf<SurfSolidBox> d_boxes;
+  DevBuf<unsigned long long> solid_keys;
+  size_t n_solid_keys = 0;
+  if (n_ops) {
+    solid_timer[0].reset(new EventTimer); solid_timer[1].reset(new EventTimer);
+    d_ops.reserve(solids.ops.size());
+    copy_in(d_ops.p, solids.ops.data(), sizeof(double) * solids.ops.size(), s);
+    std::vector<SurfSolidBox> boxes;
+    size_t total = 0;
+    for (size_t o = 0; o < solids.size(); ++o) {
+      if (solids.ops[16 * o] != (double)E3D_SURFACE_UNION) continue;
+      SurfSolidBox B{};
+      B.first = total; B.op = (int)o;
+      size_t count = 1;
+      for (int a = 0; a < 3; ++a) {
+        B.b0[a] = (solids.lo[3 * o + a] - P.org[a]) >> 2;
+        B.nb[a] = ((solids.hi[3 * o + a] - P.org[a]) >> 2) - B.b0[a] + 1;
+        count *= (size_t)B.nb[a];                                        // at most 2^19 per axis
+      }
+      total += count;
+      if (total > kMaxItems) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: the solids up to operation %zu cover too many bricks for one call", o));
+      boxes.push_back(B);
+    }
+    solid_timer[0]->start(s);
+    if (total) {
+      d_boxes.reserve(boxes.size());
+      copy_in(d_boxes.p, boxes.data(), sizeof(SurfSolidBox) * boxes.size(), s);
+      const double thr = 2.0 * h + 1.5 * std::sqrt(3.0) * h * (1.0 + 1e-6);
+      run.flags.reserve(total);
+      hipLaunchKernelGGL(k_surf_solid_brick_keys, blocks(total), dim3(kSurfBlock), 0, s, d_boxes.p, (int)boxes.size(), d_ops.p, total, P, thr, run.flags.p,
+                         (const unsigned*)nullptr, (unsigned long long*)nullptr);
+      n_solid_keys = run.scan(total);
+      solid_keys.reserve(n_solid_keys);
+      if (n_solid_keys)
+        hipLaunchKernelGGL(k_surf_solid_brick_keys, blocks(total), dim3(kSurfBlock), 0, s, d_boxes.p, (int)boxes.size(), d_ops.p, total, P, thr, run.flags.p,
+                           run.offsets.p, solid_keys.p);
+    }
+    solid_timer[0]->stop(s);
+    E3D_HIP(hipStreamSynchronize(s));                                    // `boxes` is read by the copy above
+  }
+
+  // ---- candidates: occupied voxels -> bricks, with the solids' bricks --------------------------------------------------------------
   timer[1].start(s);
   DevBuf<unsigned long long> voxels, bricks;
-  // (the sort moves the keys of the points that do not contribute, kEmptyKey, behind the m others only with all 64 bits)
-  const size_t n_sorted_voxels = run.sort_unique(vk, ka, voxels, n, 64);
-  const size_t n_voxels = n_sorted_voxels - (m < n ? 1 : 0);          // kEmptyKey is the last unique key if any point was dropped
+  size_t n_voxels = 0;
+  if (m) {
+    // (the sort moves the keys of the points that do not contribute, kEmptyKey, behind the m others only with all 64 bits)
+    const size_t n_sorted_voxels = run.sort_unique(vk, ka, voxels, n, 64);
+    n_voxels = n_sorted_voxels - (m < n ? 1 : 0);                      // kEmptyKey is the last unique key if any point was dropped
+  }
   const int M = ((2 * P.D + 4) >> 2) + 1;
   const size_t n_brick_keys = n_voxels * (size_t)M * M * M;
   if (n_brick_keys > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many occupied voxels for one call");
-  kb.reserve(n_brick_keys);
-  hipLaunchKernelGGL(k_surf_brick_keys, blocks(n_brick_keys), dim3(kSurfBlock), 0, s, voxels.p, n_voxels, P.D, M, kb.p);
-  const size_t n_bricks = run.sort_unique(kb, ka, bricks, n_brick_keys, key_bits);
+  if (n_brick_keys + n_solid_keys > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct_csg: too many candidate bricks of the cloud and the solids for one call");
+  kb.reserve(n_brick_keys + n_solid_keys);
+  if (n_brick_keys) hipLaunchKernelGGL(k_surf_brick_keys, blocks(n_brick_keys), dim3(kSurfBlock), 0, s, voxels.p, n_voxels, P.D, M, kb.p);
+  if (n_solid_keys) E3D_HIP(hipMemcpyAsync(kb.p + n_brick_keys, solid_keys.p, sizeof(unsigned long long) * n_solid_keys, hipMemcpyDeviceToDevice, s));
+  const size_t n_bricks = run.sort_unique(kb, ka, bricks, n_brick_keys + n_solid_keys, key_bits);
   timer[1].stop(s);
   const size_t n_slots = n_bricks * 64;
   if (n_slots > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many candidate corners for one call");
+  if (n_bricks == 0) { E3D_HIP(hipStreamSynchronize(s)); return; }
 
   // ---- field -------------------------------------------------------------------------------------------------------------------------
   DevBuf<double> f, w;
@@ -485,21 +690,31 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   timer[2].stop(s);
   E3D_HIP(hipGetLastError());
 
+  // ---- solids: the operation list at every candidate corner ---------------------------------------------------------------------------
+  DevBuf<unsigned char> defined;
+  defined.reserve(n_slots);
+  if (n_ops) {
+    solid_timer[1]->start(s);
+    hipLaunchKernelGGL(k_surf_apply_solids, blocks(n_slots), dim3(kSurfBlock), sizeof(double) * 16 * n_ops, s, bricks.p, n_slots, d_ops.p, (int)n_ops, P, count.p,
+                       f.p, defined.p);
+    solid_timer[1]->stop(s);
+    E3D_HIP(hipGetLastError());
+  }
+
   // ---- corners: the defined ones in (k, j, i) ------------------------------------------------------------------------------------------
   timer[3].start(s);
-  run.flags.reserve(n_slots);
-  hipLaunchKernelGGL(k_surf_corner_flags, blocks(n_slots), dim3(kSurfBlock), 0, s, count.p, n_slots, run.flags.p);
-  const size_t n_corners = run.scan(n_slots);
+  if (!n_ops) hipLaunchKernelGGL(k_surf_corner_flags, blocks(n_slots), dim3(kSurfBlock), 0, s, count.p, n_slots, defined.p);
+  const size_t n_corners = run.scan(defined.p, n_slots);
   if (3 * n_corners > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many corners for one call");
   DevBuf<unsigned long long> ck;
   DevBuf<unsigned> cs;
   DevBuf<int> o_ijk, o_count;
   DevBuf<double> o_f, o_w;
   DevBuf<unsigned char> cross;
-  const SurfField F{bricks.p, n_bricks, f.p, count.p};
+  const SurfField F{bricks.p, n_bricks, f.p, count.p, defined.p};
   if (n_corners) {
     ka.reserve(n_corners); ck.reserve(n_corners); va.reserve(n_corners); cs.reserve(n_corners);
-    hipLaunchKernelGGL(k_surf_corner_keys, blocks(n_slots), dim3(kSurfBlock), 0, s, bricks.p, run.flags.p, run.offsets.p, n_slots, ka.p, va.p);
+    hipLaunchKernelGGL(k_surf_corner_keys, blocks(n_slots), dim3(kSurfBlock), 0, s, bricks.p, defined.p, run.offsets.p, n_slots, ka.p, va.p);
     sort_pairs_u64_u32(ka.p, ck.p, va.p, cs.p, n_corners, key_bits, run.temp, s);
     o_ijk.reserve(3 * n_corners); o_count.reserve(n_corners); o_f.reserve(n_corners); o_w.reserve(n_corners); cross.reserve(3 * n_corners);
     hipLaunchKernelGGL(k_surf_corner_out, blocks(n_corners), dim3(kSurfBlock), 0, s, ck.p, cs.p, n_corners, P, F, w.p, o_ijk.p, o_f.p, o_w.p, o_count.p,
@@ -540,10 +755,11 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   E3D_HIP(hipStreamSynchronize(s));
   E3D_HIP(hipGetLastError());
   for (int g = 0; g < kSurfGroups; ++g) out.ms[g] = timer[g].ms();
+  if (n_ops) out.ms[kSurfGroups] = solid_timer[0]->ms() + solid_timer[1]->ms();
   static const bool trace = env_default_off("E3D_SURFACE_TRACE");
   if (trace)
-    fprintf(stderr, "[surface] %zu points, %zu contribute, %zu voxels, %zu bricks (%zu candidate corners), %zu grid cells, %zu corners, %zu crossing edges, %zu vertices\n",
-            n, m, n_voxels, n_bricks, n_slots, (size_t)n_grid_cells, n_corners, n_edges, n_cells);
+    fprintf(stderr, "[surface] %zu points, %zu contribute, %zu voxels, %zu bricks (%zu candidate corners), %zu grid cells, %zu corners, %zu crossing edges, %zu vertices, %zu operations, %zu bricks of solids\n",
+            n, m, n_voxels, n_bricks, n_slots, (size_t)n_grid_cells, n_corners, n_edges, n_cells, n_ops, n_solid_keys);
 }
 
 }  // namespace
@@ -554,7 +770,21 @@ e3d_surface_t* e3d_surface_reconstruct(const float* xyz, const float* normals, s
   e3d_surface* h = nullptr;
   try {
     h = new e3d_surface;
-    reconstruct(*h, xyz, normals, n, voxel_size, support_radius);
+    reconstruct(*h, xyz, normals, n, voxel_size, support_radius, nullptr, 0);
+    return h;
+  } catch (const std::exception& e) {
+    e3d::set_last_error(e.what());
+    delete h;
+    return nullptr;
+  }
+}
+
+e3d_surface_t* e3d_surface_reconstruct_csg(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius,
+                                           const e3d_surface_solid_t* ops, size_t n_ops) {
+  e3d_surface* h = nullptr;
+  try {
+    h = new e3d_surface;
+    reconstruct(*h, xyz, normals, n, voxel_size, support_radius, ops, n_ops);
     return h;
   } catch (const std::exception& e) {
     e3d::set_last_error(e.what());
@@ -601,11 +831,11 @@ int e3d_surface_get_mesh(e3d_surface_t* h, float* vertices, int32_t* cell_ijk, u
 int e3d_surface_kernel_ms(e3d_surface_t* h, float* ms, const char** names, int capacity) {
   E3D_TRY
   if (!h) throw Error(E3D_ERR_INVALID, "e3d_surface_kernel_ms: null handle");
-  for (int g = 0; g < kSurfGroups && g < capacity; ++g) {
+  for (int g = 0; g < h->groups && g < capacity; ++g) {
     if (ms) ms[g] = h->ms[g];
     if (names) names[g] = kSurfGroupNames[g];
   }
-  return kSurfGroups;
+  return h->groups;
   E3D_CATCH()
 }
 

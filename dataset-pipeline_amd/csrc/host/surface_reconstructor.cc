@@ -5,10 +5,27 @@
 // (e3d_surface_reconstruct; the rules: include/e3d_hip.h).  The mesh ends where the data ends: unobserved regions are not filled.
 //
 //   SurfaceReconstructor --point_normal_cloud_path cloud.ply --output_path surface.ply [--voxel_size 0.02] [--support_radius 2 x voxel_size]
-//                        [--timings]
+//                        [--csg_script boxes.txt] [--print_csg_script] [--timings]
+//
+// --csg_script: what the reference's editor does by hand with its CSG tool (src/point_cloud_editor/tool_csg.cc: a box united with or
+// subtracted from the surface mesh where the scanner missed glass or dark objects), as a text file that is applied again whenever the
+// surface is rebuilt (e3d_surface_reconstruct_csg).  `#` starts a comment; otherwise one operation per line, applied in order:
+//   union box    CX CY CZ  QW QX QY QZ  EX EY EZ
+//   subtract box CX CY CZ  QW QX QY QZ  EX EY EZ
+// C is the centre, E the FULL extents in metres (the editor's object_extent_), Q a unit quaternion, world from box.  A quaternion whose
+// norm n = sqrt(((w w + x x) + y y) + z z) differs from 1 by more than 1e-6 is an error; otherwise (w, x, y, z) are divided by n and
+//   R = | 1 - 2 (y y + z z)   2 (x y - w z)       2 (x z + w y)     |
+//       | 2 (x y + w z)       1 - 2 (x x + z z)   2 (y z - w x)     |
+//       | 2 (x z - w y)       2 (y z + w x)       1 - 2 (x x + y y) |
+// in f64, each entry evaluated as written.  The whole file is read and checked before the cloud is loaded; every error names file:line.
+// --print_csg_script prints the operations as they go to the library (%.17g).  The cloud may hold zero points.
+#include <cmath>
 #include <cstdint>
+#include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
+#include <sstream>
 #include <string>
 #include <vector>
 
@@ -17,6 +34,73 @@
 #include "util.h"
 
 using namespace e3d_host;
+
+namespace {
+
+bool to_double(const std::string& s, double* v) {
+  if (s.empty()) return false;
+  char* end = nullptr;
+  *v = strtod(s.c_str(), &end);
+  return end && *end == 0;
+}
+
+// one line of the script (comment removed) -> an operation, or the reason why not
+bool parse_csg_line(const std::vector<std::string>& tok, e3d_surface_solid_t* op, std::string* why) {
+  if (tok[0] == "union") op->kind = E3D_SURFACE_UNION;
+  else if (tok[0] == "subtract") op->kind = E3D_SURFACE_SUBTRACT;
+  else { *why = "unknown operation '" + tok[0] + "' (union or subtract expected)"; return false; }
+  if (tok.size() < 2 || tok[1] != "box") { *why = tok[0] + ": the only solid is 'box'"; return false; }
+  if (tok.size() != 12) { *why = tok[0] + " box: 10 numbers expected (CX CY CZ QW QX QY QZ EX EY EZ), " + std::to_string(tok.size() - 2) + " given"; return false; }
+  double v[10];
+  for (int i = 0; i < 10; ++i) {
+    if (!to_double(tok[2 + i], &v[i])) { *why = tok[0] + " box: '" + tok[2 + i] + "' is not a number"; return false; }
+    if (!std::isfinite(v[i])) { *why = tok[0] + " box: '" + tok[2 + i] + "' is not finite"; return false; }
+  }
+  double w = v[3], x = v[4], y = v[5], z = v[6];
+  const double norm = std::sqrt(((w * w + x * x) + y * y) + z * z);
+  if (!(std::fabs(norm - 1.0) <= 1e-6)) {
+    char buf[128];
+    snprintf(buf, sizeof buf, " box: the quaternion has norm %.9g, a unit quaternion is expected", norm);
+    *why = tok[0] + buf;
+    return false;
+  }
+  w /= norm; x /= norm; y /= norm; z /= norm;
+  double* R = op->rotation;
+  R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - w * z);       R[2] = 2.0 * (x * z + w * y);
+  R[3] = 2.0 * (x * y + w * z);       R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - w * x);
+  R[6] = 2.0 * (x * z - w * y);       R[7] = 2.0 * (y * z + w * x);       R[8] = 1.0 - 2.0 * (x * x + y * y);
+  for (int a = 0; a < 3; ++a) {
+    op->centre[a] = v[a];
+    if (!(v[7 + a] > 0.0)) { *why = tok[0] + " box: the extents must be positive"; return false; }
+    op->half_extent[a] = 0.5 * v[7 + a];
+  }
+  return true;
+}
+
+bool read_csg_script(const std::string& path, std::vector<e3d_surface_solid_t>* ops) {
+  std::ifstream f(path);
+  if (!f) { std::cerr << "Cannot read the script " << path << std::endl; return false; }
+  std::string line;
+  int line_no = 0;
+  while (std::getline(f, line)) {
+    ++line_no;
+    const size_t hash = line.find('#');
+    if (hash != std::string::npos) line.resize(hash);
+    std::istringstream ls(line);
+    std::vector<std::string> tok;
+    std::string t;
+    while (ls >> t) tok.push_back(t);
+    if (tok.empty()) continue;
+    e3d_surface_solid_t op{};
+    std::string why;
+    if (ops->size() >= 256) why = "more than 256 operations";
+    if (!why.empty() || !parse_csg_line(tok, &op, &why)) { std::cerr << path << ":" << line_no << ": " << why << std::endl; return false; }
+    ops->push_back(op);
+  }
+  return true;
+}
+
+}  // namespace
 
 int main(int argc, char** argv) {
   std::string point_normal_cloud_path;
@@ -28,11 +112,26 @@ int main(int argc, char** argv) {
   float support_radius = 2.f * voxel_size;
   parse_argument(argc, argv, "--support_radius", support_radius);
   const bool timings = find_argument(argc, argv, "--timings") > 0;
+  std::string csg_script;
+  parse_argument(argc, argv, "--csg_script", csg_script);
 
   if (point_normal_cloud_path.empty() || output_path.empty()) {
     std::cout << "Please provide input / output paths." << std::endl;
     return EXIT_FAILURE;
   }
+
+  std::vector<e3d_surface_solid_t> ops;
+  if (!csg_script.empty() && !read_csg_script(csg_script, &ops)) return EXIT_FAILURE;
+  if (find_argument(argc, argv, "--print_csg_script") > 0)
+    for (const e3d_surface_solid_t& op : ops) {
+      fprintf(stderr, "[csg] %s box centre", op.kind == E3D_SURFACE_UNION ? "union" : "subtract");
+      for (double v : op.centre) fprintf(stderr, " %.17g", v);
+      fprintf(stderr, " rotation");
+      for (double v : op.rotation) fprintf(stderr, " %.17g", v);
+      fprintf(stderr, " half_extent");
+      for (double v : op.half_extent) fprintf(stderr, " %.17g", v);
+      fprintf(stderr, "\n");
+    }
 
   std::cerr << "Loading point cloud ..." << std::endl;
   PointCloud cloud;
@@ -43,7 +142,10 @@ int main(int argc, char** argv) {
   }
 
   std::cerr << "Reconstructing the surface ..." << std::endl;
-  e3d_surface_t* surface = api().e3d_surface_reconstruct(cloud.xyz.data(), cloud.normals.data(), cloud.size(), voxel_size, support_radius);
+  e3d_surface_t* surface = csg_script.empty()
+                               ? api().e3d_surface_reconstruct(cloud.xyz.data(), cloud.normals.data(), cloud.size(), voxel_size, support_radius)
+                               : api().e3d_surface_reconstruct_csg(cloud.xyz.data(), cloud.normals.data(), cloud.size(), voxel_size, support_radius,
+                                                                   ops.data(), ops.size());
   if (!surface) {
     std::cerr << "SurfaceReconstructor: " << api().e3d_last_error() << std::endl;
     return EXIT_FAILURE;

@@ -835,8 +835,47 @@ int e3d_surface_get_corners(e3d_surface_t* surface, int32_t* ijk, double* f, dou
 /* The mesh: vertices[3 v] f32, the vertices' cells cell_ijk[3 v] (may be NULL), triangles[3 t] as vertex indices. */
 int e3d_surface_get_mesh(e3d_surface_t* surface, float* vertices, int32_t* cell_ijk, uint32_t* triangles);
 /* HIP-event times of the call's kernel groups in ms and their names (static strings), at most capacity of each (either
- * array may be NULL); returns the number of groups: grid, candidates, field, corners, extract. */
+ * array may be NULL); returns the number of groups: grid, candidates, field, corners, extract, and for a handle made with
+ * n_ops > 0 a sixth, solids, last. */
 int e3d_surface_kernel_ms(e3d_surface_t* surface, float* ms, const char** names, int capacity);
+
+/* ---- SurfaceReconstructor: box union and subtraction (the reference's CSG tool, src/point_cloud_editor/tool_csg.cc) --------
+ * Scanners miss glass, dark or shiny objects and what no scan position sees; the reference's editor places a subdivided box by
+ * hand and unites it with or subtracts it from the surface mesh through a mesh boolean.  Here the box is an analytic signed
+ * function on the lattice and is combined with the scan field BEFORE the extraction above, which stays as it is.  All
+ * arithmetic is f64 with no contraction, in the stated order.  x = (h i, h j, h k) is a lattice corner.
+ *
+ * A solid is an oriented box with centre c[3], rotation Q[9] (row-major; the columns are the box axes in world coordinates)
+ * and half extents a[3].  Its function at x:  d = x - c;  u_m = (Q[0][m] d_0 + Q[1][m] d_1) + Q[2][m] d_2;  q_m = |u_m| - a_m;
+ * g = max(max(q_0, q_1), q_2).  g is negative inside, zero on the surface and 1-Lipschitz; no square root, no libm call.
+ * An operation list of at most 256 entries (kind, solid) is applied in order to the scan field f = S / W (defined iff a
+ * point counts):
+ *   union     at a defined corner f <- min(f, g); at an undefined corner with |g| <= 2 h the corner becomes defined with
+ *             f = g.  (An edge of length h that crosses g = 0 has |g| < h at both ends: the rest of the band is slack.)
+ *   subtract  (A minus B) at a defined corner f <- max(f, -g).  No corner becomes defined: as in the reference, subtracting
+ *             from nothing gives nothing.
+ * min and max return their first argument on equality.  "Negative iff f < 0", the crossing rule, t = f_a / (f_a - f_b) and the
+ * vertex, quad and ordering rules are unchanged.  For a corner defined by solids alone e3d_surface_get_corners reports
+ * count = 0 and W = 0; for every other corner count and W are the scan's.
+ * Known artefact.  Where a union box touches a wall seen from one side, the band of newly defined positive corners outside
+ * the box meets the wall's negative back side: a strip of back sheet at most two cells wide appears behind the wall.
+ * Refused (NULL; E3D_ERR_INVALID, the library stays usable): more than 256 operations or an unknown kind; a centre, rotation
+ * or extent that is not finite; a half extent <= 0; max |Q^T Q - I| > 1e-9 or det Q < 0; a solid whose band (its world
+ * bounding box grown by 2 h, two lattice steps of margin) reaches |coordinate| / h >= 2^20; points and solids (union and
+ * subtract alike) that together span more than 2^21 - 36 lattice steps along one axis; solids whose bands cover more than
+ * 2^32 - 64 bricks of 4 x 4 x 4 corners, or candidates beyond the per-call limits of e3d_surface_reconstruct.
+ * n_ops == 0 is e3d_surface_reconstruct: the same launches, the same bytes, the same five kernel groups.  n == 0 or no
+ * contributing point is no early end when there is a union: the result is the mesh of the boxes alone. */
+#define E3D_SURFACE_UNION 0
+#define E3D_SURFACE_SUBTRACT 1
+typedef struct e3d_surface_solid {
+  int32_t kind;           /* E3D_SURFACE_UNION or E3D_SURFACE_SUBTRACT */
+  double centre[3];
+  double rotation[9];
+  double half_extent[3];
+} e3d_surface_solid_t;
+e3d_surface_t* e3d_surface_reconstruct_csg(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius,
+                                           const e3d_surface_solid_t* ops, size_t n_ops);
 
 /* ---- ReconstructionEvaluator: accuracy and completeness of a reconstruction against the scans ----------------------------
  * The ETH3D evaluation scheme the reference's README describes and neither tree computes: a reconstruction point within a
