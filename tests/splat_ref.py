@@ -110,6 +110,8 @@ def mesh_min_sq(points, V, T, max_sq=np.inf, chunk=1 << 20):
     n, nt = points.shape[0], T.shape[0]
     best = np.full(n, np.inf, F)
     bid = np.full(n, -1, np.int32)
+    if nt == 0:                                                        # an empty mesh: nothing is below +inf
+        return best, bid
     per = max(1, chunk // max(nt, 1))
     for s in range(0, n, per):
         e = min(n, s + per)
@@ -196,6 +198,23 @@ def culled_min_sq(Q, V, T, max_sq):
     return best, bid
 
 
+def near_feature_pairs(rng, m):
+    """(p, a, b, c) float32 for the tests of the pruning margin: ordinary triangles with vertices in [-2, 2]^3 and a query a few
+    tens of ulps -- 10^U(-7, -5) of the triangle's max |coordinate| -- from vertex b or from a point of edge ab, in a random
+    direction (half of them perpendicular to ab).  This close the computed edge point a + t ab can land an ulp outside the
+    triangle's box on the query's side, which is a visible part of the distance: the input class that needs delta."""
+    a, b, c = (rng.uniform(-2, 2, (m, 3)).astype(F) for _ in range(3))
+    ab = b.astype(np.float64) - a
+    d = rng.normal(size=(m, 3))
+    perp = d - (d * ab).sum(1, keepdims=True) * ab / np.maximum((ab * ab).sum(1, keepdims=True), 1e-300)
+    d = np.where(rng.random((m, 1)) < 0.5, perp, d)
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    ext = np.abs(np.stack([a, b, c], 1)).max((1, 2))[:, None]
+    t = np.where(rng.random((m, 1)) < 0.5, 1.0, rng.uniform(0, 1, (m, 1)))
+    p = (a + t * ab + 10.0 ** rng.uniform(-7, -5, (m, 1)) * ext * d).astype(F)
+    return p, a, b, c
+
+
 def unit_orthogonal(n):
     """Eigen 3.3 unitOrthogonal of (m, 3) float32 vectors (the 3-vector selector, precision 1e-5f)."""
     n = np.asarray(n, F)
@@ -240,8 +259,9 @@ def splat_radius(xyz, max_splat_size=np.inf):
     return r
 
 
-def splats(xyz, normals, V, T, distance_threshold=0.02, max_splat_size=np.inf):
-    """The tool: (vertices[4m,3], faces[2m,3], add_splat[n], radius[n]) in ascending point order."""
+def splats(xyz, normals, V, T, distance_threshold=0.02, max_splat_size=np.inf, cull=True):
+    """The tool: (vertices[4m,3], faces[2m,3], add_splat[n], radius[n]) in ascending point order.  cull=False: "within" is the
+    full brute-force minimum (mesh_min_sq) <= thr2, with no box culling and no margin delta: nothing shared with the index."""
     xyz = np.asarray(xyz, F); normals = np.asarray(normals, F)
     thr = F(distance_threshold)
     thr2 = thr * thr
@@ -256,7 +276,7 @@ def splats(xyz, normals, V, T, distance_threshold=0.02, max_splat_size=np.inf):
         for q in [xyz[idx]] + [C[:, k] for k in range(4)]:
             fin = np.isfinite(q).all(1)
             within = np.zeros(idx.size, bool)
-            within[fin] = any_within(q[fin], V, T, thr2)
+            within[fin] = any_within(q[fin], V, T, thr2) if cull else (mesh_min_sq(q[fin], V, T, thr2)[0] <= thr2)
             far |= ~within
         add[idx] = far
     verts = C[add[idx]].reshape(-1, 3)

@@ -85,6 +85,130 @@ def test_brute_force_minimum_ties_and_nan():
     assert d[0] == np.inf and i[0] == -1
 
 
+def test_splats_cull_argument_selects_the_brute_force_reference(monkeypatch):
+    """splats(cull=False) decides "within" by mesh_min_sq alone; the default still goes through any_within."""
+    calls = []
+    real = sr.any_within
+    monkeypatch.setattr(sr, "any_within", lambda *a: (calls.append(1), real(*a))[1])
+    monkeypatch.setattr(sr, "splat_radius", lambda xyz, m=np.inf: np.minimum(np.full(len(xyz), 0.25, np.float32), np.float32(m)))
+    V = np.array([[0, 0, 0], [4, 0, 0], [0, 4, 0]], np.float32)
+    T = np.array([[0, 1, 2]], np.int64)
+    xyz = np.array([[1, 1, 0.5], [1, 1, 0.51], [1, 2, 0.25], [3.9, 3.9, 0], [1, 1, np.nan], [2, 1, 0.5]], np.float32)
+    nrm = np.tile(np.array([[0, 0, 1]], np.float32), (6, 1))
+    nrm[5, 0] = np.nan
+    a = sr.splats(xyz, nrm, V, T, 0.5, np.inf)
+    assert calls
+    calls.clear()
+    b = sr.splats(xyz, nrm, V, T, 0.5, np.inf, cull=False)
+    assert not calls
+    assert list(b[2]) == [False, True, False, True, False, False]      # at the threshold, above it, below it, off the mesh
+    for x, y in zip(a, b):
+        assert np.array_equal(x, y, equal_nan=True)
+
+
+# ---- the pruning bound of csrc/e3d_splats.hip, restated -----------------------------------------------------------------
+BOUND_SHRINK = np.float32(1.0) - np.float32(1.0) / np.float32(1048576.0)     # kBoundShrink
+REGULAR_SIN2 = 1.0 / 65536.0                                                 # kRegularSin2
+
+
+def query_delta(mag, p):
+    """query_delta: kMarginScale * max(mag, |px|, |py|, |pz|), f32."""
+    F = np.float32
+    return sr.MARGIN_SCALE * np.maximum(F(mag), np.maximum(np.abs(p[:, 0]), np.maximum(np.abs(p[:, 1]), np.abs(p[:, 2]))))
+
+
+def node_lower_bound(lo, hi, p, delta):
+    """node_lower_bound in f32, the kernel's operation order: per axis max(max(lo - p, p - hi) - delta, 0), the squares summed as
+    (gx gx + gy gy) + gz gz, times (1 - 2^-20)."""
+    F = np.float32
+    g = [np.maximum(np.maximum(lo[:, k] - p[:, k], p[:, k] - hi[:, k]) - delta, F(0)) for k in range(3)]
+    return ((g[0] * g[0] + g[1] * g[1]) + g[2] * g[2]) * BOUND_SHRINK
+
+
+def in_tree(a, b, c):
+    """k_tri_keys' test for finite vertices: no two equal and the f64 sin^2 of the angle at a >= 2^-16."""
+    distinct = (a != b).any(1) & (a != c).any(1) & (b != c).any(1)
+    u = b.astype(np.float64) - a.astype(np.float64)
+    w = c.astype(np.float64) - a.astype(np.float64)
+    n = np.stack([u[:, 1] * w[:, 2] - u[:, 2] * w[:, 1], u[:, 2] * w[:, 0] - u[:, 0] * w[:, 2], u[:, 0] * w[:, 1] - u[:, 1] * w[:, 0]], 1)
+    nn = n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1] + n[:, 2] * n[:, 2]
+    uu = u[:, 0] * u[:, 0] + u[:, 1] * u[:, 1] + u[:, 2] * u[:, 2]
+    ww = w[:, 0] * w[:, 0] + w[:, 1] * w[:, 1] + w[:, 2] * w[:, 2]
+    return distinct & (nn >= REGULAR_SIN2 * uu * ww)
+
+
+def _bound_pairs(rng, m):
+    """(point, triangle) pairs: scale 10^U(-3, 3), offset up to 10^4, a third generic, two thirds slivers with an angle of
+    10^U(-2.45, -1) rad at a; the query a + u ab + v ac + h n with u, v in [-0.5, 1.5] and |h| = 10^U(-4, 3) scale."""
+    F = np.float32
+    scale = 10.0 ** rng.uniform(-3, 3, (m, 1))
+    off = rng.uniform(-1, 1, (m, 3)) * 10.0 ** rng.uniform(-1, 4, (m, 1))
+    off[rng.random(m) < 0.1] = 0.0
+    a = off + scale * rng.uniform(-1, 1, (m, 3))
+    d1 = rng.normal(size=(m, 3)); d1 /= np.linalg.norm(d1, axis=1, keepdims=True)
+    d2 = rng.normal(size=(m, 3)); d2 -= (d2 * d1).sum(1, keepdims=True) * d1; d2 /= np.linalg.norm(d2, axis=1, keepdims=True)
+    theta = np.where(rng.random((m, 1)) < 1.0 / 3.0, rng.uniform(0.1, np.pi - 0.1, (m, 1)), 10.0 ** rng.uniform(-2.45, -1, (m, 1)))
+    b = a + scale * rng.uniform(0.2, 1.5, (m, 1)) * d1
+    c = a + scale * rng.uniform(0.2, 1.5, (m, 1)) * (np.cos(theta) * d1 + np.sin(theta) * d2)
+    a, b, c = a.astype(F), b.astype(F), c.astype(F)
+    keep = in_tree(a, b, c)
+    a, b, c, scale = a[keep], b[keep], c[keep], scale[keep]
+    k = a.shape[0]
+    ab = b.astype(np.float64) - a; ac = c.astype(np.float64) - a
+    n = np.cross(ab, ac); n /= np.linalg.norm(n, axis=1, keepdims=True)
+    h = 10.0 ** rng.uniform(-4, 3, (k, 1)) * scale * rng.choice([-1.0, 1.0], (k, 1))
+    p = (a + rng.uniform(-0.5, 1.5, (k, 1)) * ab + rng.uniform(-0.5, 1.5, (k, 1)) * ac + h * n).astype(F)
+    return p, a, b, c
+
+
+def _own_box(p, a, b, c):
+    """the triangle's own box, the kernel's bound with the smallest delta a mesh holding the triangle can have (mag = its own
+    max |coordinate|), the same bound with delta = 0, and the computed leaf value"""
+    lo = np.minimum(np.minimum(a, b), c); hi = np.maximum(np.maximum(a, b), c)
+    mag = np.maximum(np.abs(lo), np.abs(hi)).max(1)
+    value = sr.ericson_sq(p, a, b, c)
+    assert not np.isnan(value).any()
+    return node_lower_bound(lo, hi, p, query_delta(mag, p)), node_lower_bound(lo, hi, p, query_delta(mag, p) * 0), value
+
+
+def test_node_bound_of_a_triangles_own_box_never_exceeds_its_leaf_value():
+    """The prune of mesh_min_sq / mesh_any_within is safe only if the bound of a box never lies above the computed Ericson value
+    of a tree triangle inside it.  Checked here for the tightest box (the triangle's own) and the smallest delta a mesh holding
+    the triangle can have.  One violation is a wrong answer on the GPU: a one-triangle mesh queried with max_sq = the computed
+    value would return +inf.  Zero violations is the condition.
+
+    Two strata.  The wide one (scales 10^-3 .. 10^3, offsets to 10^4, slivers down to the tree's threshold, heights from
+    10^-4 scales) never needs delta: there the value falls below the bare gap only by the rounding of the two sums, which
+    the factor (1 - 2^-20) covers.  The near one (queries tens of ulps from a vertex or an edge) does: the computed edge point
+    a + t ab lands an ulp outside the box on the query's side, and an ulp is up to 10^-3 of such a distance.  The test counts
+    those pairs, so a restatement that drops delta fails the condition on them."""
+    rng = np.random.default_rng(20240614)
+    total = 0
+    slivers = 0
+    tight = 0
+    for _ in range(4):
+        p, a, b, c = _bound_pairs(rng, 560_000)
+        bound, bare, value = _own_box(p, a, b, c)
+        bad = np.nonzero(~(bound <= value))[0]
+        assert bad.size == 0, (bad.size, [(p[i], a[i], b[i], c[i], bound[i], value[i]) for i in bad[:3]])
+        total += p.shape[0]
+        u = b.astype(np.float64) - a; w = c.astype(np.float64) - a
+        s2 = (np.cross(u, w) ** 2).sum(1) / ((u * u).sum(1) * (w * w).sum(1))
+        slivers += int((s2 < 4 * REGULAR_SIN2).sum())
+        tight += int((bare / BOUND_SHRINK >= value)[value > 0].sum())
+    assert total >= 1_900_000
+    assert slivers >= 50_000          # triangles within a factor 4 of the smallest sin^2 the tree admits
+    assert tight >= 1_000             # pairs whose value does not exceed the bare gap: the factor is what keeps the bound below
+    # the near stratum
+    p, a, b, c = sr.near_feature_pairs(rng, 400_000)
+    keep = in_tree(a, b, c)
+    bound, bare, value = _own_box(p[keep], a[keep], b[keep], c[keep])
+    bad = np.nonzero(~(bound <= value))[0]
+    assert bad.size == 0, (bad.size, [(p[keep][i], a[keep][i], b[keep][i], c[keep][i], bound[i], value[i]) for i in bad[:3]])
+    assert keep.sum() >= 390_000
+    assert (bare > value).sum() >= 50  # pairs that delta alone keeps right
+
+
 def test_unit_orthogonal_unit_orthogonal_both_branches():
     rng = np.random.default_rng(7)
     n = rng.normal(size=(5000, 3)).astype(np.float32)
