@@ -23,6 +23,10 @@ struct Error : std::runtime_error {
 
 void set_last_error(const std::string& msg);
 
+// The number of visible HIP devices; throws E3D_ERR_NO_DEVICE if there is none.  Entry points call it after their argument checks:
+// a bad argument is refused as E3D_ERR_INVALID with or without a GPU.
+int require_device();
+
 // Frees the device memory the library only keeps as a cache (the kNN workspace pool of e3d_normals.hip); true if anything
 // was freed.  DevBuf calls it once when hipMalloc reports out-of-memory and retries.
 bool release_cached_device_memory();
@@ -56,6 +60,10 @@ inline bool env_default_off(const char* name) { const char* e = getenv(name); re
 #define E3D_CATCH()                                                                         \
   } catch (const e3d::Error& e) { e3d::set_last_error(e.what()); return e.code; }           \
   catch (const std::exception& e) { e3d::set_last_error(e.what()); return E3D_ERR_INVALID; }
+// ... of a constructor, which returns a handle: nullptr, and the half-built handle h (a plain pointer declared before E3D_TRY,
+// nullptr until it is allocated) is deleted
+#define E3D_CATCH_NEW(h)                                                                    \
+  } catch (const std::exception& e) { e3d::set_last_error(e.what()); delete (h); return nullptr; }
 
 #define E3D_HIP(expr)                                                                     \
   do {                                                                                    \
@@ -137,6 +145,28 @@ struct EventTimer {
   void start(hipStream_t s) { E3D_HIP(hipEventRecord(a, s)); }
   void stop(hipStream_t s) { E3D_HIP(hipEventRecord(b, s)); }
   float ms() { E3D_HIP(hipEventSynchronize(b)); float t = 0; E3D_HIP(hipEventElapsedTime(&t, a, b)); return t; }
+};
+
+// HIP-event time of a kernel group whose launches alternate with another group's: the sum of its spans
+struct GroupTimer {
+  std::vector<EventTimer*> spans;
+  GroupTimer() = default;
+  GroupTimer(const GroupTimer&) = delete;
+  GroupTimer& operator=(const GroupTimer&) = delete;
+  ~GroupTimer() { for (EventTimer* t : spans) delete t; }
+  void start(hipStream_t s) { spans.push_back(new EventTimer); spans.back()->start(s); }
+  void stop(hipStream_t s) { spans.back()->stop(s); }
+  float ms() { float sum = 0; for (EventTimer* t : spans) sum += t->ms(); return sum; }
+};
+
+// The non-blocking stream of one call.  Declare it before the buffers the call's work uses: leaving the call, by return or by
+// exception, first waits for whatever is still queued and then destroys the stream.
+struct OwnedStream {
+  hipStream_t s = nullptr;
+  OwnedStream() { E3D_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  OwnedStream(const OwnedStream&) = delete;
+  OwnedStream& operator=(const OwnedStream&) = delete;
+  ~OwnedStream() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
 };
 
 inline size_t div_up(size_t a, size_t b) { return (a + b - 1) / b; }

@@ -214,114 +214,105 @@ using namespace e3d;
 
 extern "C" int e3d_render_cube_map(const float* xyz, const uint8_t* rgb, size_t n, int size, int fill, uint8_t* color_out,
                                    float* depth_out, int32_t* sweeps_out) {
-  try {
-    if ((!xyz && n) || (!rgb && n) || !color_out || !depth_out) throw Error(E3D_ERR_INVALID, "e3d_render_cube_map: null argument");
-    if (size < 3) throw Error(E3D_ERR_INVALID, fmt("e3d_render_cube_map: size %d, need at least 3", size));
-    if (size > 16384) throw Error(E3D_ERR_INVALID, fmt("e3d_render_cube_map: size %d, at most 16384", size));
-    if (n >= ((size_t)1 << 31)) throw Error(E3D_ERR_INVALID, "e3d_render_cube_map: more than 2^31-1 points");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-      throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-    hipStream_t s = nullptr;
-    E3D_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } guard{s};
+  E3D_TRY
+  if ((!xyz && n) || (!rgb && n) || !color_out || !depth_out) throw Error(E3D_ERR_INVALID, "e3d_render_cube_map: null argument");
+  if (size < 3) throw Error(E3D_ERR_INVALID, fmt("e3d_render_cube_map: size %d, need at least 3", size));
+  if (size > 16384) throw Error(E3D_ERR_INVALID, fmt("e3d_render_cube_map: size %d, at most 16384", size));
+  if (n >= ((size_t)1 << 31)) throw Error(E3D_ERR_INVALID, "e3d_render_cube_map: more than 2^31-1 points");
+  require_device();
+  OwnedStream stream;
+  hipStream_t s = stream.s;
 
-    const size_t face_px = (size_t)size * size, n_px = 6 * face_px;
-    const int batch = sweep_batch_setting();
-    const int max_sweeps = size;                 // the largest Chebyshev distance inside a face is size - 1; one more sweep finds nothing
-    const size_t n_flag_words = (size_t)kSweepWords * ((size_t)max_sweeps + batch + 2);
-    DevBuf<float> X, D, FD;
-    DevBuf<unsigned char> C, OUT;
-    DevBuf<unsigned long long> K;
-    DevBuf<unsigned> P0, P1, FL;
-    EventTimer t_points, t_resolve, t_fill, t_sweeps;
-    X.reserve(3 * n); C.reserve(3 * n); K.reserve(n_px); D.reserve(n_px); P0.reserve(n_px); OUT.reserve(3 * n_px + 16);
-    copy_in(X.p, xyz, sizeof(float) * 3 * n, s);
-    copy_in(C.p, rgb, 3 * n, s);
+  const size_t face_px = (size_t)size * size, n_px = 6 * face_px;
+  const int batch = sweep_batch_setting();
+  const int max_sweeps = size;                 // the largest Chebyshev distance inside a face is size - 1; one more sweep finds nothing
+  const size_t n_flag_words = (size_t)kSweepWords * ((size_t)max_sweeps + batch + 2);
+  DevBuf<float> X, D, FD;
+  DevBuf<unsigned char> C, OUT;
+  DevBuf<unsigned long long> K;
+  DevBuf<unsigned> P0, P1, FL;
+  EventTimer t_points, t_resolve, t_fill, t_sweeps;
+  X.reserve(3 * n); C.reserve(3 * n); K.reserve(n_px); D.reserve(n_px); P0.reserve(n_px); OUT.reserve(3 * n_px + 16);
+  copy_in(X.p, xyz, sizeof(float) * 3 * n, s);
+  copy_in(C.p, rgb, 3 * n, s);
 
-    t_points.start(s);
-    E3D_HIP(hipMemsetAsync(K.p, 0xFF, sizeof(unsigned long long) * n_px, s));
-    if (n) hipLaunchKernelGGL(k_cube_points, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, X.p, (unsigned)n, size, (float)(size / 2), K.p);
-    t_points.stop(s);
-    t_resolve.start(s);
-    hipLaunchKernelGGL(k_cube_resolve, dim3((unsigned)div_up(n_px, 256)), dim3(256), 0, s, K.p, C.p, n_px, D.p, P0.p);
-    t_resolve.stop(s);
+  t_points.start(s);
+  E3D_HIP(hipMemsetAsync(K.p, 0xFF, sizeof(unsigned long long) * n_px, s));
+  if (n) hipLaunchKernelGGL(k_cube_points, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, X.p, (unsigned)n, size, (float)(size / 2), K.p);
+  t_points.stop(s);
+  t_resolve.start(s);
+  hipLaunchKernelGGL(k_cube_resolve, dim3((unsigned)div_up(n_px, 256)), dim3(256), 0, s, K.p, C.p, n_px, D.p, P0.p);
+  t_resolve.stop(s);
+  E3D_HIP(hipGetLastError());
+
+  int32_t sweeps[6] = {0, 0, 0, 0, 0, 0};
+  int n_batches = 0, n_launched = 0;
+  const float* depth_final = D.p;
+  const unsigned* color_final = P0.p;
+  if (fill) {
+    FD.reserve(n_px); P1.reserve(n_px); FL.reserve(n_flag_words);
+    K.release();                                                     // the keys are resolved
+    DevBuf<unsigned> P2;
+    P2.reserve(n_px);
+    E3D_HIP(hipMemsetAsync(FL.p, 0, sizeof(unsigned) * n_flag_words, s));
+    const dim3 grid((unsigned)div_up(size, kSweepTileX), (unsigned)div_up(size, kSweepTileY), 6), block(kSweepTileX, kSweepTileY);
+    t_fill.start(s);
+    hipLaunchKernelGGL(k_cube_fill, grid, block, 0, s, D.p, P0.p, size, FD.p, P1.p, FL.p);
+    t_fill.stop(s);
     E3D_HIP(hipGetLastError());
-
-    int32_t sweeps[6] = {0, 0, 0, 0, 0, 0};
-    int n_batches = 0, n_launched = 0;
-    const float* depth_final = D.p;
-    const unsigned* color_final = P0.p;
-    if (fill) {
-      FD.reserve(n_px); P1.reserve(n_px); FL.reserve(n_flag_words);
-      K.release();                                                     // the keys are resolved
-      DevBuf<unsigned> P2;
-      P2.reserve(n_px);
-      E3D_HIP(hipMemsetAsync(FL.p, 0, sizeof(unsigned) * n_flag_words, s));
-      const dim3 grid((unsigned)div_up(size, kSweepTileX), (unsigned)div_up(size, kSweepTileY), 6), block(kSweepTileX, kSweepTileY);
-      t_fill.start(s);
-      hipLaunchKernelGGL(k_cube_fill, grid, block, 0, s, D.p, P0.p, size, FD.p, P1.p, FL.p);
-      t_fill.stop(s);
+    // sweep k (1-based) reads buffer (k - 1) & 1 and writes k & 1 of {P1, P2}; its word row is k
+    unsigned* buf[2] = {P1.p, P2.p};
+    PinBuf<unsigned> mailbox;
+    mailbox.reserve((size_t)kSweepWords * (batch + 1));
+    t_sweeps.start(s);
+    int done = 0;                               // sweeps launched and looked at
+    bool more = true;
+    // row 0 (pass 1) decides whether anything is launched at all
+    E3D_HIP(hipMemcpyAsync(mailbox.p, FL.p, sizeof(unsigned) * kSweepWords, hipMemcpyDeviceToHost, s));
+    E3D_HIP(hipStreamSynchronize(s));
+    more = false;
+    for (int f = 0; f < 6; ++f) more = more || mailbox.p[f] != 0u;
+    while (more && done < max_sweeps) {
+      for (int k = done + 1; k <= done + batch; ++k)
+        hipLaunchKernelGGL(k_cube_sweep, grid, block, 0, s, buf[(k - 1) & 1], buf[k & 1], size, FL.p + (size_t)kSweepWords * (k - 1),
+                           FL.p + (size_t)kSweepWords * k);
       E3D_HIP(hipGetLastError());
-      // sweep k (1-based) reads buffer (k - 1) & 1 and writes k & 1 of {P1, P2}; its word row is k
-      unsigned* buf[2] = {P1.p, P2.p};
-      PinBuf<unsigned> mailbox;
-      mailbox.reserve((size_t)kSweepWords * (batch + 1));
-      t_sweeps.start(s);
-      int done = 0;                               // sweeps launched and looked at
-      bool more = true;
-      // row 0 (pass 1) decides whether anything is launched at all
-      E3D_HIP(hipMemcpyAsync(mailbox.p, FL.p, sizeof(unsigned) * kSweepWords, hipMemcpyDeviceToHost, s));
+      E3D_HIP(hipMemcpyAsync(mailbox.p, FL.p + (size_t)kSweepWords * (done + 1), sizeof(unsigned) * kSweepWords * batch, hipMemcpyDeviceToHost, s));
       E3D_HIP(hipStreamSynchronize(s));
+      ++n_batches; n_launched += batch;
       more = false;
-      for (int f = 0; f < 6; ++f) more = more || mailbox.p[f] != 0u;
-      while (more && done < max_sweeps) {
-        for (int k = done + 1; k <= done + batch; ++k)
-          hipLaunchKernelGGL(k_cube_sweep, grid, block, 0, s, buf[(k - 1) & 1], buf[k & 1], size, FL.p + (size_t)kSweepWords * (k - 1),
-                             FL.p + (size_t)kSweepWords * k);
-        E3D_HIP(hipGetLastError());
-        E3D_HIP(hipMemcpyAsync(mailbox.p, FL.p + (size_t)kSweepWords * (done + 1), sizeof(unsigned) * kSweepWords * batch, hipMemcpyDeviceToHost, s));
-        E3D_HIP(hipStreamSynchronize(s));
-        ++n_batches; n_launched += batch;
-        more = false;
-        for (int f = 0; f < 6; ++f) {
-          for (int k = 0; k < batch; ++k) sweeps[f] += mailbox.p[(size_t)kSweepWords * k + f] != 0u;
-          more = more || mailbox.p[(size_t)kSweepWords * (batch - 1) + f] != 0u;
-        }
-        done += batch;
+      for (int f = 0; f < 6; ++f) {
+        for (int k = 0; k < batch; ++k) sweeps[f] += mailbox.p[(size_t)kSweepWords * k + f] != 0u;
+        more = more || mailbox.p[(size_t)kSweepWords * (batch - 1) + f] != 0u;
       }
-      // sweep k validates the pixels at Chebyshev distance k from a valid one, and no distance reaches `size`
-      if (more) throw Error(E3D_ERR_INVALID, "e3d_render_cube_map: the dilation did not settle");
-      t_sweeps.stop(s);
-      depth_final = FD.p;
-      // a face that swept ends with both buffers equal (its last sweep validated nothing and copied); one that never swept
-      // lives in P1 only
-      color_final = buf[0];
-      hipLaunchKernelGGL(k_cube_unpack, dim3((unsigned)div_up(div_up(n_px, 4), 256)), dim3(256), 0, s, color_final, n_px, OUT.p);
-      E3D_HIP(hipGetLastError());
-      copy_out(color_out, OUT.p, 3 * n_px, s);
-      copy_out(depth_out, depth_final, sizeof(float) * n_px, s);
-      E3D_HIP(hipStreamSynchronize(s));
-      g_cube_timings[2] = t_fill.ms(); g_cube_timings[3] = t_sweeps.ms();
-    } else {
-      hipLaunchKernelGGL(k_cube_unpack, dim3((unsigned)div_up(div_up(n_px, 4), 256)), dim3(256), 0, s, color_final, n_px, OUT.p);
-      E3D_HIP(hipGetLastError());
-      copy_out(color_out, OUT.p, 3 * n_px, s);
-      copy_out(depth_out, depth_final, sizeof(float) * n_px, s);
-      E3D_HIP(hipStreamSynchronize(s));
-      g_cube_timings[2] = 0.f; g_cube_timings[3] = 0.f;
+      done += batch;
     }
-    g_cube_timings[0] = t_points.ms(); g_cube_timings[1] = t_resolve.ms();
-    g_cube_timings[4] = (float)n_batches; g_cube_timings[5] = (float)n_launched;
-    if (sweeps_out) for (int f = 0; f < 6; ++f) sweeps_out[f] = sweeps[f];
-    return 0;
-  } catch (const e3d::Error& e) {
-    e3d::set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return E3D_ERR_INVALID;
+    // sweep k validates the pixels at Chebyshev distance k from a valid one, and no distance reaches `size`
+    if (more) throw Error(E3D_ERR_INVALID, "e3d_render_cube_map: the dilation did not settle");
+    t_sweeps.stop(s);
+    depth_final = FD.p;
+    // a face that swept ends with both buffers equal (its last sweep validated nothing and copied); one that never swept
+    // lives in P1 only
+    color_final = buf[0];
+    hipLaunchKernelGGL(k_cube_unpack, dim3((unsigned)div_up(div_up(n_px, 4), 256)), dim3(256), 0, s, color_final, n_px, OUT.p);
+    E3D_HIP(hipGetLastError());
+    copy_out(color_out, OUT.p, 3 * n_px, s);
+    copy_out(depth_out, depth_final, sizeof(float) * n_px, s);
+    E3D_HIP(hipStreamSynchronize(s));
+    g_cube_timings[2] = t_fill.ms(); g_cube_timings[3] = t_sweeps.ms();
+  } else {
+    hipLaunchKernelGGL(k_cube_unpack, dim3((unsigned)div_up(div_up(n_px, 4), 256)), dim3(256), 0, s, color_final, n_px, OUT.p);
+    E3D_HIP(hipGetLastError());
+    copy_out(color_out, OUT.p, 3 * n_px, s);
+    copy_out(depth_out, depth_final, sizeof(float) * n_px, s);
+    E3D_HIP(hipStreamSynchronize(s));
+    g_cube_timings[2] = 0.f; g_cube_timings[3] = 0.f;
   }
+  g_cube_timings[0] = t_points.ms(); g_cube_timings[1] = t_resolve.ms();
+  g_cube_timings[4] = (float)n_batches; g_cube_timings[5] = (float)n_launched;
+  if (sweeps_out) for (int f = 0; f < 6; ++f) sweeps_out[f] = sweeps[f];
+  return 0;
+  E3D_CATCH()
 }
 
 extern "C" int e3d_cube_map_timings(float* out) {

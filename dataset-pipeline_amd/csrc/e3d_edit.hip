@@ -334,26 +334,23 @@ void compact(e3d_edit* h, int invert, float* out, size_t capacity) {
 extern "C" {
 
 e3d_edit_t* e3d_edit_create(const float* xyz, size_t n) {
-  try {
-    if (!xyz && n) throw Error(E3D_ERR_INVALID, "e3d_edit_create: null points");
-    if (n >= ((size_t)1 << 32)) throw Error(E3D_ERR_INVALID, "e3d_edit_create: 2^32 points or more");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-    std::unique_ptr<e3d_edit> h(new e3d_edit());
-    E3D_HIP(hipGetDevice(&h->device));
-    E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->timer.reset(new EventTimer());
-    h->n = n;
-    h->X.reserve(3 * round4(n) + 4); h->F.reserve(round4(n) + 4); h->words.reserve(1 + E3D_EDIT_MAX_CLICKS);
-    E3D_HIP(hipMemsetAsync(h->X.p, 0, sizeof(float) * (3 * round4(n) + 4), h->stream));
-    E3D_HIP(hipMemsetAsync(h->F.p, 0, round4(n) + 4, h->stream));
-    copy_in(h->X.p, xyz, sizeof(float) * 3 * n, h->stream);
-    E3D_HIP(hipStreamSynchronize(h->stream));
-    return h.release();
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return nullptr;
-  }
+  e3d_edit* h = nullptr;
+  E3D_TRY
+  if (!xyz && n) throw Error(E3D_ERR_INVALID, "e3d_edit_create: null points");
+  if (n >= ((size_t)1 << 32)) throw Error(E3D_ERR_INVALID, "e3d_edit_create: 2^32 points or more");
+  require_device();
+  h = new e3d_edit();
+  E3D_HIP(hipGetDevice(&h->device));
+  E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  h->timer.reset(new EventTimer());
+  h->n = n;
+  h->X.reserve(3 * round4(n) + 4); h->F.reserve(round4(n) + 4); h->words.reserve(1 + E3D_EDIT_MAX_CLICKS);
+  E3D_HIP(hipMemsetAsync(h->X.p, 0, sizeof(float) * (3 * round4(n) + 4), h->stream));
+  E3D_HIP(hipMemsetAsync(h->F.p, 0, round4(n) + 4, h->stream));
+  copy_in(h->X.p, xyz, sizeof(float) * 3 * n, h->stream);
+  E3D_HIP(hipStreamSynchronize(h->stream));
+  return h;
+  E3D_CATCH_NEW(h)
 }
 
 void e3d_edit_destroy(e3d_edit_t* h) {

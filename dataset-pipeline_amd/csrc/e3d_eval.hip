@@ -299,15 +299,6 @@ struct e3d_eval {
 
 namespace {
 
-// HIP-event time of a kernel group whose launches alternate with another group's
-struct GroupTimer {
-  std::vector<EventTimer*> spans;
-  ~GroupTimer() { for (EventTimer* t : spans) delete t; }
-  void start(hipStream_t s) { spans.push_back(new EventTimer); spans.back()->start(s); }
-  void stop(hipStream_t s) { spans.back()->stop(s); }
-  float ms() { float sum = 0; for (EventTimer* t : spans) sum += t->ms(); return sum; }
-};
-
 float ordered_to_float(unsigned u) {
   const unsigned b = (u & 0x80000000u) ? (u & 0x7FFFFFFFu) : ~u;
   float f; memcpy(&f, &b, sizeof f); return f;
@@ -331,19 +322,13 @@ struct EvalCloud {
   size_t n_open = 0;
 };
 
-struct EvalRun {
-  hipStream_t s = nullptr;
-  DevBuf<char> temp;
-  DevBuf<unsigned char> flags;
-  DevBuf<unsigned> offsets, vals_a, vals_b, counter;
+struct EvalRun : Compactor {
+  DevBuf<unsigned> vals_a, vals_b, counter;
   DevBuf<unsigned long long> keys_a, keys_b;
   GroupTimer timer[kEvalGroups];
-  ~EvalRun() { if (s) (void)hipStreamDestroy(s); }
+  using Compactor::Compactor;
 
   static dim3 blocks(size_t n) { return dim3((unsigned)div_up(n, kEvalBlock)); }
-
-  // exclusive offsets of n flags; the number set
-  size_t scan(size_t n) { return compaction_offsets(flags.p, n, offsets, temp, s); }
 
   void upload(EvalCloud& c, const float* xyz, size_t n, float h, int T, bool with_free, const char* what) {
     c.n = n;
@@ -378,20 +363,7 @@ struct EvalRun {
     for (int a = 0; a < 3; ++a) G.org[a] = c.lo[a];
     keys_a.reserve(c.n); keys_b.reserve(c.n); vals_a.reserve(c.n); vals_b.reserve(c.n);
     hipLaunchKernelGGL(k_eval_grid_keys, blocks(c.n), dim3(kEvalBlock), 0, s, c.xyz.p, c.n, G, keys_a.p, vals_a.p);
-    sort_pairs_u64_u32(keys_a.p, keys_b.p, vals_a.p, vals_b.p, c.n, 64, temp, s);
-    P4.reserve(c.m);
-    launch_permute(c.xyz.p, nullptr, vals_b.p, c.m, P4.p, nullptr, s);
-    E3D_HIP(hipMemsetAsync(counter.p, 0, sizeof(unsigned), s));
-    launch_count_cells(keys_b.p, c.m, counter.p, s);
-    unsigned n_cells = 0;
-    copy_out(&n_cells, counter.p, sizeof n_cells, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    size_t tsize = 64;
-    while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
-    table.reserve(tsize);
-    G.mask = (unsigned)(tsize - 1);
-    E3D_HIP(hipMemsetAsync(table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-    launch_build_table(keys_b.p, c.m, table.p, G.mask, s);
+    G.mask = sort_into_cells(keys_a.p, keys_b.p, vals_a.p, vals_b.p, c.n, c.m, 64, c.xyz.p, nullptr, P4, nullptr, temp, counter, table, s).mask;
     G.P4 = P4.p; G.table = table.p;
     return G;
   }
@@ -470,13 +442,12 @@ void evaluate(e3d_eval& out, const float* rec_xyz, size_t n_rec, const float* sc
   const size_t n_scan = (size_t)scan_offsets[S];
   if (n_rec >= (size_t)1 << 31 || n_scan >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, fmt("%s: more than 2^31-1 points", fn));
   if ((n_rec && !rec_xyz) || (n_scan && !scan_xyz)) throw Error(E3D_ERR_INVALID, fmt("%s: null argument", fn));
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
+  require_device();
 
   out.T = T;
-  EvalRun run;
-  E3D_HIP(hipStreamCreateWithFlags(&run.s, hipStreamNonBlocking));
-  hipStream_t s = run.s;
+  OwnedStream stream;
+  hipStream_t s = stream.s;
+  EvalRun run(s);
   EvalCloud rec, scan;
   run.upload(rec, rec_xyz, n_rec, h, T, true, "reconstruction");
   run.upload(scan, scan_xyz, n_scan, h, T, false, "scan");
@@ -562,15 +533,11 @@ extern "C" {
 e3d_eval_t* e3d_evaluate_reconstruction(const float* rec_xyz, size_t n_rec, const float* scan_xyz, const int64_t* scan_offsets, const float* scan_origins,
                                         int n_scans, const float* tolerances, int n_tolerances, float voxel_size, int cube_map_size) {
   e3d_eval* h = nullptr;
-  try {
-    h = new e3d_eval;
-    evaluate(*h, rec_xyz, n_rec, scan_xyz, scan_offsets, scan_origins, n_scans, tolerances, n_tolerances, voxel_size, cube_map_size);
-    return h;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    delete h;
-    return nullptr;
-  }
+  E3D_TRY
+  h = new e3d_eval;
+  evaluate(*h, rec_xyz, n_rec, scan_xyz, scan_offsets, scan_origins, n_scans, tolerances, n_tolerances, voxel_size, cube_map_size);
+  return h;
+  E3D_CATCH_NEW(h)
 }
 
 void e3d_eval_destroy(e3d_eval_t* h) { delete h; }

@@ -36,6 +36,12 @@ static thread_local std::string g_last_error;
 void set_last_error(const std::string& msg) { g_last_error = msg; }
 const char* last_error_cstr() { return g_last_error.c_str(); }
 
+int require_device() {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
+  return n;
+}
+
 // Every environment switch of this file, parsed once at first use; each field carries its default and its parse rule.  "on unless 0" is
 // env_default_on (off only if the value starts with '0'), "off unless 1" env_default_off (on only if it starts with '1'); numbers go
 // through atoi / atof unclamped unless the field says so.  nn_mode, resident and sequential_dsum are initial values: e3d_set_nn_mode and
@@ -424,10 +430,8 @@ static void build_grid(e3d_icp* h, Cloud& c, float d) {
   c.G4_valid = false;                                      // the sorted order changes
   c.generation = g_grid_generation.fetch_add(1, std::memory_order_relaxed) + 1;
   c.cum_motion = 0.0; c.last_motion = 0.0; c.err_max = 0.0;
-  unsigned n_cells = 0;
   if (n > 0) {
     reserve_sort_buffers(h, n);
-    h->counter.reserve(1);
     if (sw.half != 0) {
       // sub-cell order inside every cell: sort by the 3-bit half-cell code first, then (stable) by the cell key
       unsigned* fk_a = reinterpret_cast<unsigned*>(h->keys_b.p);
@@ -440,17 +444,10 @@ static void build_grid(e3d_icp* h, Cloud& c, float d) {
     }
     sort_pairs_u64_u32(h->keys_a.p, h->keys_b.p, h->vals_a.p, h->vals_b.p, n, 63, h->sort_temp, s);
     launch_permute(c.raw_xyz.p, c.raw_nrm.p, h->vals_b.p, n, c.L4.p, c.LN.p, s);
-    E3D_HIP(hipMemsetAsync(h->counter.p, 0, sizeof(unsigned), s));
-    launch_count_cells(h->keys_b.p, n, h->counter.p, s);
-    E3D_HIP(hipMemcpyAsync(&n_cells, h->counter.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    sync(h);
   }
-  size_t tsize = 64;
-  while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
-  c.table.reserve(tsize);
-  c.grid.mask = (unsigned)(tsize - 1);
-  E3D_HIP(hipMemsetAsync(c.table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-  if (n > 0) launch_build_table(h->keys_b.p, n, c.table.p, c.grid.mask, s);
+  const CellTable cells = build_cell_table(h->keys_b.p, n, h->counter, c.table, s);
+  const unsigned n_cells = cells.n_cells;
+  c.grid.mask = cells.mask;
   sync(h);
   // dense query-key range: cells of the stored points +- 2 (one for the 27-neighbourhood, one for host/device
   // rounding of the bbox corners)
@@ -2096,8 +2093,7 @@ const char* e3d_last_error(void) { return e3d::last_error_cstr(); }
 
 int e3d_init(int device) {
   E3D_TRY
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
+  const int n = require_device();
   if (device < 0 || device >= n) throw Error(E3D_ERR_INVALID, fmt("device %d out of range (%d devices)", device, n));
   E3D_HIP(hipSetDevice(device));
   g_device = device;
@@ -2112,19 +2108,16 @@ int e3d_set_nn_mode(int mode) {
 }
 
 e3d_icp_t* e3d_icp_create(void) {
-  try {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-    E3D_HIP(hipSetDevice(g_device));
-    std::unique_ptr<e3d_icp> h(new e3d_icp());
-    h->device = g_device;
-    h->nn_mode = g_nn_mode;
-    E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    return h.release();
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return nullptr;
-  }
+  e3d_icp* h = nullptr;
+  E3D_TRY
+  require_device();
+  E3D_HIP(hipSetDevice(g_device));
+  h = new e3d_icp();
+  h->device = g_device;
+  h->nn_mode = g_nn_mode;
+  E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  return h;
+  E3D_CATCH_NEW(h)
 }
 
 void e3d_icp_destroy(e3d_icp_t* icp) { delete icp; }

@@ -214,99 +214,79 @@ using namespace e3d;
 extern "C" int64_t e3d_merge_close_points(float merge_distance, int num_scans, const float* xyz, const float* colors,
                                           const uint8_t* scan_indices, const float* max_radius, size_t n, float* out_xyz,
                                           float* out_colors, uint8_t* out_scan_indices, float* out_max_radius) {
-  try {
-    if (n && (!xyz || !colors || !scan_indices || !max_radius || !out_xyz || !out_colors || !out_scan_indices || !out_max_radius))
-      throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: null argument");
-    if (!(merge_distance > 0.f) || !std::isfinite(merge_distance)) throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: merge distance must be positive");
-    if (num_scans < 1 || num_scans > kMergeMaxScans) throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: 1..%d scans supported", kMergeMaxScans));
-    if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: more than 2^31-1 points");
-    // Inputs the reference does not define are refused on the host, before anything is launched.  A NaN point would become a centre
-    // without neighbours (mean 0 / 0); one infinite coordinate makes the bounding box infinite, the cell size grows to inf and every
-    // point lands in ONE cell -- quadratic work inside the wait loop of k_merge_decide; a scan index >= num_scans is counted but can
-    // never win the majority (colour divided by a zero count).
-    for (size_t i = 0; i < 3 * n; ++i)
-      if (!std::isfinite(xyz[i])) throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: point %zu has a non-finite coordinate", i / 3));
-    for (size_t i = 0; i < n; ++i)
-      if ((int)scan_indices[i] >= num_scans)
-        throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: point %zu has scan index %d, but there are %d scans", i, (int)scan_indices[i], num_scans));
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-    if (n == 0) return 0;
-    hipStream_t s = nullptr;
-    E3D_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{s};
+  E3D_TRY
+  if (n && (!xyz || !colors || !scan_indices || !max_radius || !out_xyz || !out_colors || !out_scan_indices || !out_max_radius))
+    throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: null argument");
+  if (!(merge_distance > 0.f) || !std::isfinite(merge_distance)) throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: merge distance must be positive");
+  if (num_scans < 1 || num_scans > kMergeMaxScans) throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: 1..%d scans supported", kMergeMaxScans));
+  if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_merge_close_points: more than 2^31-1 points");
+  // Inputs the reference does not define are refused on the host, before anything is launched.  A NaN point would become a centre
+  // without neighbours (mean 0 / 0); one infinite coordinate makes the bounding box infinite, the cell size grows to inf and every
+  // point lands in ONE cell -- quadratic work inside the wait loop of k_merge_decide; a scan index >= num_scans is counted but can
+  // never win the majority (colour divided by a zero count).
+  for (size_t i = 0; i < 3 * n; ++i)
+    if (!std::isfinite(xyz[i])) throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: point %zu has a non-finite coordinate", i / 3));
+  for (size_t i = 0; i < n; ++i)
+    if ((int)scan_indices[i] >= num_scans)
+      throw Error(E3D_ERR_INVALID, fmt("e3d_merge_close_points: point %zu has scan index %d, but there are %d scans", i, (int)scan_indices[i], num_scans));
+  require_device();
+  if (n == 0) return 0;
+  OwnedStream stream;
+  hipStream_t s = stream.s;
 
-    DevBuf<float> raw, d_col, d_mr, bbox_partial, bbox_out, o_xyz, o_col, o_mr;
-    DevBuf<unsigned char> d_scan, state, o_scan;
-    raw.reserve(3 * n); d_col.reserve(n); d_mr.reserve(n); d_scan.reserve(n); state.reserve(n);
-    copy_in(raw.p, xyz, sizeof(float) * 3 * n, s);
-    copy_in(d_col.p, colors, sizeof(float) * n, s);
-    copy_in(d_mr.p, max_radius, sizeof(float) * n, s);
-    copy_in(d_scan.p, scan_indices, n, s);
-    bbox_partial.reserve(6 * (size_t)kMaxBboxBlocks); bbox_out.reserve(6);
-    launch_bbox_aos(raw.p, n, bbox_partial.p, bbox_out.p, s);
-    float bb[6];
-    copy_out(bb, bbox_out.p, sizeof bb, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    double extent = 0, magnitude = 0;
-    for (int a = 0; a < 3; ++a) extent = std::max(extent, (double)bb[3 + a] - (double)bb[a]);
-    for (int a = 0; a < 6; ++a) magnitude = std::max(magnitude, std::fabs((double)bb[a]));
-    double cell = (double)merge_distance * (1.0 + 1e-4) + 16.0 * FLT_EPSILON * (magnitude + 4.0 * (double)merge_distance);
-    while (extent / cell > (double)((1 << 21) - 8)) cell *= 2.0;      // cells larger than the radius are fine, only slower
-    GridDesc g{};
-    g.inv_cell = (float)(1.0 / cell);
-    for (int a = 0; a < 3; ++a) g.origin[a] = (float)((double)bb[a] - 2.0 * cell);
-    DevBuf<unsigned long long> ka, kb;
-    DevBuf<unsigned> va, vb, counter, pos_of, ticket, block_counts, block_offsets;
-    DevBuf<char> temp;
-    DevBuf<float4> P4;
-    DevBuf<HashEntry> table;
-    ka.reserve(n); kb.reserve(n); va.reserve(n); vb.reserve(n); counter.reserve(2); P4.reserve(n); pos_of.reserve(n); ticket.reserve(1);
-    launch_cell_keys(raw.p, n, g, ka.p, va.p, s);
-    sort_pairs_u64_u32(ka.p, kb.p, va.p, vb.p, n, 63, temp, s);
-    launch_permute(raw.p, nullptr, vb.p, n, P4.p, nullptr, s);
-    E3D_HIP(hipMemsetAsync(counter.p, 0, 2 * sizeof(unsigned), s));
-    launch_count_cells(kb.p, n, counter.p, s);
-    unsigned n_cells = 0;
-    E3D_HIP(hipMemcpyAsync(&n_cells, counter.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    E3D_HIP(hipStreamSynchronize(s));
-    size_t tsize = 64;
-    while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
-    table.reserve(tsize);
-    g.mask = (unsigned)(tsize - 1);
-    E3D_HIP(hipMemsetAsync(table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-    launch_build_table(kb.p, n, table.p, g.mask, s);
-    const double md = (double)merge_distance;
-    const float r2 = (float)(md * md);        // pcl::KdTreeFLANN::radiusSearch: static_cast<float>(radius * radius), strict <
-    const unsigned nblk = (unsigned)div_up(n, kMergeBlock);
-    hipLaunchKernelGGL(k_merge_positions, dim3(nblk), dim3(kMergeBlock), 0, s, P4.p, n, pos_of.p);
-    E3D_HIP(hipMemsetAsync(state.p, 0, n, s));
-    E3D_HIP(hipMemsetAsync(ticket.p, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_merge_decide, dim3(nblk), dim3(kMergeBlock), 0, s, P4.p, pos_of.p, n, table.p, g, r2, ticket.p, state.p);
-    block_counts.reserve(nblk); block_offsets.reserve(nblk);
-    hipLaunchKernelGGL(k_merge_block_counts, dim3(nblk), dim3(kMergeBlock), 0, s, state.p, n, block_counts.p);
-    std::vector<unsigned> hc(nblk), ho(nblk);
-    copy_out(hc.data(), block_counts.p, sizeof(unsigned) * nblk, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    E3D_HIP(hipGetLastError());
-    size_t total = 0;
-    for (unsigned b = 0; b < nblk; ++b) { ho[b] = (unsigned)total; total += hc[b]; }
-    copy_in(block_offsets.p, ho.data(), sizeof(unsigned) * nblk, s);
-    o_xyz.reserve(3 * total); o_col.reserve(total); o_mr.reserve(total); o_scan.reserve(total);
-    hipLaunchKernelGGL(k_merge_output, dim3(nblk), dim3(kMergeBlock), 0, s, P4.p, pos_of.p, n, table.p, g, r2, state.p, block_offsets.p,
-                       d_col.p, d_scan.p, d_mr.p, num_scans, o_xyz.p, o_col.p, o_scan.p, o_mr.p);
-    copy_out(out_xyz, o_xyz.p, sizeof(float) * 3 * total, s);
-    copy_out(out_colors, o_col.p, sizeof(float) * total, s);
-    copy_out(out_scan_indices, o_scan.p, total, s);
-    copy_out(out_max_radius, o_mr.p, sizeof(float) * total, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    E3D_HIP(hipGetLastError());
-    return (int64_t)total;
-  } catch (const e3d::Error& e) {
-    e3d::set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return E3D_ERR_INVALID;
-  }
+  DevBuf<float> raw, d_col, d_mr, bbox_partial, bbox_out, o_xyz, o_col, o_mr;
+  DevBuf<unsigned char> d_scan, state, o_scan;
+  raw.reserve(3 * n); d_col.reserve(n); d_mr.reserve(n); d_scan.reserve(n); state.reserve(n);
+  copy_in(raw.p, xyz, sizeof(float) * 3 * n, s);
+  copy_in(d_col.p, colors, sizeof(float) * n, s);
+  copy_in(d_mr.p, max_radius, sizeof(float) * n, s);
+  copy_in(d_scan.p, scan_indices, n, s);
+  bbox_partial.reserve(6 * (size_t)kMaxBboxBlocks); bbox_out.reserve(6);
+  launch_bbox_aos(raw.p, n, bbox_partial.p, bbox_out.p, s);
+  float bb[6];
+  copy_out(bb, bbox_out.p, sizeof bb, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  double extent = 0, magnitude = 0;
+  for (int a = 0; a < 3; ++a) extent = std::max(extent, (double)bb[3 + a] - (double)bb[a]);
+  for (int a = 0; a < 6; ++a) magnitude = std::max(magnitude, std::fabs((double)bb[a]));
+  double cell = (double)merge_distance * (1.0 + 1e-4) + 16.0 * FLT_EPSILON * (magnitude + 4.0 * (double)merge_distance);
+  while (extent / cell > (double)((1 << 21) - 8)) cell *= 2.0;      // cells larger than the radius are fine, only slower
+  GridDesc g{};
+  g.inv_cell = (float)(1.0 / cell);
+  for (int a = 0; a < 3; ++a) g.origin[a] = (float)((double)bb[a] - 2.0 * cell);
+  DevBuf<unsigned long long> ka, kb;
+  DevBuf<unsigned> va, vb, counter, pos_of, ticket, block_counts, block_offsets;
+  DevBuf<char> temp;
+  DevBuf<float4> P4;
+  DevBuf<HashEntry> table;
+  ka.reserve(n); kb.reserve(n); va.reserve(n); vb.reserve(n); P4.reserve(n); pos_of.reserve(n); ticket.reserve(1);
+  launch_cell_keys(raw.p, n, g, ka.p, va.p, s);
+  g.mask = sort_into_cells(ka.p, kb.p, va.p, vb.p, n, n, 63, raw.p, nullptr, P4, nullptr, temp, counter, table, s).mask;
+  const double md = (double)merge_distance;
+  const float r2 = (float)(md * md);        // pcl::KdTreeFLANN::radiusSearch: static_cast<float>(radius * radius), strict <
+  const unsigned nblk = (unsigned)div_up(n, kMergeBlock);
+  hipLaunchKernelGGL(k_merge_positions, dim3(nblk), dim3(kMergeBlock), 0, s, P4.p, n, pos_of.p);
+  E3D_HIP(hipMemsetAsync(state.p, 0, n, s));
+  E3D_HIP(hipMemsetAsync(ticket.p, 0, sizeof(unsigned), s));
+  hipLaunchKernelGGL(k_merge_decide, dim3(nblk), dim3(kMergeBlock), 0, s, P4.p, pos_of.p, n, table.p, g, r2, ticket.p, state.p);
+  block_counts.reserve(nblk); block_offsets.reserve(nblk);
+  hipLaunchKernelGGL(k_merge_block_counts, dim3(nblk), dim3(kMergeBlock), 0, s, state.p, n, block_counts.p);
+  std::vector<unsigned> hc(nblk), ho(nblk);
+  copy_out(hc.data(), block_counts.p, sizeof(unsigned) * nblk, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  E3D_HIP(hipGetLastError());
+  size_t total = 0;
+  for (unsigned b = 0; b < nblk; ++b) { ho[b] = (unsigned)total; total += hc[b]; }
+  copy_in(block_offsets.p, ho.data(), sizeof(unsigned) * nblk, s);
+  o_xyz.reserve(3 * total); o_col.reserve(total); o_mr.reserve(total); o_scan.reserve(total);
+  hipLaunchKernelGGL(k_merge_output, dim3(nblk), dim3(kMergeBlock), 0, s, P4.p, pos_of.p, n, table.p, g, r2, state.p, block_offsets.p,
+                     d_col.p, d_scan.p, d_mr.p, num_scans, o_xyz.p, o_col.p, o_scan.p, o_mr.p);
+  copy_out(out_xyz, o_xyz.p, sizeof(float) * 3 * total, s);
+  copy_out(out_colors, o_col.p, sizeof(float) * total, s);
+  copy_out(out_scan_indices, o_scan.p, total, s);
+  copy_out(out_max_radius, o_mr.p, sizeof(float) * total, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  E3D_HIP(hipGetLastError());
+  return (int64_t)total;
+  E3D_CATCH()
 }

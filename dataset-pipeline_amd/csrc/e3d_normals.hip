@@ -1729,19 +1729,7 @@ static KnnGrid knn_grid_over(const float bb[6], double cell_size) {
 // as bits), the occupied cells into LB.table, G.g.mask set.  The caller has reserved LB.ka, kb, va, vb, counter and P4.
 static void build_hash_grid(const float* xyz, size_t n, LevelBuffers& LB, KnnGrid& G, hipStream_t s) {
   launch_cell_keys(xyz, n, G.g, LB.ka.p, LB.va.p, s);
-  sort_pairs_u64_u32(LB.ka.p, LB.kb.p, LB.va.p, LB.vb.p, n, 63, LB.temp, s);
-  launch_permute(xyz, nullptr, LB.vb.p, n, LB.P4.p, nullptr, s);
-  E3D_HIP(hipMemsetAsync(LB.counter.p, 0, 2 * sizeof(unsigned), s));
-  launch_count_cells(LB.kb.p, n, LB.counter.p, s);
-  unsigned n_cells = 0;
-  E3D_HIP(hipMemcpyAsync(&n_cells, LB.counter.p, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-  E3D_HIP(hipStreamSynchronize(s));
-  size_t tsize = 64;
-  while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
-  LB.table.reserve(tsize);
-  G.g.mask = (unsigned)(tsize - 1);
-  E3D_HIP(hipMemsetAsync(LB.table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-  launch_build_table(LB.kb.p, n, LB.table.p, G.g.mask, s);
+  G.g.mask = sort_into_cells(LB.ka.p, LB.kb.p, LB.va.p, LB.vb.p, n, n, 63, xyz, nullptr, LB.P4, nullptr, LB.temp, LB.counter, LB.table, s).mask;
 }
 
 // The arguments of k_knn_normals that most launches leave alone
@@ -2053,11 +2041,6 @@ void e3d::knn_kth_sqdist(const float* xyz, size_t n, int k, const std::function<
 }
 
 namespace e3d {
-static void require_device() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-}
 
 // LocalStatisticalOutlierRemoval, second pass (local_statistical_outlier_removal.hpp:113-160)
 __global__ __launch_bounds__(256) void k_outlier_classify(const int* __restrict__ knn, const float* __restrict__ mean_dist, size_t n,
@@ -2206,9 +2189,8 @@ extern "C" int e3d_normals_radius(const float* xyz, size_t n, float radius, cons
   if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_normals_radius: more than 2^31-1 points");
   require_device();
   if (n == 0) return 0;
-  hipStream_t s = nullptr;
-  E3D_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-  struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamDestroy(s); } } guard{s};
+  OwnedStream stream;
+  hipStream_t s = stream.s;
   DevBuf<float> raw, d_on, d_oc, bbox_partial, bbox_out;
   DevBuf<int> d_cnt;
   raw.reserve(3 * n); d_on.reserve(3 * n); d_oc.reserve(n);

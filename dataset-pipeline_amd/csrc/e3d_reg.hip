@@ -2518,19 +2518,16 @@ static void apply_update(e3d_reg* h, bool print, bool* applied_update, float* la
 extern "C" {
 
 e3d_reg_t* e3d_reg_create(const e3d_reg_params* params) {
-  try {
-    check_params(params);
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-    std::unique_ptr<e3d_reg> h(new e3d_reg());
-    E3D_HIP(hipGetDevice(&h->device));
-    E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    h->prm = *params;
-    return h.release();
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return nullptr;
-  }
+  e3d_reg* h = nullptr;
+  E3D_TRY
+  check_params(params);
+  require_device();
+  h = new e3d_reg();
+  E3D_HIP(hipGetDevice(&h->device));
+  E3D_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+  h->prm = *params;
+  return h;
+  E3D_CATCH_NEW(h)
 }
 void e3d_reg_destroy(e3d_reg_t* reg) { delete reg; }
 

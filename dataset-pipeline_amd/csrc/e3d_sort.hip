@@ -79,6 +79,36 @@ size_t compaction_offsets(const unsigned char* flags, size_t n, DevBuf<unsigned>
   return (size_t)last + (lf ? 1 : 0);
 }
 
+CellTable build_cell_table(const unsigned long long* sorted_keys, size_t m, DevBuf<unsigned>& counter, DevBuf<HashEntry>& table, hipStream_t s) {
+  unsigned n_cells = 0;
+  if (m > 0) {
+    counter.reserve(1);
+    E3D_HIP(hipMemsetAsync(counter.p, 0, sizeof(unsigned), s));
+    launch_count_cells(sorted_keys, m, counter.p, s);
+    copy_out(&n_cells, counter.p, sizeof n_cells, s);
+    E3D_HIP(hipStreamSynchronize(s));
+  }
+  size_t tsize = 64;
+  while (tsize < 2 * (size_t)n_cells) tsize <<= 1;
+  table.reserve(tsize);
+  const unsigned mask = (unsigned)(tsize - 1);
+  E3D_HIP(hipMemsetAsync(table.p, 0xFF, sizeof(HashEntry) * tsize, s));
+  if (m > 0) launch_build_table(sorted_keys, m, table.p, mask, s);
+  return CellTable{mask, n_cells};
+}
+
+CellTable sort_into_cells(unsigned long long* keys_a, unsigned long long* keys_b, unsigned* vals_a, unsigned* vals_b, size_t n, size_t m, int end_bit,
+                          const float* xyz, const float* nrm, DevBuf<float4>& P4, DevBuf<float4>* N4, DevBuf<char>& temp,
+                          DevBuf<unsigned>& counter, DevBuf<HashEntry>& table, hipStream_t s) {
+  if (m > 0) {
+    sort_pairs_u64_u32(keys_a, keys_b, vals_a, vals_b, n, end_bit, temp, s);
+    P4.reserve(m);
+    if (N4) N4->reserve(m);
+    launch_permute(xyz, nrm, vals_b, m, P4.p, N4 ? N4->p : nullptr, s);
+  }
+  return build_cell_table(keys_b, m, counter, table, s);
+}
+
 __global__ __launch_bounds__(kBlock) void k_flag_run_starts(const unsigned long long* __restrict__ keys, size_t n, unsigned char* __restrict__ flags) {
   const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (j < n) flags[j] = (j == 0 || keys[j] != keys[j - 1]) ? 1 : 0;

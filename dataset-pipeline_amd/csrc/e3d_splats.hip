@@ -382,12 +382,6 @@ __global__ __launch_bounds__(256) void k_splat_write(const float* __restrict__ x
   }
 }
 
-static void require_gpu() {
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-    throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
-}
-
 static void check_mesh_args(const char* what, const float* vertices, size_t nv, const uint32_t* triangles, size_t nt) {
   if ((!vertices && nv) || (!triangles && nt)) throw Error(E3D_ERR_INVALID, fmt("%s: null mesh argument", what));
 }
@@ -399,114 +393,95 @@ using namespace e3d;
 extern "C" int e3d_mesh_squared_distance(const float* points, size_t n, const float* vertices, size_t n_vertices,
                                          const uint32_t* triangles, size_t n_triangles, float max_sq_distance, float* sq_distance,
                                          int32_t* closest_triangle) {
-  try {
-    if ((!points && n) || (!sq_distance && n)) throw Error(E3D_ERR_INVALID, "e3d_mesh_squared_distance: null argument");
-    check_mesh_args("e3d_mesh_squared_distance", vertices, n_vertices, triangles, n_triangles);
-    if (std::isnan(max_sq_distance)) throw Error(E3D_ERR_INVALID, "e3d_mesh_squared_distance: max_sq_distance is NaN");
-    require_gpu();
-    hipStream_t s = nullptr;
-    E3D_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    struct StreamGuard { hipStream_t s; ~StreamGuard() { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); } } guard{s};
-    MeshIndexBuffers B;
-    build_mesh_index(B, vertices, n_vertices, triangles, n_triangles, s);
-    if (n == 0) return 0;
-    DevBuf<float> P, D;
-    DevBuf<int> I;
-    P.reserve(3 * n); D.reserve(n);
-    if (closest_triangle) I.reserve(n);
-    copy_in(P.p, points, sizeof(float) * 3 * n, s);
-    hipLaunchKernelGGL(k_mesh_min, dim3((unsigned)div_up(n, kSplatBlock)), dim3(kSplatBlock), 0, s, B.X, P.p, n, max_sq_distance, D.p,
-                       closest_triangle ? I.p : nullptr);
-    E3D_HIP(hipGetLastError());
-    copy_out(sq_distance, D.p, sizeof(float) * n, s);
-    if (closest_triangle) copy_out(closest_triangle, I.p, sizeof(int) * n, s);
-    E3D_HIP(hipStreamSynchronize(s));
-    return 0;
-  } catch (const e3d::Error& e) {
-    e3d::set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return E3D_ERR_INVALID;
-  }
+  E3D_TRY
+  if ((!points && n) || (!sq_distance && n)) throw Error(E3D_ERR_INVALID, "e3d_mesh_squared_distance: null argument");
+  check_mesh_args("e3d_mesh_squared_distance", vertices, n_vertices, triangles, n_triangles);
+  if (std::isnan(max_sq_distance)) throw Error(E3D_ERR_INVALID, "e3d_mesh_squared_distance: max_sq_distance is NaN");
+  require_device();
+  OwnedStream stream;
+  hipStream_t s = stream.s;
+  MeshIndexBuffers B;
+  build_mesh_index(B, vertices, n_vertices, triangles, n_triangles, s);
+  if (n == 0) return 0;
+  DevBuf<float> P, D;
+  DevBuf<int> I;
+  P.reserve(3 * n); D.reserve(n);
+  if (closest_triangle) I.reserve(n);
+  copy_in(P.p, points, sizeof(float) * 3 * n, s);
+  hipLaunchKernelGGL(k_mesh_min, dim3((unsigned)div_up(n, kSplatBlock)), dim3(kSplatBlock), 0, s, B.X, P.p, n, max_sq_distance, D.p,
+                     closest_triangle ? I.p : nullptr);
+  E3D_HIP(hipGetLastError());
+  copy_out(sq_distance, D.p, sizeof(float) * n, s);
+  if (closest_triangle) copy_out(closest_triangle, I.p, sizeof(int) * n, s);
+  E3D_HIP(hipStreamSynchronize(s));
+  return 0;
+  E3D_CATCH()
 }
 
 extern "C" int64_t e3d_create_splats(const float* xyz, const float* normals, size_t n, const float* vertices, size_t n_vertices,
                                      const uint32_t* triangles, size_t n_triangles, float distance_threshold, float max_splat_size,
                                      float* splat_vertices, size_t capacity, uint8_t* add_splat, float* splat_radius,
                                      float* timings_ms) {
-  try {
-    if ((!xyz && n) || (!normals && n)) throw Error(E3D_ERR_INVALID, "e3d_create_splats: null argument");
-    if (!splat_vertices && capacity) throw Error(E3D_ERR_INVALID, "e3d_create_splats: capacity without splat_vertices");
-    check_mesh_args("e3d_create_splats", vertices, n_vertices, triangles, n_triangles);
-    if (n >= ((size_t)1 << 31)) throw Error(E3D_ERR_INVALID, "e3d_create_splats: more than 2^31-1 points");
-    require_gpu();
-    // the points on the host: non-finite ones are neither searched nor splatted (compacted out, as e3d_local_outlier_removal does)
-    std::vector<float> hx(3 * n);
-    if (n) E3D_HIP(hipMemcpy(hx.data(), xyz, sizeof(float) * 3 * n, hipMemcpyDefault));
-    std::vector<float> finite;
-    std::vector<unsigned> origin;
-    bool all_finite = true;
-    for (size_t i = 0; i < n && all_finite; ++i) all_finite = std::isfinite(hx[3 * i]) && std::isfinite(hx[3 * i + 1]) && std::isfinite(hx[3 * i + 2]);
-    const float* pts = hx.data();
-    size_t m = n;
-    if (!all_finite) {
-      for (size_t i = 0; i < n; ++i)
-        if (std::isfinite(hx[3 * i]) && std::isfinite(hx[3 * i + 1]) && std::isfinite(hx[3 * i + 2])) {
-          finite.insert(finite.end(), &hx[3 * i], &hx[3 * i] + 3);
-          origin.push_back((unsigned)i);
-        }
-      pts = finite.data(); m = origin.size();
-    }
-    // the reference CHECKs that the k = 5 search returns 5 points (splat_creator.cc:161-163)
-    if (m < 5) throw Error(E3D_ERR_INVALID, fmt("e3d_create_splats: %zu finite points, the splat radius needs at least 5", m));
-    const float thr2 = distance_threshold * distance_threshold;
-    int64_t count = 0;
-    knn_kth_sqdist(pts, m, 5, [&](const float* kth, const float4* order, hipStream_t s) {
-      EventTimer t_index, t_splat;
-      t_index.start(s);
-      MeshIndexBuffers B;
-      build_mesh_index(B, vertices, n_vertices, triangles, n_triangles, s);
-      t_index.stop(s);
-      t_splat.start(s);
-      DevBuf<float> X, N, R, out;
-      DevBuf<unsigned char> F;
-      DevBuf<unsigned> O, off;
-      DevBuf<char> temp;
-      X.reserve(3 * n); N.reserve(3 * n); R.reserve(n); F.reserve(n); off.reserve(n);
-      copy_in(X.p, hx.data(), sizeof(float) * 3 * n, s);
-      copy_in(N.p, normals, sizeof(float) * 3 * n, s);
-      if (!all_finite) { O.reserve(m); copy_in(O.p, origin.data(), sizeof(unsigned) * m, s); }
-      hipLaunchKernelGGL(k_fill_splat_outputs, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, n, F.p, R.p);
-      hipLaunchKernelGGL(k_splat_flags, dim3((unsigned)div_up(m, kSplatBlock)), dim3(kSplatBlock), 0, s, B.X, order, kth,
-                         all_finite ? nullptr : O.p, m, N.p, thr2, max_splat_size, F.p, R.p);
-      E3D_HIP(hipGetLastError());
-      exclusive_sum_u8_u32(F.p, off.p, n, temp, s);
-      unsigned last_off = 0;
-      unsigned char last_flag = 0;
-      E3D_HIP(hipMemcpyAsync(&last_off, off.p + (n - 1), sizeof last_off, hipMemcpyDeviceToHost, s));
-      E3D_HIP(hipMemcpyAsync(&last_flag, F.p + (n - 1), 1, hipMemcpyDeviceToHost, s));
-      E3D_HIP(hipStreamSynchronize(s));
-      count = (int64_t)last_off + last_flag;
-      const size_t n_write = std::min((size_t)count, capacity);
-      if (n_write) {
-        out.reserve(12 * n_write);
-        hipLaunchKernelGGL(k_splat_write, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, X.p, N.p, n, F.p, R.p, off.p, n_write, out.p);
-        E3D_HIP(hipGetLastError());
-        copy_out(splat_vertices, out.p, sizeof(float) * 12 * n_write, s);
+  E3D_TRY
+  if ((!xyz && n) || (!normals && n)) throw Error(E3D_ERR_INVALID, "e3d_create_splats: null argument");
+  if (!splat_vertices && capacity) throw Error(E3D_ERR_INVALID, "e3d_create_splats: capacity without splat_vertices");
+  check_mesh_args("e3d_create_splats", vertices, n_vertices, triangles, n_triangles);
+  if (n >= ((size_t)1 << 31)) throw Error(E3D_ERR_INVALID, "e3d_create_splats: more than 2^31-1 points");
+  require_device();
+  // the points on the host: non-finite ones are neither searched nor splatted (compacted out, as e3d_local_outlier_removal does)
+  std::vector<float> hx(3 * n);
+  if (n) E3D_HIP(hipMemcpy(hx.data(), xyz, sizeof(float) * 3 * n, hipMemcpyDefault));
+  std::vector<float> finite;
+  std::vector<unsigned> origin;
+  bool all_finite = true;
+  for (size_t i = 0; i < n && all_finite; ++i) all_finite = std::isfinite(hx[3 * i]) && std::isfinite(hx[3 * i + 1]) && std::isfinite(hx[3 * i + 2]);
+  const float* pts = hx.data();
+  size_t m = n;
+  if (!all_finite) {
+    for (size_t i = 0; i < n; ++i)
+      if (std::isfinite(hx[3 * i]) && std::isfinite(hx[3 * i + 1]) && std::isfinite(hx[3 * i + 2])) {
+        finite.insert(finite.end(), &hx[3 * i], &hx[3 * i] + 3);
+        origin.push_back((unsigned)i);
       }
-      t_splat.stop(s);
-      if (add_splat) copy_out(add_splat, F.p, n, s);
-      if (splat_radius) copy_out(splat_radius, R.p, sizeof(float) * n, s);
-      E3D_HIP(hipStreamSynchronize(s));
-      if (timings_ms) { timings_ms[0] = t_index.ms(); timings_ms[1] = t_splat.ms(); }
-    });
-    return count;
-  } catch (const e3d::Error& e) {
-    e3d::set_last_error(e.what());
-    return e.code;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    return E3D_ERR_INVALID;
+    pts = finite.data(); m = origin.size();
   }
+  // the reference CHECKs that the k = 5 search returns 5 points (splat_creator.cc:161-163)
+  if (m < 5) throw Error(E3D_ERR_INVALID, fmt("e3d_create_splats: %zu finite points, the splat radius needs at least 5", m));
+  const float thr2 = distance_threshold * distance_threshold;
+  int64_t count = 0;
+  knn_kth_sqdist(pts, m, 5, [&](const float* kth, const float4* order, hipStream_t s) {
+    EventTimer t_index, t_splat;
+    t_index.start(s);
+    MeshIndexBuffers B;
+    build_mesh_index(B, vertices, n_vertices, triangles, n_triangles, s);
+    t_index.stop(s);
+    t_splat.start(s);
+    DevBuf<float> X, N, R, out;
+    DevBuf<unsigned char> F;
+    DevBuf<unsigned> O, off;
+    DevBuf<char> temp;
+    X.reserve(3 * n); N.reserve(3 * n); R.reserve(n); F.reserve(n); off.reserve(n);
+    copy_in(X.p, hx.data(), sizeof(float) * 3 * n, s);
+    copy_in(N.p, normals, sizeof(float) * 3 * n, s);
+    if (!all_finite) { O.reserve(m); copy_in(O.p, origin.data(), sizeof(unsigned) * m, s); }
+    hipLaunchKernelGGL(k_fill_splat_outputs, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, n, F.p, R.p);
+    hipLaunchKernelGGL(k_splat_flags, dim3((unsigned)div_up(m, kSplatBlock)), dim3(kSplatBlock), 0, s, B.X, order, kth,
+                       all_finite ? nullptr : O.p, m, N.p, thr2, max_splat_size, F.p, R.p);
+    E3D_HIP(hipGetLastError());
+    count = (int64_t)compaction_offsets(F.p, n, off, temp, s);
+    const size_t n_write = std::min((size_t)count, capacity);
+    if (n_write) {
+      out.reserve(12 * n_write);
+      hipLaunchKernelGGL(k_splat_write, dim3((unsigned)div_up(n, 256)), dim3(256), 0, s, X.p, N.p, n, F.p, R.p, off.p, n_write, out.p);
+      E3D_HIP(hipGetLastError());
+      copy_out(splat_vertices, out.p, sizeof(float) * 12 * n_write, s);
+    }
+    t_splat.stop(s);
+    if (add_splat) copy_out(add_splat, F.p, n, s);
+    if (splat_radius) copy_out(splat_radius, R.p, sizeof(float) * n, s);
+    E3D_HIP(hipStreamSynchronize(s));
+    if (timings_ms) { timings_ms[0] = t_index.ms(); timings_ms[1] = t_splat.ms(); }
+  });
+  return count;
+  E3D_CATCH()
 }

@@ -452,31 +452,6 @@ struct e3d_surface {
 
 namespace {
 
-struct SurfRun {
-  hipStream_t s = nullptr;
-  DevBuf<char> temp;
-  DevBuf<unsigned char> flags;
-  DevBuf<unsigned> offsets;
-  ~SurfRun() { if (s) (void)hipStreamDestroy(s); }
-
-  // exclusive offsets of n flags; the number set
-  size_t scan(const unsigned char* f, size_t n) { return compaction_offsets(f, n, offsets, temp, s); }
-  size_t scan(size_t n) { return scan(flags.p, n); }
-  // sorts keys[0, n) (into `sorted`) and leaves their unique values in `out`; the number of unique keys
-  size_t sort_unique(DevBuf<unsigned long long>& keys, DevBuf<unsigned long long>& sorted, DevBuf<unsigned long long>& out, size_t n, int end_bit) {
-    if (n == 0) return 0;
-    sorted.reserve(n);
-    sort_keys_u64(keys.p, sorted.p, n, end_bit, temp, s);
-    flags.reserve(n);
-    const unsigned nb = (unsigned)div_up(n, kSurfBlock);
-    launch_flag_run_starts(sorted.p, n, flags.p, s);
-    const size_t m = scan(n);
-    out.reserve(m);
-    hipLaunchKernelGGL(k_surf_scatter_keys, dim3(nb), dim3(kSurfBlock), 0, s, sorted.p, flags.p, offsets.p, n, out.p);
-    return m;
-  }
-};
-
 // The operation list checked on the host: the operations as the kernels read them (16 doubles each: kind, centre, rotation, half
 // extents) and the lattice bounding box of every solid's band |g| <= 2 h (corner coordinates, one step of margin each side).
 struct SurfSolids {
@@ -537,16 +512,18 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   SurfSolids solids;
   check_solids(solids, ops, n_ops, h);
   if (n_ops) out.groups = kSurfMaxGroups;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) throw Error(E3D_ERR_NO_DEVICE, "no HIP device visible (libe3dhip needs an MI355X / gfx950 GPU)");
+  require_device();
   // without a union nothing can be defined where no point counts: subtracting from nothing gives nothing
   if (n == 0 && !solids.any_union) return;
 
-  SurfRun run;
-  E3D_HIP(hipStreamCreateWithFlags(&run.s, hipStreamNonBlocking));
-  hipStream_t s = run.s;
+  OwnedStream stream;
+  hipStream_t s = stream.s;
+  Compactor run(s);
   EventTimer timer[kSurfGroups];
   const auto blocks = [](size_t m) { return dim3((unsigned)div_up(m, kSurfBlock)); };
+  const auto scatter_keys = [&](const unsigned long long* sorted, size_t count, unsigned long long* unique) {
+    hipLaunchKernelGGL(k_surf_scatter_keys, blocks(count), dim3(kSurfBlock), 0, s, sorted, run.flags.p, run.offsets.p, count, unique);
+  };
   const size_t kMaxItems = ((size_t)1 << 32) - 64;        // the compactions use 32-bit offsets
 
   // ---- grid ----------------------------------------------------------------------------------------------------------------------
@@ -594,35 +571,24 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   DevBuf<unsigned long long> ka, kb, vk;
   DevBuf<unsigned> va, vb, counter;
   DevBuf<float4> P4, N4;
-  unsigned n_grid_cells = 0;
+  DevBuf<HashEntry> table;
   P4.reserve(m); N4.reserve(m);
   if (m) {
-    ka.reserve(n); kb.reserve(n); vk.reserve(n); va.reserve(n); vb.reserve(n); counter.reserve(2);
+    ka.reserve(n); kb.reserve(n); vk.reserve(n); va.reserve(n); vb.reserve(n);
     hipLaunchKernelGGL(k_surf_point_keys, blocks(n), dim3(kSurfBlock), 0, s, d_xyz.p, d_nrm.p, n, P, ka.p, va.p, vk.p);
-    sort_pairs_u64_u32(ka.p, kb.p, va.p, vb.p, n, 64, run.temp, s);
-    launch_permute(d_xyz.p, d_nrm.p, vb.p, m, P4.p, N4.p, s);
-    E3D_HIP(hipMemsetAsync(counter.p, 0, 2 * sizeof(unsigned), s));
-    launch_count_cells(kb.p, m, counter.p, s);
-    copy_out(&n_grid_cells, counter.p, sizeof(unsigned), s);
-    E3D_HIP(hipStreamSynchronize(s));
   }
-  size_t tsize = 64;
-  while (tsize < 2 * (size_t)n_grid_cells) tsize <<= 1;
-  DevBuf<HashEntry> table;
-  table.reserve(tsize);
-  P.mask = (unsigned)(tsize - 1);
-  E3D_HIP(hipMemsetAsync(table.p, 0xFF, sizeof(HashEntry) * tsize, s));
-  if (m) launch_build_table(kb.p, m, table.p, P.mask, s);
+  const CellTable grid = sort_into_cells(ka.p, kb.p, va.p, vb.p, n, m, 64, d_xyz.p, d_nrm.p, P4, &N4, run.temp, counter, table, s);
+  const size_t n_grid_cells = grid.n_cells;
+  P.mask = grid.mask;
   timer[0].stop(s);
 
   // ---- solids: the bricks of the union solids' bands ---------------------------------------------------------------------------------
-  std::unique_ptr<EventTimer> solid_timer[2];
+  GroupTimer solid_timer;
   DevBuf<double> d_ops;
   DevBuf<SurfSolidBox> d_boxes;
   DevBuf<unsigned long long> solid_keys;
   size_t n_solid_keys = 0;
   if (n_ops) {
-    solid_timer[0].reset(new EventTimer); solid_timer[1].reset(new EventTimer);
     d_ops.reserve(solids.ops.size());
     copy_in(d_ops.p, solids.ops.data(), sizeof(double) * solids.ops.size(), s);
     std::vector<SurfSolidBox> boxes;
@@ -641,7 +607,7 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
       if (total > kMaxItems) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_csg: the solids up to operation %zu cover too many bricks for one call", o));
       boxes.push_back(B);
     }
-    solid_timer[0]->start(s);
+    solid_timer.start(s);
     if (total) {
       d_boxes.reserve(boxes.size());
       copy_in(d_boxes.p, boxes.data(), sizeof(SurfSolidBox) * boxes.size(), s);
@@ -655,7 +621,7 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
         hipLaunchKernelGGL(k_surf_solid_brick_keys, blocks(total), dim3(kSurfBlock), 0, s, d_boxes.p, (int)boxes.size(), d_ops.p, total, P, thr, run.flags.p,
                            run.offsets.p, solid_keys.p);
     }
-    solid_timer[0]->stop(s);
+    solid_timer.stop(s);
     E3D_HIP(hipStreamSynchronize(s));                                    // `boxes` is read by the copy above
   }
 
@@ -665,7 +631,7 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   size_t n_voxels = 0;
   if (m) {
     // (the sort moves the keys of the points that do not contribute, kEmptyKey, behind the m others only with all 64 bits)
-    const size_t n_sorted_voxels = run.sort_unique(vk, ka, voxels, n, 64);
+    const size_t n_sorted_voxels = run.sort_unique(vk, ka, voxels, n, 64, scatter_keys);
     n_voxels = n_sorted_voxels - (m < n ? 1 : 0);                      // kEmptyKey is the last unique key if any point was dropped
   }
   const int M = ((2 * P.D + 4) >> 2) + 1;
@@ -675,7 +641,7 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   kb.reserve(n_brick_keys + n_solid_keys);
   if (n_brick_keys) hipLaunchKernelGGL(k_surf_brick_keys, blocks(n_brick_keys), dim3(kSurfBlock), 0, s, voxels.p, n_voxels, P.D, M, kb.p);
   if (n_solid_keys) E3D_HIP(hipMemcpyAsync(kb.p + n_brick_keys, solid_keys.p, sizeof(unsigned long long) * n_solid_keys, hipMemcpyDeviceToDevice, s));
-  const size_t n_bricks = run.sort_unique(kb, ka, bricks, n_brick_keys + n_solid_keys, key_bits);
+  const size_t n_bricks = run.sort_unique(kb, ka, bricks, n_brick_keys + n_solid_keys, key_bits, scatter_keys);
   timer[1].stop(s);
   const size_t n_slots = n_bricks * 64;
   if (n_slots > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many candidate corners for one call");
@@ -694,10 +660,10 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   DevBuf<unsigned char> defined;
   defined.reserve(n_slots);
   if (n_ops) {
-    solid_timer[1]->start(s);
+    solid_timer.start(s);
     hipLaunchKernelGGL(k_surf_apply_solids, blocks(n_slots), dim3(kSurfBlock), sizeof(double) * 16 * n_ops, s, bricks.p, n_slots, d_ops.p, (int)n_ops, P, count.p,
                        f.p, defined.p);
-    solid_timer[1]->stop(s);
+    solid_timer.stop(s);
     E3D_HIP(hipGetLastError());
   }
 
@@ -742,7 +708,7 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
     if (4 * n_edges > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many crossing edges for one call");
     edges.reserve(n_edges); kb.reserve(4 * n_edges);
     hipLaunchKernelGGL(k_surf_edges, blocks(3 * n_corners), dim3(kSurfBlock), 0, s, ck.p, run.flags.p, run.offsets.p, 3 * n_corners, edges.p, kb.p);
-    n_cells = run.sort_unique(kb, ka, cells, 4 * n_edges, key_bits);
+    n_cells = run.sort_unique(kb, ka, cells, 4 * n_edges, key_bits, scatter_keys);
     vertices.reserve(3 * n_cells); cell_ijk.reserve(3 * n_cells); tri.reserve(6 * n_edges);
     hipLaunchKernelGGL(k_surf_vertices, blocks(n_cells), dim3(kSurfBlock), 0, s, cells.p, n_cells, P, F, vertices.p, cell_ijk.p);
     hipLaunchKernelGGL(k_surf_triangles, blocks(n_edges), dim3(kSurfBlock), 0, s, edges.p, n_edges, ck.p, cs.p, f.p, cells.p, n_cells, tri.p);
@@ -755,11 +721,11 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   E3D_HIP(hipStreamSynchronize(s));
   E3D_HIP(hipGetLastError());
   for (int g = 0; g < kSurfGroups; ++g) out.ms[g] = timer[g].ms();
-  if (n_ops) out.ms[kSurfGroups] = solid_timer[0]->ms() + solid_timer[1]->ms();
+  if (n_ops) out.ms[kSurfGroups] = solid_timer.ms();
   static const bool trace = env_default_off("E3D_SURFACE_TRACE");
   if (trace)
     fprintf(stderr, "[surface] %zu points, %zu contribute, %zu voxels, %zu bricks (%zu candidate corners), %zu grid cells, %zu corners, %zu crossing edges, %zu vertices, %zu operations, %zu bricks of solids\n",
-            n, m, n_voxels, n_bricks, n_slots, (size_t)n_grid_cells, n_corners, n_edges, n_cells, n_ops, n_solid_keys);
+            n, m, n_voxels, n_bricks, n_slots, n_grid_cells, n_corners, n_edges, n_cells, n_ops, n_solid_keys);
 }
 
 }  // namespace
@@ -768,29 +734,21 @@ extern "C" {
 
 e3d_surface_t* e3d_surface_reconstruct(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius) {
   e3d_surface* h = nullptr;
-  try {
-    h = new e3d_surface;
-    reconstruct(*h, xyz, normals, n, voxel_size, support_radius, nullptr, 0);
-    return h;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    delete h;
-    return nullptr;
-  }
+  E3D_TRY
+  h = new e3d_surface;
+  reconstruct(*h, xyz, normals, n, voxel_size, support_radius, nullptr, 0);
+  return h;
+  E3D_CATCH_NEW(h)
 }
 
 e3d_surface_t* e3d_surface_reconstruct_csg(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius,
                                            const e3d_surface_solid_t* ops, size_t n_ops) {
   e3d_surface* h = nullptr;
-  try {
-    h = new e3d_surface;
-    reconstruct(*h, xyz, normals, n, voxel_size, support_radius, ops, n_ops);
-    return h;
-  } catch (const std::exception& e) {
-    e3d::set_last_error(e.what());
-    delete h;
-    return nullptr;
-  }
+  E3D_TRY
+  h = new e3d_surface;
+  reconstruct(*h, xyz, normals, n, voxel_size, support_radius, ops, n_ops);
+  return h;
+  E3D_CATCH_NEW(h)
 }
 
 void e3d_surface_destroy(e3d_surface_t* h) { delete h; }

@@ -176,7 +176,53 @@ def scans16_case(all_15=False):
     return (dist, 16, P, rng.uniform(0, 255, 3000).astype(F), sidx, rng.uniform(0.001, 0.1, 3000).astype(F))
 
 
+def grid_cells(dist, P):
+    """The integer cell of every point of P in the hashed grid e3d_merge_close_points builds (csrc/e3d_multires.hip: cell size and
+    origin in f64 from the f32 bounding box; cell_coord of csrc/e3d_kernels.hpp: floor((v - origin) * inv_cell) in f32), restated
+    operation by operation."""
+    P = np.ascontiguousarray(P, F).reshape(-1, 3)
+    lo, hi = P.min(0).astype(np.float64), P.max(0).astype(np.float64)
+    md = float(F(dist))
+    cell = md * (1.0 + 1e-4) + 16.0 * 2.0 ** -23 * (max(np.abs(lo).max(), np.abs(hi).max()) + 4.0 * md)
+    while (hi - lo).max() / cell > (1 << 21) - 8:
+        cell *= 2.0
+    origin, inv_cell = (lo - 2.0 * cell).astype(F), F(1.0 / cell)
+    return np.floor((P - origin) * inv_cell).astype(np.int64)
+
+
+# occupied grid cells at which twice their number meets and crosses a power of two, the 64-slot floor of the hash table included
+CELL_COUNTS = (1, 32, 33, 64, 65, 1024, 1025)
+
+
+def cells_case(C):
+    """C pairs, each alone in a grid cell of its own: the first C sites (x fastest) of a cubic lattice of pitch 3.35 cells (about 3.35
+    merge distances: no two pairs interact), and dist / 16 further along x each site's partner -- the partner of point j is point
+    C + j, decided in another wave or block.  3.35: the sites of the first eleven columns lie between 0.05 and 0.8 of a cell behind
+    a cell boundary, the partner 0.06 further on.  Only the first column sits ON a boundary (the grid's origin is the bounding box's
+    minimum less two cells), on whichever side the rounding puts it; the cloud is moved by eighths until grid_cells puts every pair
+    in one cell.  Integer colours, max_radius in eighths, 3 scans: with two points per centre every sum is the same in any order."""
+    dist = 1.0 / 16
+    side = 1
+    while side ** 3 < C:
+        side += 1
+    k = np.arange(C)
+    site = np.stack([k % side, (k // side) % side, k // (side * side)], 1) * (3.35 * dist * (1.0 + 1e-4))
+    for eighths in range(64):
+        A = (site + eighths / 8.0).astype(F)
+        B = A.copy()
+        B[:, 0] += F(dist / 16)
+        cells = grid_cells(dist, np.concatenate([A, B]))
+        if np.array_equal(cells[:C], cells[C:]) and len(np.unique(cells[:C], axis=0)) == C:
+            break
+    else:
+        raise AssertionError("no placement with %d pairs in %d cells" % (C, C))
+    rng = np.random.RandomState(100 + C)
+    return (dist, 3, np.concatenate([A, B]), rng.randint(0, 256, 2 * C).astype(F), rng.randint(0, 3, 2 * C).astype(np.uint8),
+            (rng.randint(1, 64, 2 * C) / 8.0).astype(F))
+
+
 CASES = {"size_%d" % n: functools.partial(sizes_case, n) for n in SIZES}
+CASES.update({"cells_%d" % C: functools.partial(cells_case, C) for C in CELL_COUNTS})
 CASES.update({name: functools.partial(lattice_case, shift) for name, shift in LATTICE_SHIFTS.items()})
 CASES.update({"chain_" + o: functools.partial(chain_case, o) for o in ("increasing", "decreasing", "shuffled")})
 CASES.update({"dense": dense_case, "scans16": scans16_case, "scans16_all15": functools.partial(scans16_case, True)})

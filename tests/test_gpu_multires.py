@@ -121,6 +121,14 @@ def test_merge_lattice_exact(e3d, name):
     assert R["m"].max() <= 32                  # the sums stay exact
 
 
+@pytest.mark.parametrize("C", [1, 32, 33, 64, 65, 1024, 1025])
+def test_merge_hash_table_size_edges(e3d, C):
+    """exactly C occupied grid cells, a pair to merge in each (tests/test_multires_host.py proves it of the input): the table is the
+    smallest power of two >= 64 and >= 2 C, and at these C twice the count meets and crosses one, the 64-slot floor included"""
+    g, R = _check_against_restatement(e3d, "cells_%d" % C, exact=True)
+    assert len(g[0]) == C and (R["m"] == 2).all()
+
+
 def test_merge_lattice_far_from_the_origin(e3d):
     """the same sites around (2^17, -2^17, 2^17 - 3): the cell size is dominated by 16 FLT_EPSILON * magnitude, the sums round"""
     import multires_ref as ref

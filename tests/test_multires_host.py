@@ -132,6 +132,30 @@ def test_library_refuses_undefined_input_before_it_needs_a_device(e3d):
             e3d.merge_close_points(d, scans, P, col, sidx, mxr)
 
 
+@pytest.mark.parametrize("C", ref.CELL_COUNTS)
+def test_cell_count_cases_fill_exactly_C_cells_with_one_pair_each(C):
+    """the input does what it says: C occupied cells of the library's grid, two points less than the merge distance apart in each, the
+    pairs at least three merge distances from one another -- and the restatement alone merges them into exactly C points"""
+    dist, scans, P, col, sidx, mxr = ref.case("cells_%d" % C)
+    assert len(P) == 2 * C
+    cells = ref.grid_cells(dist, P)
+    assert np.array_equal(cells[:C], cells[C:]) and len(np.unique(cells, axis=0)) == C
+    within = np.sqrt(((P[:C].astype(np.float64) - P[C:]) ** 2).sum(1))
+    assert (within > 0).all() and (within < 0.1 * dist).all()
+    for i in range(2 * C):                                                      # every other pair: three merge distances away or more
+        d = np.sqrt(((P.astype(np.float64) - P[i]) ** 2).sum(1))
+        d[[i % C, C + i % C]] = np.inf
+        assert d.min() >= 3.0 * dist
+    R = ref.reference("cells_%d" % C)
+    assert len(R["m"]) == C and (R["m"] == 2).all() and np.array_equal(R["centre"], np.arange(C))
+    assert all(np.array_equal(nb, (i, C + i)) for i, nb in enumerate(R["nbrs"]))
+    # the hash table's size by the library's rule, and that the counts sit where 2 C meets and crosses it
+    tsize = 64
+    while tsize < 2 * C:
+        tsize <<= 1
+    assert tsize == {1: 64, 32: 64, 33: 128, 64: 128, 65: 256, 1024: 2048, 1025: 4096}[C]
+
+
 def test_chain_closed_form():
     R = ref.reference("chain_increasing")
     assert np.array_equal(R["centre"], np.arange(0, ref.CHAIN_N, 2))            # the even positions
