@@ -34,6 +34,12 @@ class UndistortPlan(C.Structure):
         return (self.width, self.height, self.fx, self.fy, self.cx, self.cy)
 
 
+class StereoPlan(C.Structure):
+    """e3d_stereo_plan: the common PINHOLE camera of a rectified pair, its baseline, the two rectified poses and source_T_rect rotations."""
+    _fields_ = [("camera", UndistortPlan), ("baseline", C.c_float), ("q_rect", C.c_float * 4), ("t_left", C.c_float * 3),
+                ("t_right", C.c_float * 3), ("S_left", C.c_float * 9), ("S_right", C.c_float * 9)]
+
+
 UNDISTORT_U8, UNDISTORT_RGB, UNDISTORT_MASK, UNDISTORT_NEAREST = 0, 1, 2, 3
 _UNDISTORT_PIXEL = {0: (np.uint8, ()), 1: (np.uint8, (3,)), 2: (np.uint8, ()), 3: (np.float32, ())}
 
@@ -152,6 +158,10 @@ SIGNATURES = {
     "e3d_reg_undistort_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_void_p]),
     "e3d_reg_undistort": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_undistort_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_reg_stereo_plan": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_int, C.c_double, C.c_void_p]),
+    "e3d_reg_stereo_rectify": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "e3d_reg_stereo_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_reg_stereo_ground_truth": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_pose_from_bearings": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_reg_set_cache_observations": (C.c_int, [C.c_void_p, C.c_int]),
     "e3d_reg_determine_observed_indices": (C.c_int, [C.c_void_p]),
@@ -1018,7 +1028,7 @@ class RegProblem:
         return sm.value, cn.value
 
     def set_image(self, image_id, intrinsics_id, levels, masks=None):
-        if levels is None:                       # an image owned by another rank: id, intrinsics and pose only
+        if levels is None:                       # an image without pixels (another rank's, or geometry only): id, intrinsics and pose
             self._chk(lib().e3d_reg_set_image(self._h, image_id, intrinsics_id, None, None), "e3d_reg_set_image")
             self._image_intr[image_id] = intrinsics_id
             return
@@ -1204,6 +1214,55 @@ class RegProblem:
         ms = C.c_float()
         self._chk(lib().e3d_reg_undistort_kernel_ms(self._h, C.byref(ms)), "e3d_reg_undistort_kernel_ms")
         return float(ms.value)
+
+    # ---- StereoPairCreator ------------------------------------------------------------------------------------------------------------
+    def stereo_plan(self, left_image_id, right_image_id, blank_pixels=0.0, max_image_size=-1, focal_length=0.0):
+        """The rectified camera, poses and rotations of a pair of images at their current poses (e3d_reg_stereo_plan) -> StereoPlan."""
+        plan = StereoPlan()
+        self._chk(lib().e3d_reg_stereo_plan(self._h, int(left_image_id), int(right_image_id), float(blank_pixels), int(max_image_size),
+                                            float(focal_length), C.byref(plan)), "e3d_reg_stereo_plan")
+        return plan
+
+    def stereo_rectify(self, intrinsics_id, target, S, kind, src, return_valid=False):
+        """undistort() with the ray of every output pixel rotated by S (9 float32, row-major source_T_rect) before the source model."""
+        kind = int(kind)
+        if kind not in _UNDISTORT_PIXEL:
+            raise E3DError("e3d_reg_stereo_rectify: unknown kind %d" % kind)
+        dtype, tail = _UNDISTORT_PIXEL[kind]
+        src = np.ascontiguousarray(src, dtype)
+        S = np.ascontiguousarray(S, np.float32).reshape(-1)
+        if S.shape != (9,):
+            raise E3DError("e3d_reg_stereo_rectify: S has %d entries, not 9" % S.size)
+        size = self._intr_size.get(int(intrinsics_id))
+        if size is not None and src.shape != size + tail:
+            raise E3DError("e3d_reg_stereo_rectify: the source is %s, the camera's level 0 %s" % (src.shape, size + tail))
+        out = np.zeros((max(int(target.height), 0), max(int(target.width), 0)) + tail, dtype)
+        valid = np.zeros(out.shape[:2], np.uint8) if return_valid else None
+        self._chk(lib().e3d_reg_stereo_rectify(self._h, int(intrinsics_id), C.byref(target), C.c_void_p(S.ctypes.data), kind,
+                                               C.c_void_p(src.ctypes.data), C.c_void_p(out.ctypes.data),
+                                               C.c_void_p(valid.ctypes.data) if return_valid else None), "e3d_reg_stereo_rectify")
+        return (out, valid) if return_valid else out
+
+    def stereo_kernel_ms(self):
+        """HIP-event time of the resampling kernel of the last stereo_rectify()."""
+        ms = C.c_float()
+        self._chk(lib().e3d_reg_stereo_kernel_ms(self._h, C.byref(ms)), "e3d_reg_stereo_kernel_ms")
+        return float(ms.value)
+
+    def stereo_ground_truth(self, left_image_id, right_image_id, left_excluded=None, right_excluded=None, return_depth=False):
+        """Disparity ground truth of the left of two rectified images (e3d_reg_stereo_ground_truth) -> (disparity float32, +inf =
+        unknown; mask uint8 255 / 128 / 0 [, depth float32]), all (height, width).  Leaves the scan observation counters holding the
+        counts over the two images."""
+        shape = self._level0_shape(int(left_image_id))
+        keep = []
+        le = self._mask_ptr(left_excluded, shape, keep, "left_excluded") if left_excluded is not None else None
+        re_ = self._mask_ptr(right_excluded, shape, keep, "right_excluded") if right_excluded is not None else None
+        disparity = np.zeros(shape, np.float32); nocc = np.zeros(shape, np.uint8)
+        depth = np.zeros(shape, np.float32) if return_depth else None
+        self._chk(lib().e3d_reg_stereo_ground_truth(self._h, int(left_image_id), int(right_image_id), le, re_, C.c_void_p(disparity.ctypes.data),
+                                                    C.c_void_p(nocc.ctypes.data), C.c_void_p(depth.ctypes.data) if return_depth else None),
+                  "e3d_reg_stereo_ground_truth")
+        return (disparity, nocc, depth) if return_depth else (disparity, nocc)
 
     @staticmethod
     def pose_from_bearings(points, bearings, q, t):

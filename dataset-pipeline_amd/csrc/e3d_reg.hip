@@ -2672,7 +2672,16 @@ int e3d_reg_set_image(e3d_reg_t* h, int image_id, int intrinsics_id, const uint8
     im.depth_scale = -1;
     return 0;
   }
-  if (!level_pixels) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!level_pixels) {
+    // an image without pixels: id, intrinsics and pose serve the calls that ask about geometry only (occlusion depth, scan
+    // visibility, the stereo plan and ground truth); the calls that read intensities refuse it
+    if (level_masks) throw Error(E3D_ERR_INVALID, "masks without pixels");
+    ImageDev& im = h->images[image_id];
+    im.intrinsics_id = intrinsics_id;
+    im.pix.clear(); im.mask.clear(); im.has_mask.clear(); im.obs.clear();
+    im.depth_scale = -1;
+    return 0;
+  }
   ImageDev& im = h->images[image_id];
   im.intrinsics_id = intrinsics_id;
   const int L = (int)in.levels.size();
@@ -3052,6 +3061,7 @@ int e3d_reg_point_radius_minmax(e3d_reg_t* h, const float* xyz, size_t n, float*
     if (!h->owns(kv.first)) continue;
     ImageDev& im = kv.second;
     const Intrin& in = h->intr.at(im.intrinsics_id);
+    if (im.pix.size() != in.levels.size()) throw Error(E3D_ERR_INVALID, fmt("image %d was set without pixels", kv.first));
     const int scale = best_available_scale(h, in);
     render_depth(h, kv.first, scale, nullptr);
     const int lvl = std::max(0, scale - in.min_image_scale);

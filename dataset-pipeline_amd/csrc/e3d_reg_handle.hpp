@@ -132,6 +132,13 @@ struct ScanTools {
   DevBuf<unsigned char> undistort_src, undistort_dst, undistort_valid;
   std::unique_ptr<EventTimer> t_undistort;
   float undistort_ms = 0.f;
+  // StereoPairCreator: e3d_reg_stereo_rectify stages through the undistorter's buffers and has a timer of its own;
+  // e3d_reg_stereo_ground_truth keeps the depth of the nearest point seen by both images, the disparity and the mask
+  std::unique_ptr<EventTimer> t_stereo;
+  float stereo_ms = 0.f;
+  DevBuf<unsigned> stereo_d2;
+  DevBuf<float> stereo_disparity;
+  DevBuf<unsigned char> stereo_nocc;
 };
 
 }  // namespace e3d

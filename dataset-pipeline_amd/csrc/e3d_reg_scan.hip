@@ -395,6 +395,14 @@ int e3d_reg_set_scan_points(e3d_reg_t* h, const float* xyz, size_t n) {
   return 0;
   E3D_CATCH()
 }
+// one k_scan_visibility launch against im.depth as it stands (mask_dev: device, may be null; gt_depth: the map of modes 1 and 2)
+static void launch_scan_visibility(e3d_reg* h, ImageDev& im, const Intrin& in, const unsigned char* mask_dev, int excluded_flag, int mode,
+                                   int min_count, unsigned* gt_depth, int radius = 0) {
+  if (h->scan.n_scan)
+    E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_scan_visibility<M>, dim3(nblk(h->scan.n_scan)), dim3(kBlock), 0, h->stream, h->scan.scan_pts.p,
+                                               h->scan.n_scan, im.pose, in.levels[0], im.depth.p, h->prm.occlusion_depth_threshold, mask_dev,
+                                               excluded_flag, mode, min_count, h->scan.scan_counts.p, gt_depth, radius));
+}
 static void scan_visibility(e3d_reg* h, int image_id, const uint8_t* mask, int excluded_flag, int mode, int min_count, int radius = 0) {
   ImageDev& im = get_image(h, image_id);
   const Intrin& in = h->intr.at(im.intrinsics_id);
@@ -403,11 +411,7 @@ static void scan_visibility(e3d_reg* h, int image_id, const uint8_t* mask, int e
   const CamLevel& cam = in.levels[0];
   const size_t px = (size_t)cam.width * cam.height;
   if (mask) { h->scan.eval_mask.reserve(px); copy_in(h->scan.eval_mask.p, mask, px, h->stream); }
-  if (h->scan.n_scan)
-    E3D_CAM_SWITCH(in.type, hipLaunchKernelGGL(k_scan_visibility<M>, dim3(nblk(h->scan.n_scan)), dim3(kBlock), 0, h->stream, h->scan.scan_pts.p,
-                                               h->scan.n_scan, im.pose, cam, im.depth.p, h->prm.occlusion_depth_threshold,
-                                               mask ? h->scan.eval_mask.p : nullptr, excluded_flag, mode, min_count, h->scan.scan_counts.p,
-                                               h->scan.gt_depth.p, radius));
+  launch_scan_visibility(h, im, in, mask ? h->scan.eval_mask.p : nullptr, excluded_flag, mode, min_count, h->scan.gt_depth.p, radius);
 }
 int e3d_reg_count_scan_observations(e3d_reg_t* h, int image_id, const uint8_t* mask, int excluded_flag) {
   E3D_TRY_ON(h)
@@ -635,14 +639,11 @@ static const Intrin& undistort_intrinsics(e3d_reg* h, int intrinsics_id) {
   return it->second;
 }
 
-int e3d_reg_undistort_plan(e3d_reg_t* h, int intrinsics_id, double blank_pixels, int max_image_size, e3d_undistort_plan* out) {
-  E3D_TRY_ON(h)
-  if (!h || !out) throw Error(E3D_ERR_INVALID, "null argument");
-  if (!(blank_pixels >= 0.0 && blank_pixels <= 1.0)) throw Error(E3D_ERR_INVALID, fmt("blank_pixels = %g is outside [0, 1]", blank_pixels));
-  const Intrin& in = undistort_intrinsics(h, intrinsics_id);
+// the border samples of a level-0 model: ImageToNormalized of the pixel centres (0, y), (W - 1, y) of every row, then (x, 0), (x, H - 1)
+// of every column, in that order (2 H + 2 W values)
+static std::vector<float2> undistort_border_samples(e3d_reg* h, const Intrin& in) {
   const CamLevel& cam = in.levels[0];
   const int W = cam.width, H = cam.height, n = 2 * W + 2 * H;
-  // border samples: the pixel centres (0, y), (W - 1, y) of every row, then (x, 0), (x, H - 1) of every column
   std::vector<float2> px((size_t)n);
   for (int y = 0; y < H; ++y) { px[2 * y] = make_float2(0.f, (float)y); px[2 * y + 1] = make_float2((float)(W - 1), (float)y); }
   for (int x = 0; x < W; ++x) { px[2 * H + 2 * x] = make_float2((float)x, 0.f); px[2 * H + 2 * x + 1] = make_float2((float)x, (float)(H - 1)); }
@@ -654,12 +655,22 @@ int e3d_reg_undistort_plan(e3d_reg_t* h, int intrinsics_id, double blank_pixels,
   copy_out(nxy.data(), h->scan.undistort_border.p + n, sizeof(float2) * n, h->stream);
   rsync(h);
   E3D_HIP(hipGetLastError());
+  return nxy;
+}
+// ... dealt out to the four sides {left, right, top, bottom} (appended: the stereo plan unites two cameras' samples)
+static void undistort_append_sides(const std::vector<float2>& nxy, int W, int H, std::vector<float2> sides[4]) {
+  for (int y = 0; y < H; ++y) { sides[0].push_back(nxy[2 * (size_t)y]); sides[1].push_back(nxy[2 * (size_t)y + 1]); }
+  for (int x = 0; x < W; ++x) { sides[2].push_back(nxy[2 * (size_t)H + 2 * x]); sides[3].push_back(nxy[2 * (size_t)H + 2 * x + 1]); }
+}
+
+// the plan rule from the samples of the four sides and the focal lengths (include/e3d_hip.h, e3d_reg_undistort_plan)
+static void undistort_plan_from_sides(const std::vector<float2> sides[4], float cam_fx, float cam_fy, double blank_pixels, int max_image_size,
+                                      e3d_undistort_plan* out) {
   // per side: inner and outer extent of one coordinate of its samples
   struct Side { double in, out; int count = 0; };
-  auto extent = [&](int first, int step, int count, bool x_coordinate, bool low_side) {
+  auto extent = [&](const std::vector<float2>& samples, bool x_coordinate, bool low_side) {
     Side s{low_side ? -INFINITY : INFINITY, low_side ? INFINITY : -INFINITY};
-    for (int i = 0; i < count; ++i) {
-      const float2 v = nxy[first + (size_t)step * i];
+    for (const float2 v : samples) {
       if (!std::isfinite(v.x) || !std::isfinite(v.y)) {
         if (blank_pixels > 0.0)
           throw Error(E3D_ERR_INVALID, "a border pixel has no finite undistorted position (beyond the model's radius cut-off): "
@@ -674,20 +685,20 @@ int e3d_reg_undistort_plan(e3d_reg_t* h, int intrinsics_id, double blank_pixels,
     if (!s.count) throw Error(E3D_ERR_INVALID, "no border pixel of one image side has a finite undistorted position");
     return s;
   };
-  const Side L = extent(0, 2, H, true, true), R = extent(1, 2, H, true, false);
-  const Side T = extent(2 * H, 2, W, false, true), B = extent(2 * H + 1, 2, W, false, false);
+  const Side L = extent(sides[0], true, true), R = extent(sides[1], true, false);
+  const Side T = extent(sides[2], false, true), B = extent(sides[3], false, false);
   const double b = blank_pixels;
   const double nL = b * L.out + (1.0 - b) * L.in, nR = b * R.out + (1.0 - b) * R.in;
   const double nT = b * T.out + (1.0 - b) * T.in, nB = b * B.out + (1.0 - b) * B.in;
   if (!(nL < nR) || !(nT < nB)) throw Error(E3D_ERR_INVALID, "the undistorted image is empty: its left / top extent is not below its right / bottom one");
   // a blended bound may lie up to b pixels outside its extent (the outer bounds are rounded outwards): 2 b pixels of margin
   double s = 1.0;
-  const double extent_px = std::max((double)cam.fx * (nR - nL), (double)cam.fy * (nB - nT)), margin = 1.0 + 2.0 * b;
+  const double extent_px = std::max((double)cam_fx * (nR - nL), (double)cam_fy * (nB - nT)), margin = 1.0 + 2.0 * b;
   if (max_image_size > 0 && extent_px + margin > (double)max_image_size) {
     s = ((double)max_image_size - margin) / extent_px;
     if (!(s > 0.0)) throw Error(E3D_ERR_INVALID, fmt("max_image_size = %d leaves no room for an image", max_image_size));
   }
-  const float fx = (float)(s * (double)cam.fx), fy = (float)(s * (double)cam.fy);
+  const float fx = (float)(s * (double)cam_fx), fy = (float)(s * (double)cam_fy);
   // inner bounds rounded inwards, outer bounds outwards, blended as integers
   auto low_bound = [&](double f, const Side& e) { return std::ceil(b * std::floor(f * e.out) + (1.0 - b) * std::ceil(f * e.in)); };
   auto high_bound = [&](double f, const Side& e) { return std::floor(b * std::ceil(f * e.out) + (1.0 - b) * std::floor(f * e.in)); };
@@ -700,34 +711,60 @@ int e3d_reg_undistort_plan(e3d_reg_t* h, int intrinsics_id, double blank_pixels,
     throw Error(E3D_ERR_INVALID, "the undistorted image would be larger than 2^24 pixels a side");
   out->width = (int32_t)Wd; out->height = (int32_t)Hd;
   out->fx = fx; out->fy = fy; out->cx = (float)(-x0); out->cy = (float)(-y0);
+}
+
+int e3d_reg_undistort_plan(e3d_reg_t* h, int intrinsics_id, double blank_pixels, int max_image_size, e3d_undistort_plan* out) {
+  E3D_TRY_ON(h)
+  if (!h || !out) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!(blank_pixels >= 0.0 && blank_pixels <= 1.0)) throw Error(E3D_ERR_INVALID, fmt("blank_pixels = %g is outside [0, 1]", blank_pixels));
+  const Intrin& in = undistort_intrinsics(h, intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  std::vector<float2> sides[4];
+  undistort_append_sides(undistort_border_samples(h, in), cam.width, cam.height, sides);
+  undistort_plan_from_sides(sides, cam.fx, cam.fy, blank_pixels, max_image_size, out);
   return 0;
   E3D_CATCH()
 }
 
-int e3d_reg_undistort(e3d_reg_t* h, int intrinsics_id, const e3d_undistort_plan* plan, int kind, const void* src, void* dst, uint8_t* valid_out) {
-  E3D_TRY_ON(h)
-  if (!h || !plan || !src || !dst) throw Error(E3D_ERR_INVALID, "null argument");
+// one image through a plan: e3d_reg_undistort (S null) and e3d_reg_stereo_rectify (S: the 9 entries of source_T_rect)
+static void undistort_resample(e3d_reg* h, int intrinsics_id, const e3d_undistort_plan* plan, const float* S, int kind, const void* src, void* dst,
+                               uint8_t* valid_out) {
   if (kind < 0 || kind >= kNumUndistortKinds) throw Error(E3D_ERR_INVALID, "unknown kind (0 = u8, 1 = u8 x 3, 2 = mask, 3 = f32 nearest)");
   const Intrin& in = undistort_intrinsics(h, intrinsics_id);
   const CamLevel& cam = in.levels[0];
   if (plan->width < 1 || plan->height < 1 || plan->width > (1 << 24) || plan->height > 65535 * 4 || !(plan->fx > 0.f) || !(plan->fy > 0.f) ||
       !std::isfinite(plan->fx) || !std::isfinite(plan->fy) || !std::isfinite(plan->cx) || !std::isfinite(plan->cy))
-    throw Error(E3D_ERR_INVALID, "bad plan (e3d_reg_undistort_plan fills it)");
+    throw Error(E3D_ERR_INVALID, S ? "bad plan (e3d_reg_stereo_plan fills it)" : "bad plan (e3d_reg_undistort_plan fills it)");
+  StereoRotation rotation{};
+  if (S)
+    for (int k = 0; k < 9; ++k) {
+      if (!std::isfinite(S[k])) throw Error(E3D_ERR_INVALID, "the rotation S has an entry that is not finite");
+      rotation.m[k] = S[k];
+    }
   const size_t px_bytes = undistort_pixel_bytes(kind);
   const size_t n_src = (size_t)cam.width * (size_t)cam.height, n_dst = (size_t)plan->width * (size_t)plan->height;
   h->scan.undistort_src.reserve(n_src * px_bytes); h->scan.undistort_dst.reserve(n_dst * px_bytes);
   if (valid_out) h->scan.undistort_valid.reserve(n_dst);
   copy_in(h->scan.undistort_src.p, src, n_src * px_bytes, h->stream);
-  if (!h->scan.t_undistort) h->scan.t_undistort.reset(new EventTimer());
+  std::unique_ptr<EventTimer>& timer = S ? h->scan.t_stereo : h->scan.t_undistort;
+  if (!timer) timer.reset(new EventTimer());
   const UndistortTarget target{plan->width, plan->height, plan->fx, plan->fy, plan->cx, plan->cy};
-  h->scan.t_undistort->start(h->stream);
-  undistort_launch(cam, target, kind, h->scan.undistort_src.p, h->scan.undistort_dst.p, valid_out ? h->scan.undistort_valid.p : nullptr, h->stream);
-  h->scan.t_undistort->stop(h->stream);
+  uint8_t* valid = valid_out ? h->scan.undistort_valid.p : nullptr;
+  timer->start(h->stream);
+  if (S) rectify_launch(cam, target, rotation, kind, h->scan.undistort_src.p, h->scan.undistort_dst.p, valid, h->stream);
+  else undistort_launch(cam, target, kind, h->scan.undistort_src.p, h->scan.undistort_dst.p, valid, h->stream);
+  timer->stop(h->stream);
   copy_out(dst, h->scan.undistort_dst.p, n_dst * px_bytes, h->stream);
   if (valid_out) copy_out(valid_out, h->scan.undistort_valid.p, n_dst, h->stream);
   rsync(h);
   E3D_HIP(hipGetLastError());
-  h->scan.undistort_ms = h->scan.t_undistort->ms();
+  (S ? h->scan.stereo_ms : h->scan.undistort_ms) = timer->ms();
+}
+
+int e3d_reg_undistort(e3d_reg_t* h, int intrinsics_id, const e3d_undistort_plan* plan, int kind, const void* src, void* dst, uint8_t* valid_out) {
+  E3D_TRY_ON(h)
+  if (!h || !plan || !src || !dst) throw Error(E3D_ERR_INVALID, "null argument");
+  undistort_resample(h, intrinsics_id, plan, nullptr, kind, src, dst, valid_out);
   return 0;
   E3D_CATCH()
 }
@@ -901,6 +938,158 @@ int e3d_pose_from_bearings(const double* points, const double* bearings, int n, 
   E3D_CATCH()
 }
 
+// ---- StereoPairCreator (include/e3d_hip.h states the three rules) -----------------------------------------------------------
+namespace {
+// image_T_global of an image in f64: the rotation of its renormalised quaternion, row-major, and the camera centre C = -R^T t
+struct StereoView { double R[9], C[3]; };
+StereoView stereo_view(const ImageDev& im) {
+  double w = im.pose_q.q.w, x = im.pose_q.q.x, y = im.pose_q.q.y, z = im.pose_q.q.z;
+  const double n = std::sqrt(w * w + x * x + y * y + z * z);
+  if (!(n > 0.0) || !std::isfinite(n)) throw Error(E3D_ERR_INVALID, "an image pose is not finite");
+  w /= n; x /= n; y /= n; z /= n;
+  StereoView v;
+  quat_to_matrix<double>(w, x, y, z, v.R);
+  const double t[3] = {im.pose_q.t[0], im.pose_q.t[1], im.pose_q.t[2]};
+  for (int k = 0; k < 3; ++k) v.C[k] = -(v.R[k] * t[0] + v.R[3 + k] * t[1] + v.R[6 + k] * t[2]);
+  return v;
+}
+void cross3(const double a[3], const double b[3], double c[3]) {
+  c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+double dot3(const double a[3], const double b[3]) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+}  // namespace
+
+int e3d_reg_stereo_plan(e3d_reg_t* h, int left_image_id, int right_image_id, double blank_pixels, int max_image_size, double focal_length,
+                        e3d_stereo_plan* out) {
+  E3D_TRY_ON(h)
+  if (!h || !out) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!(blank_pixels >= 0.0 && blank_pixels <= 1.0)) throw Error(E3D_ERR_INVALID, fmt("blank_pixels = %g is outside [0, 1]", blank_pixels));
+  const ImageDev* im[2] = {&get_image(h, left_image_id), &get_image(h, right_image_id)};
+  const Intrin* in[2] = {&h->intr.at(im[0]->intrinsics_id), &h->intr.at(im[1]->intrinsics_id)};
+  const StereoView v[2] = {stereo_view(*im[0]), stereo_view(*im[1])};
+  // the rectified frame: x along the baseline, z the part of the mean optical axis at right angles to it
+  const double b[3] = {v[1].C[0] - v[0].C[0], v[1].C[1] - v[0].C[1], v[1].C[2] - v[0].C[2]};
+  const double B = std::sqrt(b[0] * b[0] + b[1] * b[1] + b[2] * b[2]);
+  if (!std::isfinite(B) || B < 1e-9) throw Error(E3D_ERR_INVALID, "the two images have the same camera centre: no baseline");
+  const double ex[3] = {b[0] / B, b[1] / B, b[2] / B};
+  const double zs[3] = {v[0].R[6] + v[1].R[6], v[0].R[7] + v[1].R[7], v[0].R[8] + v[1].R[8]};
+  double c[3];
+  cross3(zs, ex, c);
+  const double nc = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]), nzs = std::sqrt(zs[0] * zs[0] + zs[1] * zs[1] + zs[2] * zs[2]);
+  if (!(nc >= 1e-6 * nzs) || !(nc > 0.0)) throw Error(E3D_ERR_INVALID, "the cameras look along the baseline: the pair cannot be rectified");
+  const double ey[3] = {c[0] / nc, c[1] / nc, c[2] / nc};
+  double ez[3];
+  cross3(ex, ey, ez);
+  const double ys[3] = {v[0].R[3] + v[1].R[3], v[0].R[4] + v[1].R[4], v[0].R[5] + v[1].R[5]};
+  if (!(dot3(ey, ys) > 0.0))
+    throw Error(E3D_ERR_INVALID, "the pair is given right-then-left (the rectified images would be upside down): swap the two images");
+  for (int i = 0; i < 2; ++i)
+    if (!(dot3(ez, v[i].R + 6) > 0.0)) throw Error(E3D_ERR_INVALID, "a camera looks away from the rectified viewing direction");
+  const double Rr[9] = {ex[0], ex[1], ex[2], ey[0], ey[1], ey[2], ez[0], ez[1], ez[2]};
+  e3d_stereo_plan plan{};
+  float* S[2] = {plan.S_left, plan.S_right};
+  for (int i = 0; i < 2; ++i)
+    for (int r = 0; r < 3; ++r)
+      for (int k = 0; k < 3; ++k)
+        S[i][3 * r + k] = (float)(v[i].R[3 * r] * Rr[3 * k] + v[i].R[3 * r + 1] * Rr[3 * k + 1] + v[i].R[3 * r + 2] * Rr[3 * k + 2]);
+  double q[4];
+  rotation_to_quat(Rr, q);
+  for (int k = 0; k < 4; ++k) plan.q_rect[k] = (float)q[k];
+  for (int k = 0; k < 3; ++k) {
+    const double tl = -(Rr[3 * k] * v[0].C[0] + Rr[3 * k + 1] * v[0].C[1] + Rr[3 * k + 2] * v[0].C[2]);
+    plan.t_left[k] = (float)tl;
+    plan.t_right[k] = (float)(k == 0 ? tl - B : tl);
+  }
+  plan.baseline = (float)B;
+  double fd = focal_length;
+  if (!(fd > 0.0)) fd = (((double)in[0]->levels[0].fx + (double)in[0]->levels[0].fy) + ((double)in[1]->levels[0].fx + (double)in[1]->levels[0].fy)) / 4.0;
+  const float f = (float)fd;
+  if (!(f > 0.f) || !std::isfinite(f)) throw Error(E3D_ERR_INVALID, "the focal length of the rectified camera is not positive and finite");
+  // window: both cameras' border samples rotated into the rectified frame, r = S^T (nx, ny, 1) in f64 with the rounded S, united per side
+  std::vector<float2> sides[4];
+  for (int i = 0; i < 2; ++i) {
+    const CamLevel& cam = in[i]->levels[0];
+    std::vector<float2> nxy = undistort_border_samples(h, *in[i]);
+    const float* s = S[i];
+    for (float2& p : nxy) {
+      const double nx = p.x, ny = p.y;
+      const double rx = (double)s[0] * nx + (double)s[3] * ny + (double)s[6];
+      const double ry = (double)s[1] * nx + (double)s[4] * ny + (double)s[7];
+      const double rz = (double)s[2] * nx + (double)s[5] * ny + (double)s[8];
+      const double u = rx / rz, w = ry / rz;
+      if (rz > 0.0 && std::isfinite(u) && std::isfinite(w)) p = make_float2((float)u, (float)w);
+      else p = make_float2(NAN, NAN);             // behind the rectified image plane, or no finite position in its own camera
+    }
+    undistort_append_sides(nxy, cam.width, cam.height, sides);
+  }
+  undistort_plan_from_sides(sides, f, f, blank_pixels, max_image_size, &plan.camera);
+  *out = plan;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_stereo_rectify(e3d_reg_t* h, int intrinsics_id, const e3d_undistort_plan* target, const float S[9], int kind, const void* src, void* dst,
+                           uint8_t* valid_out) {
+  E3D_TRY_ON(h)
+  if (!h || !target || !S || !src || !dst) throw Error(E3D_ERR_INVALID, "null argument");
+  undistort_resample(h, intrinsics_id, target, S, kind, src, dst, valid_out);
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_stereo_kernel_ms(e3d_reg_t* h, float* ms) {
+  E3D_TRY_ON(h)
+  if (!h || !ms) throw Error(E3D_ERR_INVALID, "null argument");
+  *ms = h->scan.stereo_ms;
+  return 0;
+  E3D_CATCH()
+}
+
+int e3d_reg_stereo_ground_truth(e3d_reg_t* h, int left_rect_image_id, int right_rect_image_id, const uint8_t* left_excluded,
+                                const uint8_t* right_excluded, float* disparity, uint8_t* nocc_mask, float* depth) {
+  E3D_TRY_ON(h)
+  if (!h || !disparity || !nocc_mask) throw Error(E3D_ERR_INVALID, "null argument");
+  if (!h->scan.scan_points_set) throw Error(E3D_ERR_INVALID, "no scan points set (e3d_reg_set_scan_points)");
+  ImageDev& left = owned_image(h, left_rect_image_id);
+  ImageDev& right = owned_image(h, right_rect_image_id);
+  if (left.intrinsics_id != right.intrinsics_id) throw Error(E3D_ERR_INVALID, "the two rectified images do not share their intrinsics");
+  const Intrin& in = h->intr.at(left.intrinsics_id);
+  const CamLevel& cam = in.levels[0];
+  if (in.type != kPinhole || cam.fx != cam.fy) throw Error(E3D_ERR_INVALID, "the rectified camera is not PINHOLE with fx == fy");
+  if (memcmp(&left.pose_q.q, &right.pose_q.q, sizeof(Quatf)) != 0)
+    throw Error(E3D_ERR_INVALID, "the rotations of the two rectified images differ");
+  if (memcmp(&left.pose_q.t[1], &right.pose_q.t[1], 2 * sizeof(float)) != 0)
+    throw Error(E3D_ERR_INVALID, "the y or z translations of the two rectified images differ: the pair is not rectified");
+  const double B = (double)left.pose_q.t[0] - (double)right.pose_q.t[0];
+  if (!(B > 0.0) || !std::isfinite(B)) throw Error(E3D_ERR_INVALID, "the baseline t_left.x - t_right.x is not positive (are the images swapped?)");
+  const size_t px = (size_t)cam.width * cam.height, n = h->scan.n_scan;
+  h->scan.eval_mask.reserve(px); h->scan.gt_depth.reserve(px); h->scan.stereo_d2.reserve(px);
+  h->scan.stereo_disparity.reserve(px); h->scan.stereo_nocc.reserve(px);
+  if (n) E3D_HIP(hipMemsetAsync(h->scan.scan_counts.p, 0, sizeof(int) * n, h->stream));
+  // Each image's occlusion depth is rendered once and stays in im.depth.  One mask buffer serves both images: the right image is
+  // counted first (the counters do not depend on the order), the left image's mask then stays for its two depth maps.
+  auto count = [&](ImageDev& im, int image_id, const uint8_t* excluded) {
+    render_depth(h, image_id, in.min_image_scale, nullptr);
+    if (excluded) { copy_in(h->scan.eval_mask.p, excluded, px, h->stream); stereo_normalize_mask_launch(h->scan.eval_mask.p, px, h->stream); }
+    launch_scan_visibility(h, im, in, excluded ? h->scan.eval_mask.p : nullptr, 1, 0, 0, h->scan.gt_depth.p);
+  };
+  count(right, right_rect_image_id, right_excluded);
+  count(left, left_rect_image_id, left_excluded);
+  const unsigned char* left_mask = left_excluded ? h->scan.eval_mask.p : nullptr;
+  fill_f32(reinterpret_cast<float*>(h->scan.gt_depth.p), px, INFINITY, h->stream);
+  launch_scan_visibility(h, left, in, left_mask, 1, 1, 1, h->scan.gt_depth.p);           // D1: the nearest point the left image sees
+  fill_f32(reinterpret_cast<float*>(h->scan.stereo_d2.p), px, INFINITY, h->stream);
+  launch_scan_visibility(h, left, in, left_mask, 1, 1, 2, h->scan.stereo_d2.p);          // D2: the nearest point both see
+  stereo_disparity_launch(h->scan.gt_depth.p, h->scan.stereo_d2.p, px, cam.fx, B, h->scan.stereo_disparity.p, h->scan.stereo_nocc.p, h->stream);
+  copy_out(disparity, h->scan.stereo_disparity.p, sizeof(float) * px, h->stream);
+  copy_out(nocc_mask, h->scan.stereo_nocc.p, px, h->stream);
+  if (depth) copy_out(depth, h->scan.gt_depth.p, sizeof(float) * px, h->stream);
+  rsync(h);
+  E3D_HIP(hipGetLastError());
+  return 0;
+  E3D_CATCH()
+}
+
 // ---- debug point clouds (Problem::DebugWriteColoredPointCloud, src/opt/problem.cc:642-704) ---------------------------------------
 int e3d_reg_scan_colors_begin(e3d_reg_t* h) {
   E3D_TRY_ON(h)
@@ -922,6 +1111,7 @@ int e3d_reg_scan_colors_add_image(e3d_reg_t* h, int image_id, const uint8_t* rgb
   ImageDev& im = owned_image(h, image_id);
   if (h->scan.n_scan == 0) return 0;
   const Intrin& in = h->intr.at(im.intrinsics_id);
+  if (im.pix.size() != in.levels.size()) throw Error(E3D_ERR_INVALID, fmt("image %d was set without pixels", image_id));
   const int scale = best_available_scale(h, in);
   render_depth(h, image_id, scale, nullptr);
   const int lvl = std::max(0, scale - in.min_image_scale);

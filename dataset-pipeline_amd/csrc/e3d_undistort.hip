@@ -14,11 +14,6 @@
 
 namespace e3d {
 
-// A workgroup is four waves, each on 64 consecutive pixels of one output row (threadIdx.x is the lane): the positions the lanes of
-// a wave gather from run along one source row (a gently bent curve for the distorted models), so a wave's byte loads of one tap
-// fall on a few neighbouring cache lines, and the rows above and below belong to the waves next to it.
-constexpr int kUndistortRun = kWave, kUndistortRows = kBlock / kWave;
-
 template <int M, int KIND>
 __global__ __launch_bounds__(kBlock) void k_undistort(CamLevel c, UndistortTarget t, const unsigned char* __restrict__ src,
                                                       unsigned char* __restrict__ dst, unsigned char* __restrict__ valid) {
@@ -28,42 +23,7 @@ __global__ __launch_bounds__(kBlock) void k_undistort(CamLevel c, UndistortTarge
   const float nx = ((float)x - t.cx) / t.fx, ny = ((float)y - t.cy) / t.fy;
   float sx, sy;
   cam_normalized_to_image<M>(c, nx, ny, sx, sy);
-  const int W = c.width, H = c.height;
-  // closed interval: the plan's inner extents map to exactly these borders (NaN and +-inf fail the comparisons)
-  const bool ok = sx >= 0.f && sx <= (float)(W - 1) && sy >= 0.f && sy <= (float)(H - 1);
-  if (valid) valid[o] = ok ? 1 : 0;
-  if (!ok) {
-    if constexpr (KIND == kUndistortGray) dst[o] = 0;
-    else if constexpr (KIND == kUndistortRgb) { dst[3 * o] = 0; dst[3 * o + 1] = 0; dst[3 * o + 2] = 0; }
-    else if constexpr (KIND == kUndistortMask) dst[o] = 3;        // kObs | kEvalObs: no data
-    else reinterpret_cast<unsigned*>(dst)[o] = 0u;
-    return;
-  }
-  if constexpr (KIND == kUndistortNearest) {
-    const int ix = min((int)(sx + 0.5f), W - 1), iy = min((int)(sy + 0.5f), H - 1);
-    reinterpret_cast<unsigned*>(dst)[o] = reinterpret_cast<const unsigned*>(src)[(size_t)iy * W + ix];     // copied as bits
-  } else {
-    const int ix = min((int)sx, W - 2), iy = min((int)sy, H - 2);
-    const size_t r0 = (size_t)iy * W + ix, r1 = r0 + (size_t)W;
-    if constexpr (KIND == kUndistortMask) {
-      dst[o] = (unsigned char)(src[r0] | src[r0 + 1] | src[r1] | src[r1 + 1]);
-    } else {
-      const float ax = sx - (float)ix, ay = sy - (float)iy;
-      const float bx = 1.f - ax, by = 1.f - ay;
-      constexpr int C = KIND == kUndistortRgb ? 3 : 1;
-      unsigned char p[4][C];
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch) {                // all the loads first, then the arithmetic
-        p[0][ch] = src[C * r0 + ch]; p[1][ch] = src[C * (r0 + 1) + ch];
-        p[2][ch] = src[C * r1 + ch]; p[3][ch] = src[C * (r1 + 1) + ch];
-      }
-#pragma unroll
-      for (int ch = 0; ch < C; ++ch) {
-        const float v = by * (bx * (float)p[0][ch] + ax * (float)p[1][ch]) + ay * (bx * (float)p[2][ch] + ax * (float)p[3][ch]);
-        dst[C * o + ch] = (unsigned char)(int)(v + 0.5f);
-      }
-    }
-  }
+  undistort_sample<KIND>(sx, sy, c.width, c.height, o, src, dst, valid);
 }
 
 template <int M>

@@ -39,6 +39,7 @@ namespace e3d_host {
   X(e3d_reg_pick_scan_points) X(e3d_reg_image_bearings) X(e3d_reg_project_points) X(e3d_pose_from_bearings)            \
   X(e3d_reg_render_depth) X(e3d_reg_set_depth_map_level0)                                                              \
   X(e3d_reg_undistort_plan) X(e3d_reg_undistort)                                                                       \
+  X(e3d_reg_stereo_plan) X(e3d_reg_stereo_rectify) X(e3d_reg_stereo_ground_truth)                                      \
   X(e3d_edit_create) X(e3d_edit_destroy) X(e3d_edit_size) X(e3d_edit_get_points)                                       \
   X(e3d_edit_get_selection) X(e3d_edit_set_selection) X(e3d_edit_selection_count)                                      \
   X(e3d_edit_lasso) X(e3d_edit_beyond_plane) X(e3d_edit_pick)                                                          \

@@ -421,7 +421,10 @@ int e3d_reg_depth_cost(e3d_reg_t* reg, int image_id, int point_scale, double* su
 int e3d_reg_get_intrinsics_level(e3d_reg_t* reg, int intrinsics_id, int level, int* width, int* height,
                                  float* parameters, float* radius_cutoff_squared);
 /* opt::Image: u8 pyramid (level l has the size of intrinsics level l) and optional masks; pose image_T_global as the
- * Sophus::SE3f state: unit quaternion {w, x, y, z} + translation (what COLMAP images.txt stores). */
+ * Sophus::SE3f state: unit quaternion {w, x, y, z} + translation (what COLMAP images.txt stores).  level_pixels == NULL (then
+ * level_masks must be NULL too) sets an image without pixels: its id, intrinsics and pose serve the calls that ask about geometry
+ * only (e3d_reg_render_depth, the scan visibility calls, e3d_reg_stereo_plan / _ground_truth); calls that read intensities refuse it.
+ * Under e3d_reg_set_shard the images of other ranks are set this way. */
 int e3d_reg_set_image(e3d_reg_t* reg, int image_id, int intrinsics_id, const uint8_t* const* level_pixels,
                       const uint8_t* const* level_masks);
 int e3d_reg_set_image_pose(e3d_reg_t* reg, int image_id, const float q[4], const float t[3]);
@@ -644,6 +647,67 @@ int e3d_reg_undistort_plan(e3d_reg_t* reg, int intrinsics_id, double blank_pixel
 int e3d_reg_undistort(e3d_reg_t* reg, int intrinsics_id, const e3d_undistort_plan* plan, int kind, const void* src, void* dst,
                       uint8_t* valid_out);
 int e3d_reg_undistort_kernel_ms(e3d_reg_t* reg, float* ms);
+/* StereoPairCreator: rectified two-view sets (the third ETH3D product): a rectified image pair of two cameras of a rig, the disparity
+ * ground truth of the left image and the mask that tells pixels seen by both cameras from half-occluded ones.  The three rules are
+ * this library's own.  Pixel coordinates: (0, 0) is the centre of the top-left pixel; lengths are in the unit of the scans.
+ *   e3d_reg_stereo_plan: the common PINHOLE camera and the two poses.  Inputs: image_T_global = (q_i, t_i) of the two images as
+ *     e3d_reg_get_image_pose reports them (i = 0: left, 1: right) and their level-0 models.  All f64 from the f32 state, every
+ *     expression evaluated left to right as written:
+ *     1. n = sqrt(w w + x x + y y + z z), q / n; R_i = the quaternion's matrix (Eigen's toRotationMatrix order: tx = 2 x, twx = tx w,
+ *        ..., R00 = 1 - (tyy + tzz), R01 = txy - twz, ...).  C_i[k] = -(R_i[0][k] t0 + R_i[1][k] t1 + R_i[2][k] t2).  b = C_1 - C_0,
+ *        B = sqrt(bx bx + by by + bz bz), ex = b / B.
+ *     2. zs = row2(R_0) + row2(R_1).  c = zs x ex (c.x = zs.y ex.z - zs.z ex.y, ...), ey = c / |c|, ez = ex x ey.  Rr = rows ex, ey, ez.
+ *     3. S_i[r][k] = R_i[r][0] Rr[k][0] + R_i[r][1] Rr[k][1] + R_i[r][2] Rr[k][2] (= R_i Rr^T), rounded to f32.
+ *     4. q_rect = the quaternion of Rr (Shepperd's four branches on the trace and the largest diagonal entry, as
+ *        e3d_pose_from_bearings converts its result), divided by its norm, w >= 0, rounded to f32.
+ *     5. t_left[k] = -(Rr[k][0] C_0.x + Rr[k][1] C_0.y + Rr[k][2] C_0.z); t_right = t_left - (B, 0, 0); both rounded to f32, so their
+ *        y and z components have equal bits.  baseline = (float)B.
+ *     6. f = (float)focal_length if focal_length > 0, else (float)(((fx_0 + fy_0) + (fx_1 + fy_1)) / 4) of the level-0 models.
+ *     7. Window: each camera's border samples exactly as e3d_reg_undistort_plan takes them; each (nx, ny) becomes
+ *        r = (S[0] nx + S[3] ny + S[6], S[1] nx + S[4] ny + S[7], S[2] nx + S[5] ny + S[8]) with the rounded S_i, and the sample
+ *        ((float)(r.x / r.z), (float)(r.y / r.z)); one that is not finite or has r.z <= 0 counts as non-finite.  Per side the samples
+ *        of both cameras are united and the rule of e3d_reg_undistort_plan applies unchanged with fx = fy = f.  Both rectified
+ *        images share camera.width, .height, .fx = .fy, .cx, .cy; the disparity offset (doffs) is 0.
+ *     Refused (E3D_ERR_INVALID) besides what e3d_reg_undistort_plan refuses: B not finite or below 1e-9; |c| < 1e-6 |zs| (the cameras
+ *     look along the baseline); ey . (row1(R_0) + row1(R_1)) <= 0 (the pair is given right-then-left and the result would be upside
+ *     down: the message says to swap); ez . row2(R_i) <= 0 for either image.  Unlike the undistorter at b = 0, not every output pixel
+ *     need be valid: with a rotation the inner extents only approximate the common region, the validity maps below are authoritative.
+ *   e3d_reg_stereo_rectify: one image through the plan's camera (`target`) and its S.  For the output pixel (x, y), f32 without
+ *     contraction: nx = (float(x) - cx') / fx', ny = (float(y) - cy') / fy'; vx = (S[0] nx + S[1] ny) + S[2], vy = (S[3] nx + S[4] ny)
+ *     + S[5], vz = (S[6] nx + S[7] ny) + S[8], each product and sum rounded.  The pixel is invalid if !(vz > 0); otherwise (sx, sy) =
+ *     the level-0 model's NormalizedToImage(vx / vz, vy / vz) and everything from there is e3d_reg_undistort: the closed validity
+ *     interval, the kinds 0..3, the values 0 / 3 of invalid pixels, the refusals, plus a non-finite entry of S.  With S the identity
+ *     the result equals e3d_reg_undistort on the same target bit for bit.
+ *   e3d_reg_stereo_kernel_ms: HIP-event time of the resampling kernel of the last e3d_reg_stereo_rectify (tools/bench_stereo.py).
+ *   e3d_reg_stereo_ground_truth: the caller registers the rectified cameras -- one PINHOLE intrinsics [f f cx cy] of the plan's size
+ *     (min_image_scale 0, one level), two images without pixels (e3d_reg_set_image(id, intr, NULL, NULL)) with the poses (q_rect, t_left)
+ *     and (q_rect, t_right) -- and sets the scan points and the occlusion geometry as for e3d_reg_ground_truth_depth.  The entry sets
+ *     the scan observation counters to zero, runs the visibility test of e3d_reg_count_scan_observations for both images (a pixel of
+ *     left_excluded / right_excluded that is non-zero excludes, NULL = none; width x height bytes), each image's occlusion depth
+ *     rendered once, and renders D1 = the depth of the nearest point visible in the left image and D2 = that of the nearest point
+ *     visible in both (e3d_reg_ground_truth_depth with min_count 1 and 2).  Per pixel of the left image:
+ *       disparity = (float)((double)f * B / (double)D1) with B = (double)t_left.x - (double)t_right.x where D1 is finite, else +inf
+ *         (the Middlebury convention for "unknown");
+ *       nocc_mask = 255 where D1 is finite and the bits of D2 equal those of D1, 128 where D1 is finite and they differ (the nearest
+ *         point is hidden from the right image: half-occluded), 0 where D1 is +inf;
+ *       depth (optional) = D1.
+ *     The counters are left holding the counts over these two images (e3d_reg_get_scan_observation_counts).
+ *     Refused (E3D_ERR_INVALID): images that do not share one PINHOLE intrinsics with fx == fy; quaternions whose bits differ; t.y or
+ *     t.z whose bits differ; B <= 0; no scan points set; a null handle, disparity or nocc_mask. */
+typedef struct {
+  e3d_undistort_plan camera;          /* the common PINHOLE of both rectified images, fx == fy, pixel-centre convention */
+  float baseline;                     /* B > 0, scan units */
+  float q_rect[4];                    /* rotation of rect_T_global, {w,x,y,z}, w >= 0, the same for both images */
+  float t_left[3], t_right[3];        /* translations of the two rectified image_T_global poses */
+  float S_left[9], S_right[9];        /* source_T_rect rotations, row-major: ray in the rectified frame -> ray in the source camera frame */
+} e3d_stereo_plan;
+int e3d_reg_stereo_plan(e3d_reg_t* reg, int left_image_id, int right_image_id, double blank_pixels, int max_image_size,
+                        double focal_length /* <= 0: derive */, e3d_stereo_plan* out);
+int e3d_reg_stereo_rectify(e3d_reg_t* reg, int intrinsics_id, const e3d_undistort_plan* target, const float S[9], int kind,
+                           const void* src, void* dst, uint8_t* valid_out);
+int e3d_reg_stereo_kernel_ms(e3d_reg_t* reg, float* ms);
+int e3d_reg_stereo_ground_truth(e3d_reg_t* reg, int left_rect_image_id, int right_rect_image_id, const uint8_t* left_excluded,
+                                const uint8_t* right_excluded, float* disparity, uint8_t* nocc_mask, float* depth /* optional */);
 /* Observations cache (src/opt/observations_cache.{h,cc}; Optimizer::set_cache_observations, optimizer.h).  When enabled, the
  * observation update re-projects a fixed per-image list of point indices with the current state and applies only the
  * scale-fit and border tests (VisibilityEstimator::AppendObservationsForIndexedPointsVisibleInImage,
