@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-SOURCES = ["e3d_icp.hip", "e3d_comm.hip", "e3d_icp_kernels.hip", "e3d_sort.hip", "e3d_normals.hip", "e3d_reg.hip", "e3d_reg_depth.hip", "e3d_reg_scan.hip", "e3d_multires.hip", "e3d_splats.hip", "e3d_cubemap.hip", "e3d_edit.hip", "e3d_surface.hip", "e3d_eval.hip", "e3d_undistort.hip", "e3d_stereo.hip"]
+SOURCES = ["e3d_icp.hip", "e3d_comm.hip", "e3d_icp_kernels.hip", "e3d_grid.hip", "e3d_icp_certify.hip", "e3d_icp_rows.hip", "e3d_icp_lm.hip", "e3d_sort.hip", "e3d_normals.hip", "e3d_reg.hip", "e3d_reg_depth.hip", "e3d_reg_scan.hip", "e3d_multires.hip", "e3d_splats.hip", "e3d_cubemap.hip", "e3d_edit.hip", "e3d_surface.hip", "e3d_eval.hip", "e3d_undistort.hip", "e3d_stereo.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 
@@ -25,9 +25,11 @@ def lib_path():
 # operations of their long expression trees into v_pk_*_f32 and spends more on moves than it saves (measured on one MI355X:
 # k_lm_cost_multi 2.00 -> 1.67 ms, k_lm_pass<3> 0.97 -> 0.91 ms, k_reg_pass1 0.503 -> 0.447 ms; tools/micro/lm_variants.hip, DESIGN
 # 4.2); e3d_reg_depth.hip and e3d_reg_scan.hip were split off e3d_reg.hip and keep the flag their kernels were tuned and tested with.
+# So do e3d_grid.hip, e3d_icp_certify.hip, e3d_icp_rows.hip and e3d_icp_lm.hip, which were split off e3d_icp_kernels.hip.
 # The kNN kernels of e3d_normals.hip gain from it (1.72 vs 1.34 G normals/s) and keep it.  Rounding is the same either way.
-EXTRA_FLAGS = {"e3d_icp_kernels.hip": ["-fno-slp-vectorize"], "e3d_reg.hip": ["-fno-slp-vectorize"],
-               "e3d_reg_depth.hip": ["-fno-slp-vectorize"], "e3d_reg_scan.hip": ["-fno-slp-vectorize"]}
+_NO_SLP = ["e3d_icp_kernels.hip", "e3d_grid.hip", "e3d_icp_certify.hip", "e3d_icp_rows.hip", "e3d_icp_lm.hip", "e3d_reg.hip",
+           "e3d_reg_depth.hip", "e3d_reg_scan.hip"]
+EXTRA_FLAGS = {s: ["-fno-slp-vectorize"] for s in _NO_SLP}
 
 
 def _newer(src, dst):
@@ -41,12 +43,13 @@ def build(force=False, verbose=False):
     hdrs = [os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith((".hpp", ".h"))]
     inc = os.path.join(HERE, "..", "include")
     hdrs += [os.path.join(inc, f) for f in os.listdir(inc) if f.endswith(".h")]
+    missing = [s for s in SOURCES if not os.path.exists(os.path.join(CSRC, s))]
+    if missing:      # (before any compiler starts: a misspelt name would otherwise surface as an undefined symbol at link or load time)
+        raise RuntimeError("source listed in SOURCES does not exist: " + ", ".join(os.path.join(CSRC, s) for s in missing))
     objs = []
     procs = []
     for s in SOURCES:
         src = os.path.join(CSRC, s)
-        if not os.path.exists(src):
-            continue
         obj = os.path.join(objdir, s.replace(".hip", ".o"))
         objs.append(obj)
         cmd = ["hipcc"] + FLAGS + EXTRA_FLAGS.get(s, []) + os.environ.get("E3D_EXTRA_HIPCC_FLAGS", "").split() + ["-c", src, "-o", obj]

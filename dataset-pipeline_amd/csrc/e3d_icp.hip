@@ -45,7 +45,7 @@ int require_device() {
 // Every environment switch of this file, parsed once at first use; each field carries its default and its parse rule.  "on unless 0" is
 // env_default_on (off only if the value starts with '0'), "off unless 1" env_default_off (on only if it starts with '1'); numbers go
 // through atoi / atof unclamped unless the field says so.  nn_mode, resident and sequential_dsum are initial values: e3d_set_nn_mode and
-// the handle's setters change their copies.  (E3D_ROW_SPAN, E3D_NN_QUAD_LIMIT, E3D_NN_HALF_MIN, E3D_NN_SEED_PROBES: e3d_icp_kernels.hip.)
+// the handle's setters change their copies.  (E3D_ROW_SPAN: e3d_icp_kernels.hip; E3D_NN_QUAD_LIMIT, E3D_NN_HALF_MIN, E3D_NN_SEED_PROBES: e3d_icp_certify.hip.)
 struct IcpSwitches {
   // ---- the grids ----
   // E3D_NN_MODE: 0 auto (default), 1 per-query, 2 hash-table buckets, 3 dense rows, 4 dense rows + MFMA filter, 5 dense rows with the

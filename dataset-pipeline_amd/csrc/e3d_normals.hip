@@ -19,7 +19,7 @@
 
 #include "../../include/e3d_hip.h"
 #include "../../include/e3d_libm.h"   // bit-defined atan2f / cosf / sinf: the same bits on host and device
-#include "e3d_icp_kernels.hpp"
+#include "e3d_grid.hpp"
 
 #pragma clang fp contract(off)
 

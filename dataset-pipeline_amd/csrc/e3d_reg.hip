@@ -23,7 +23,8 @@
 #include <random>
 #include <string>
 
-#include "e3d_icp_kernels.hpp"
+#include "e3d_grid.hpp"
+#include "e3d_icp_kernels.hpp"   // launch_match_scan (e3d_icp_rows.hip) and nothing else: the scan of the observation compaction
 #include "e3d_reg_handle.hpp"
 
 #pragma clang fp contract(off)

@@ -4,7 +4,7 @@
 #include <algorithm>
 #include <cmath>
 
-#include "e3d_icp_kernels.hpp"
+#include "e3d_grid.hpp"
 #include "e3d_reg_handle.hpp"
 
 #pragma clang fp contract(off)

@@ -1,5 +1,7 @@
-// e3d_sort.hip -- device radix sort of (cell key, point index) pairs.  The sort itself is the
-// rocPRIM library primitive (its onesweep kernel with the gfx950 tuning).  Used at every grid build (one-off per cloud and search radius) AND on the
+// e3d_sort.hip -- the library's rocPRIM primitives and the host side of the hashed grid (declarations: e3d_grid.hpp): the radix sorts
+// of (key, index) pairs and of 64-bit keys, the exclusive MAX and sum scans, the stable compaction's offsets and run-start flags
+// (Compactor), and the grid builders build_cell_table / sort_into_cells over the kernels of e3d_grid.hip.  The sorts
+// are the library primitive (its onesweep kernel with the gfx950 tuning).  The pair sort runs at every grid build (one-off per cloud and search radius) AND on the
 // per-iteration path: once per batch of directed pairs for the far lists of the first outer iterations (e3d_icp.hip: find_pairs_multi).
 #include <algorithm>
 #include <cstdio>
@@ -9,7 +11,7 @@
 
 #include <rocprim/rocprim.hpp>
 
-#include "e3d_icp_kernels.hpp"
+#include "e3d_grid.hpp"
 
 namespace e3d {
 

@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/e3d_hip.h"
-#include "e3d_icp_kernels.hpp"
+#include "e3d_grid.hpp"
 
 namespace e3d {
 

@@ -1,5 +1,5 @@
 """Resident correspondence rows that hold the TARGET half only (R0 = {tp.xy}, R1 = {tp.z, tn.xyz}) while the source half of every
-row comes from one view per source cloud (V0 = {sp.xyz, sn.x}, V1 = {sn.yz}), e3d_icp.hip / e3d_icp_kernels.hip.
+row comes from one view per source cloud (V0 = {sp.xyz, sn.x}, V1 = {sn.yz}), e3d_icp.hip / e3d_icp_rows.hip (written) / e3d_icp_lm.hip (read).
 
 A query without a partner is a row with a NaN in tp.x, which the LM passes read as twelve zeros.  What can go wrong: a row that keeps
 a stale target half or a stale mark when its query changes partners, a view written for another frame, pose or sorted order, a slice
