@@ -9,7 +9,7 @@ The directory name contains a hyphen (it is the name the task prescribes), so im
     import importlib; e3d = importlib.import_module("dataset-pipeline_amd")
 """
 from .capi import (CUBE_MAP_FACES, Comm, E3DError, EditView, PointCloudEdit, PointToPlaneICP, RegParams, RegProblem, StereoPlan, UndistortPlan, create_splats, default_reg_params, determine_point_neighbors, edit_view,
-                   evaluate_reconstruction, find_correspondences, mesh_squared_distance, icp_pair_system, lib, lib_path, libm_eval, local_outlier_removal, release_workspaces, merge_close_points, normals_knn, normals_radius, pose_from_bearings, reconstruct_surface, render_cube_map, transform_cloud)
+                   evaluate_disparity, evaluate_reconstruction, find_correspondences, mesh_squared_distance, icp_pair_system, lib, lib_path, libm_eval, local_outlier_removal, release_workspaces, merge_close_points, normals_knn, normals_radius, pose_from_bearings, reconstruct_surface, render_cube_map, transform_cloud)
 
-__all__ = ["CUBE_MAP_FACES", "Comm", "E3DError", "EditView", "PointCloudEdit", "PointToPlaneICP", "RegParams", "RegProblem", "StereoPlan", "UndistortPlan", "create_splats", "default_reg_params", "determine_point_neighbors", "edit_view", "evaluate_reconstruction", "find_correspondences",
+__all__ = ["CUBE_MAP_FACES", "Comm", "E3DError", "EditView", "PointCloudEdit", "PointToPlaneICP", "RegParams", "RegProblem", "StereoPlan", "UndistortPlan", "create_splats", "default_reg_params", "determine_point_neighbors", "edit_view", "evaluate_disparity", "evaluate_reconstruction", "find_correspondences",
            "icp_pair_system", "lib", "lib_path", "libm_eval", "local_outlier_removal", "mesh_squared_distance", "release_workspaces", "merge_close_points", "normals_knn", "normals_radius", "pose_from_bearings", "reconstruct_surface", "render_cube_map", "transform_cloud"]

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
-SOURCES = ["e3d_icp.hip", "e3d_comm.hip", "e3d_icp_kernels.hip", "e3d_grid.hip", "e3d_icp_certify.hip", "e3d_icp_rows.hip", "e3d_icp_lm.hip", "e3d_sort.hip", "e3d_normals.hip", "e3d_reg.hip", "e3d_reg_depth.hip", "e3d_reg_scan.hip", "e3d_multires.hip", "e3d_splats.hip", "e3d_cubemap.hip", "e3d_edit.hip", "e3d_surface.hip", "e3d_eval.hip", "e3d_undistort.hip", "e3d_stereo.hip"]
+SOURCES = ["e3d_icp.hip", "e3d_comm.hip", "e3d_icp_kernels.hip", "e3d_grid.hip", "e3d_icp_certify.hip", "e3d_icp_rows.hip", "e3d_icp_lm.hip", "e3d_sort.hip", "e3d_normals.hip", "e3d_reg.hip", "e3d_reg_depth.hip", "e3d_reg_scan.hip", "e3d_multires.hip", "e3d_splats.hip", "e3d_cubemap.hip", "e3d_edit.hip", "e3d_surface.hip", "e3d_eval.hip", "e3d_undistort.hip", "e3d_stereo.hip", "e3d_stereo_eval.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-fhip-fp32-correctly-rounded-divide-sqrt", "-fno-fast-math", "-Wall", "-Wno-unused-function"]
 

@@ -216,6 +216,12 @@ SIGNATURES = {
     "e3d_eval_get_classes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_eval_get_voxels": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_eval_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
+    "e3d_evaluate_disparity": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]),
+    "e3d_disp_eval_destroy": (None, [C.c_void_p]),
+    "e3d_disp_eval_get_counts": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_disp_eval_get_sums": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_disp_eval_get_quantiles": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "e3d_disp_eval_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
 }
 
 
@@ -705,6 +711,80 @@ def evaluate_reconstruction(rec, scans, origins, tolerances=(0.01, 0.02, 0.05, 0
                 timings[names[i].decode() + "_ms"] = float(ms[i])
     finally:
         lib().e3d_eval_destroy(handle)
+    return out
+
+
+def disparity_scores(counts, sums):
+    """Rule 7 of e3d_evaluate_disparity from counts[..., 2 + T] and sums[..., 2] alone: a dict of f64 arrays coverage, avgerr, rms [...]
+    and bad, bad_or_missing [..., T]; each is 0 where its denominator is 0."""
+    counts = np.asarray(counts, np.int64)
+    sums = np.asarray(sums, np.float64)
+    n_region, n_valid, n_bad = counts[..., 0], counts[..., 1], counts[..., 2:]
+
+    def ratio(a, b):
+        a, b = np.broadcast_arrays(np.asarray(a, np.float64), np.asarray(b, np.float64))
+        out = np.zeros(a.shape, np.float64)
+        np.divide(a, b, out=out, where=b != 0)
+        return out
+
+    return {"coverage": ratio(n_valid, n_region), "bad": ratio(n_bad, n_valid[..., None]),
+            "bad_or_missing": ratio(n_bad + (n_region - n_valid)[..., None], n_region[..., None]),
+            "avgerr": ratio(sums[..., 0], n_valid), "rms": np.sqrt(ratio(sums[..., 1], n_valid))}
+
+
+def evaluate_disparity(gt, mask, estimates, thresholds=(0.5, 1, 2, 4), percentiles=(50, 90, 95, 99), error_maps=False, timings=None):
+    """StereoEvaluator (include/e3d_hip.h, e3d_evaluate_disparity).  gt[H, W] f32 (+inf = unknown), mask[H, W] uint8 or None, estimates
+    [H, W] or [n_est, H, W] f32, each numpy or torch, host or device (a sequence of [H, W] arrays is stacked on the host).  Returns a
+    dict: thresholds[T] f32, percentiles[P] int32, counts[n_est, 2, 2 + T] int64 (per region all / nocc: n_region, n_valid, n_bad[T]),
+    sums[n_est, 2, 2] f64 (sum1, sum2), quantiles[n_est, 2, P] f32, the derived scores of rule 7 (coverage, avgerr, rms [n_est, 2];
+    bad, bad_or_missing [n_est, 2, T]) and with error_maps the colour-coded maps [n_est, H, W, 3] uint8.  timings: a dict that receives
+    the HIP-event time of every kernel group as <group>_ms."""
+    keep = []
+    if isinstance(estimates, (list, tuple)):
+        estimates = np.stack([np.asarray(e.detach().cpu().numpy() if _is_torch(e) else e, np.float32) for e in estimates]) if len(estimates) else np.zeros((0,) + tuple(gt.shape), np.float32)
+    if len(gt.shape) != 2:
+        raise E3DError("evaluate_disparity: gt must be [H, W]")
+    H, W = int(gt.shape[0]), int(gt.shape[1])
+    shape = tuple(int(v) for v in estimates.shape)
+    if shape == (H, W):
+        n_est = 1
+    elif len(shape) == 3 and shape[1:] == (H, W):
+        n_est = shape[0]
+    else:
+        raise E3DError("evaluate_disparity: estimates of shape %s against a ground truth of %d x %d" % (shape, H, W))
+    if mask is not None and tuple(int(v) for v in mask.shape) != (H, W):
+        raise E3DError("evaluate_disparity: mask of shape %s against a ground truth of %d x %d" % (tuple(mask.shape), H, W))
+    thr = np.ascontiguousarray(thresholds, np.float32).reshape(-1)
+    pct = np.ascontiguousarray(percentiles, np.int32).reshape(-1)
+    T, P = len(thr), len(pct)
+    maps = np.zeros((n_est, H, W, 3), np.uint8) if error_maps else None
+    handle = lib().e3d_evaluate_disparity(_ptr(gt, np.float32, keep), _ptr(mask, np.uint8, keep), W, H, _ptr(estimates, np.float32, keep) if n_est else None, n_est,
+                                          C.c_void_p(thr.ctypes.data) if T else None, T, C.c_void_p(pct.ctypes.data) if P else None, P,
+                                          C.c_void_p(maps.ctypes.data) if error_maps and maps.size else None)
+    if not handle:
+        _err("e3d_evaluate_disparity")
+    try:
+        counts = np.zeros((n_est, 2, 2 + T), np.int64)
+        sums = np.zeros((n_est, 2, 2), np.float64)
+        quantiles = np.zeros((n_est, 2, P), np.float32)
+        if lib().e3d_disp_eval_get_counts(handle, C.c_void_p(counts.ctypes.data)) < 0:
+            _err("e3d_disp_eval_get_counts")
+        if lib().e3d_disp_eval_get_sums(handle, C.c_void_p(sums.ctypes.data)) < 0:
+            _err("e3d_disp_eval_get_sums")
+        if lib().e3d_disp_eval_get_quantiles(handle, C.c_void_p(quantiles.ctypes.data) if P else None) < 0:
+            _err("e3d_disp_eval_get_quantiles")
+        out = {"thresholds": thr, "percentiles": pct, "counts": counts, "sums": sums, "quantiles": quantiles}
+        out.update(disparity_scores(counts, sums))
+        if error_maps:
+            out["error_maps"] = maps
+        if timings is not None:
+            ms = (C.c_float * 16)()
+            names = (C.c_char_p * 16)()
+            g = lib().e3d_disp_eval_kernel_ms(handle, ms, names, 16)
+            for i in range(min(g, 16)):
+                timings[names[i].decode() + "_ms"] = float(ms[i])
+    finally:
+        lib().e3d_disp_eval_destroy(handle)
     return out
 
 

@@ -138,6 +138,16 @@ inline void copy_out(void* dst, const void* src_dev, size_t bytes, hipStream_t s
   E3D_HIP(hipMemcpyAsync(dst, src_dev, bytes, hipMemcpyDefault, s));
 }
 
+// A pointer the kernels can use as it is (device memory of the current device)?  Host pointers go through a staging copy.
+inline bool is_device_pointer(const void* ptr) {
+  if (!ptr) return false;
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
+  int dev = -1;
+  if (hipGetDevice(&dev) != hipSuccess) return false;
+  return attr.type == hipMemoryTypeDevice && attr.device == dev;
+}
+
 struct EventTimer {
   hipEvent_t a = nullptr, b = nullptr;
   EventTimer() { E3D_HIP(hipEventCreate(&a)); E3D_HIP(hipEventCreate(&b)); }

@@ -1628,16 +1628,6 @@ extern "C" int e3d_release_workspaces(void) {
 }
 
 namespace e3d {
-// A pointer the kernels can use as it is (device memory of the current device)?  Host pointers go through a staging copy.
-static bool is_device_pointer(const void* ptr) {
-  if (!ptr) return false;
-  hipPointerAttribute_t attr{};
-  if (hipPointerGetAttributes(&attr, ptr) != hipSuccess) { (void)hipGetLastError(); return false; }
-  int dev = -1;
-  if (hipGetDevice(&dev) != hipSuccess) return false;
-  return attr.type == hipMemoryTypeDevice && attr.device == dev;
-}
-
 // each query's k-th squared distance: FLANN's f32 (query - neighbour) distance of the last list entry (+inf if the list is short)
 __global__ __launch_bounds__(256) void k_knn_kth(const float* __restrict__ xyz, const int* __restrict__ knn, size_t n, int k,
                                                  float* __restrict__ kth) {

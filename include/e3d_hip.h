@@ -1001,6 +1001,57 @@ int e3d_eval_get_voxels(e3d_eval_t* eval, int kind, int32_t* ijk, int32_t* n_poi
  * array may be NULL); returns the number of groups: grid, search, range, voxels. */
 int e3d_eval_kernel_ms(e3d_eval_t* eval, float* ms, const char** names, int capacity);
 
+/* ---- StereoEvaluator: disparity maps of a stereo method against the two-view ground truth ----------------------------------
+ * The counterpart of e3d_evaluate_reconstruction for the two-view sets StereoPairCreator writes (disp0GT.pfm, mask0nocc.png).
+ * The rules are this library's; they restate nothing of the reference, which has no such code.
+ *
+ * Inputs: gt, W x H f32, row-major, top row first (+inf, any non-finite value: unknown); mask, W x H u8, or NULL; n_est >= 1
+ * estimates of the same size, contiguous (estimate e is elements [e W H, (e + 1) W H)), f32; T thresholds, 1 <= T <= 8, f32,
+ * finite, >= 0, strictly ascending; P percentiles, 0 <= P <= 8, int32, each in 1 .. 100.
+ *
+ * 1. Regions.  A pixel is known iff gt is finite.  Region 0 ("all") is the known pixels with mask != 0, region 1 ("nocc") the
+ *    known pixels with mask == 255; with mask == NULL both are the known pixels.  Any mask value is accepted, only != 0 and
+ *    == 255 are read.  Region 1 is a subset of region 0.
+ * 2. Valid estimate.  A pixel's estimate e is valid iff it is finite (NaN and +-inf are invalid, following Middlebury's inf);
+ *    any finite value is valid, negative ones included.
+ * 3. Error.  err = fabsf(e - gt): one f32 subtraction, no contraction; +inf if the subtraction overflows, never NaN.
+ * 4. Counts (int64), per estimate and region: n_region, the pixels of the region; n_valid, those with a valid estimate;
+ *    n_bad[t], the valid ones with err > thr_t (strict).
+ * 5. Sums (f64), per estimate and region, over the region's valid pixels: sum1 of (double)err, sum2 of (double)err *
+ *    (double)err (each product exact).  They are formed on the GPU in an order that depends on W, H and n_est alone, so two
+ *    calls return identical bytes.
+ * 6. Quantiles (f32), per estimate, region and percentile p: with n = n_valid >= 1 and k = (p n + 99) / 100 - 1 in 64-bit
+ *    integers (ceil(p n / 100) - 1), element k of the region's valid errors sorted ascending.  Nothing is interpolated: the
+ *    result has the bits of one pixel's err.  n == 0 gives NaN.
+ * 7. Derived scores (the callers', f64, from the numbers above alone): coverage = n_valid / n_region, bad_t = n_bad[t] /
+ *    n_valid, bad_or_missing_t = (n_bad[t] + n_region - n_valid) / n_region, avgerr = sum1 / n_valid, rms = sqrt(sum2 /
+ *    n_valid); each is 0 where its denominator is 0.
+ * 8. Error map (optional, u8 x 3 per pixel and estimate, R G B).  Outside region 0: (0, 0, 0).  Invalid estimate:
+ *    (255, 0, 255).  Otherwise, with c the number of thresholds with err > thr_t, palette[(c * 8) / T] of the nine entries
+ *    (49,54,149) (69,117,180) (116,173,209) (171,217,233) (254,224,144) (253,174,97) (244,109,67) (215,48,39) (165,0,38).
+ *    A pixel of region 0 outside region 1 (half-occluded) gets each channel >> 1, the invalid colour included.
+ *
+ * Refused (NULL; E3D_ERR_INVALID's message in e3d_last_error; the library stays usable): W or H < 1; W H >= 2^31; n_est < 1;
+ * T outside 1 .. 8, P outside 0 .. 8; a threshold that is not finite, is negative or is not above its predecessor; a
+ * percentile outside 1 .. 100; a null gt, estimates or thresholds (or percentiles with P > 0).
+ * gt, mask, estimates: host or device; thresholds, percentiles: host; error_maps: host, n_est H W 3 bytes, or NULL.  The
+ * ground truth and the mask are read from one copy on the device by all estimates.  The result is a host-side handle; the call
+ * returns after all device work (one synchronisation, no read-back between the passes), and no device memory is kept. */
+typedef struct e3d_disp_eval e3d_disp_eval_t;
+e3d_disp_eval_t* e3d_evaluate_disparity(const float* gt, const uint8_t* mask, int width, int height, const float* estimates,
+                                        int n_estimates, const float* thresholds, int n_thresholds, const int32_t* percentiles,
+                                        int n_percentiles, uint8_t* error_maps);
+void e3d_disp_eval_destroy(e3d_disp_eval_t* eval);
+/* counts[n_est][2][2 + T]: per estimate and region n_region, n_valid, n_bad[T]. */
+int e3d_disp_eval_get_counts(e3d_disp_eval_t* eval, int64_t* counts);
+/* sums[n_est][2][2]: per estimate and region sum1, sum2. */
+int e3d_disp_eval_get_sums(e3d_disp_eval_t* eval, double* sums);
+/* quantiles[n_est][2][P]. */
+int e3d_disp_eval_get_quantiles(e3d_disp_eval_t* eval, float* quantiles);
+/* HIP-event times of the call's kernel groups in ms and their names (static strings), at most capacity of each (either
+ * array may be NULL); returns the number of groups: classify, select, sums. */
+int e3d_disp_eval_kernel_ms(e3d_disp_eval_t* eval, float* ms, const char** names, int capacity);
+
 #ifdef __cplusplus
 }
 #endif
