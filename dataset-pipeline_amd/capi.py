@@ -208,6 +208,8 @@ SIGNATURES = {
     "e3d_surface_get_mesh": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "e3d_surface_kernel_ms": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "e3d_surface_reconstruct_csg": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_void_p, C.c_size_t]),
+    "e3d_surface_reconstruct_filled": (C.c_void_p, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_float, C.c_float, C.c_int, C.c_void_p, C.c_size_t]),
+    "e3d_surface_get_fill": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
     # ReconstructionEvaluator: accuracy and completeness of a reconstruction against the scans
     "e3d_evaluate_reconstruction": (C.c_void_p, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_float, C.c_int]),
     "e3d_eval_destroy": (None, [C.c_void_p]),
@@ -613,18 +615,25 @@ def _surface_solids(solids):
     return ops
 
 
-def reconstruct_surface(xyz, normals, voxel_size, support_radius=None, return_corners=False, timings=None, solids=None):
+def reconstruct_surface(xyz, normals, voxel_size, support_radius=None, return_corners=False, timings=None, solids=None, fill_iterations=0):
     """SurfaceReconstructor (include/e3d_hip.h, e3d_surface_reconstruct) -> (vertices[v, 3] f32, triangles[t, 3] uint32), and with
     return_corners a dict of the defined corners in ascending (k, j, i): ijk[c, 3] int32, f[c], weight[c] f64, count[c] int32, plus
     the vertices' cells cell_ijk[v, 3] int32.  support_radius defaults to 2 x voxel_size (in f32).  timings: a dict that receives the
     HIP-event time of every kernel group as <group>_ms.  solids: a list of (kind, centre[3], rotation[3, 3], half_extent[3]) with kind
-    "union" or "subtract", applied in order to the scan field (e3d_surface_reconstruct_csg); None calls e3d_surface_reconstruct."""
+    "union" or "subtract", applied in order to the scan field (e3d_surface_reconstruct_csg); None calls e3d_surface_reconstruct.
+    fill_iterations = N > 0: N iterations of hole filling before the solids (e3d_surface_reconstruct_filled); the dict of
+    return_corners then also holds corner_filled[c] and vertex_filled[v] (bool)."""
     keep = []
     n = int(xyz.shape[0])
     h = np.float32(voxel_size)
     r = np.float32(2) * h if support_radius is None else np.float32(support_radius)
     px, pn = (_ptr(xyz, np.float32, keep), _ptr(normals, np.float32, keep)) if n else (None, None)
-    if solids is None:
+    fill_iterations = int(fill_iterations)
+    if fill_iterations != 0:
+        solids = list(solids or ())
+        ops = _surface_solids(solids)
+        handle = lib().e3d_surface_reconstruct_filled(px, pn, n, float(h), float(r), fill_iterations, C.cast(ops, C.c_void_p), len(solids))
+    elif solids is None:
         handle = lib().e3d_surface_reconstruct(px, pn, n, float(h), float(r))
     else:
         solids = list(solids)
@@ -646,6 +655,13 @@ def reconstruct_surface(xyz, normals, voxel_size, support_radius=None, return_co
                        "count": np.zeros(nc.value, np.int32), "cell_ijk": cells}
             if lib().e3d_surface_get_corners(handle, *(C.c_void_p(corners[k].ctypes.data) for k in ("ijk", "f", "weight", "count"))) < 0:
                 _err("e3d_surface_get_corners")
+            if fill_iterations != 0:
+                corners["corner_filled"] = np.zeros(nc.value, np.uint8)
+                corners["vertex_filled"] = np.zeros(nv.value, np.uint8)
+                if lib().e3d_surface_get_fill(handle, C.c_void_p(corners["corner_filled"].ctypes.data), C.c_void_p(corners["vertex_filled"].ctypes.data)) < 0:
+                    _err("e3d_surface_get_fill")
+                corners["corner_filled"] = corners["corner_filled"].astype(bool)
+                corners["vertex_filled"] = corners["vertex_filled"].astype(bool)
         if timings is not None:
             ms = (C.c_float * 16)()
             names = (C.c_char_p * 16)()

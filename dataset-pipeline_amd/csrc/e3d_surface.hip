@@ -12,7 +12,10 @@
 //              looked up 64 at a time (one per lane); each non-empty cell's run of points is staged through LDS as f64, 64 points per
 //              step, and every lane adds the staged points that count for its corner.  A corner's sums live in one lane and are
 //              formed in grid order: no atomics, and the launch order cannot show
-//  solids      (e3d_surface_reconstruct_csg only) oriented boxes united with or subtracted from the field before the corners are
+//  fill        (e3d_surface_reconstruct_filled with N > 0 only) N Jacobi iterations that extend the field into undefined corners next to
+//              where the surface ends, on a brick list enlarged by floor((N + 9) / 4) face steps: per iteration k_surf_fill_x,
+//              k_surf_fill_x1 and k_surf_fill_update, one wave per brick, neighbours by __shfl and from the six face-neighbour bricks
+//  solids      (with operations only) oriented boxes united with or subtracted from the field before the corners are
 //              compacted: k_surf_solid_brick_keys adds the bricks of every union box's band to the candidates, k_surf_apply_solids
 //              applies the operation list per candidate corner and writes the defined flag
 //  corners     the defined corners compacted and sorted by (k, j, i)
@@ -34,10 +37,12 @@ namespace e3d {
 constexpr int kSurfBlock = 256;
 constexpr int kSurfOrgMargin = 16;                 // lattice units kept free below the lowest occupied voxel: dilation (<= 9) + a cell
 constexpr int kSurfGridBias = 1 << 20;             // grid-cell coordinates are in [-2^20, 2^20): cell >= h and |p| / h < 2^20
-constexpr int kSurfGroups = 5;                     // of a call without solids; with solids one more, "solids", last
-constexpr int kSurfMaxGroups = 6;
-static const char* const kSurfGroupNames[kSurfMaxGroups] = {"grid", "candidates", "field", "corners", "extract", "solids"};
+constexpr int kSurfGroups = 5;                     // of a plain call; with solids one more, "solids", and with hole filling "fill", last
+constexpr int kSurfMaxGroups = 7;
+static const char* const kSurfGroupNames[kSurfGroups] = {"grid", "candidates", "field", "corners", "extract"};
 constexpr int kSurfMaxOps = 256;
+constexpr int kSurfMaxFill = 32;                   // iterations of the hole filling
+constexpr int kSurfFillMargin = 4;                 // lattice steps beyond them that the range and span limits keep free
 
 struct SurfParams {
   double h, R, R2;
@@ -435,6 +440,188 @@ __global__ __launch_bounds__(kSurfBlock) void k_surf_triangles(const unsigned* _
   o[0] = q[0]; o[1] = q[1]; o[2] = q[2]; o[3] = q[0]; o[4] = q[2]; o[5] = q[3];
 }
 
+// ---- hole filling (e3d_surface_reconstruct_filled; the rules: include/e3d_hip.h) ---------------------------------------------------------
+// A corner's state is one byte: defined, source (defined by the scan field), negative (f < 0, so that the X pass reads no f).  One
+// wave per brick, one corner per lane as in k_surf_field.  A face neighbour inside the brick is read from the neighbouring lane's
+// register (__shfl), one across a face from the neighbour brick's arrays (16 lanes per direction).  An iteration is three passes
+// with a reach of one cell each -- X, X1, then growth and smoothing -- so only the six face-neighbour bricks are ever read, and
+// every pass reads state t - 1 and writes other arrays: no atomics, no dependence on the launch order.
+constexpr unsigned kFillDefined = 1, kFillSource = 2, kFillNegative = 4;
+
+// which bricks hold a defined corner of the scan field: the seeds of the candidate set
+__global__ __launch_bounds__(64) void k_surf_fill_seed_flags(const int* __restrict__ count, unsigned char* __restrict__ flags) {
+  const bool any = __any(count[(size_t)blockIdx.x * 64 + threadIdx.x] > 0);
+  if (threadIdx.x == 0) flags[blockIdx.x] = any ? 1 : 0;
+}
+
+// the face neighbour `d` (-x, +x, -y, +y, -z, +z) of a brick, or the brick itself where the neighbour leaves the 19 bits per axis
+__device__ __forceinline__ unsigned long long surf_fill_neighbour_key(unsigned long long key, int d) {
+  int b[3] = {(int)(key & 0x1FFFFF), (int)((key >> 21) & 0x1FFFFF), (int)((key >> 42) & 0x1FFFFF)};
+  const int v = b[d >> 1] + ((d & 1) ? 1 : -1);
+  if (v >= 0 && v < (1 << 19)) b[d >> 1] = v;
+  return cell_key(b[0], b[1], b[2]);
+}
+
+// one step of the dilation: every brick and its six face neighbours (sorted + unique afterwards)
+__global__ __launch_bounds__(kSurfBlock) void k_surf_fill_dilate(const unsigned long long* __restrict__ bricks, size_t n, unsigned long long* __restrict__ out) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 7 * n) return;
+  const unsigned long long key = bricks[t / 7];
+  const int slot = (int)(t % 7);
+  out[t] = slot ? surf_fill_neighbour_key(key, slot - 1) : key;
+}
+
+// f, W and count re-laid onto the enlarged brick list (zero where the old list has no such brick, as k_surf_field writes where no
+// point counts), the corners' first state and the per-brick flag "holds a defined corner"
+__global__ __launch_bounds__(64) void k_surf_fill_relay(const unsigned long long* __restrict__ bricks, const unsigned long long* __restrict__ old_bricks, size_t n_old,
+                                                        const double* __restrict__ f_old, const double* __restrict__ w_old, const int* __restrict__ count_old,
+                                                        double* __restrict__ f, double* __restrict__ w, int* __restrict__ count, unsigned char* __restrict__ state,
+                                                        unsigned char* __restrict__ holds) {
+  const int lane = threadIdx.x;
+  const long long ob = surf_find(old_bricks, n_old, bricks[blockIdx.x]);
+  double fv = 0.0, wv = 0.0;
+  int c = 0;
+  if (ob >= 0) { const size_t so = (size_t)ob * 64 + lane; fv = f_old[so]; wv = w_old[so]; c = count_old[so]; }
+  const size_t o = (size_t)blockIdx.x * 64 + lane;
+  f[o] = fv; w[o] = wv; count[o] = c;
+  state[o] = (unsigned char)(c > 0 ? (kFillDefined | kFillSource | (fv < 0.0 ? kFillNegative : 0u)) : 0u);
+  const bool any = __any(c > 0);
+  if (lane == 0) holds[blockIdx.x] = any ? 1 : 0;
+}
+
+// the six face-neighbour bricks of every brick as indices into the sorted list, -1 where there is none
+__global__ __launch_bounds__(kSurfBlock) void k_surf_fill_neighbours(const unsigned long long* __restrict__ bricks, size_t n, int* __restrict__ nbr) {
+  const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= 6 * n) return;
+  const unsigned long long key = bricks[t / 6], nk = surf_fill_neighbour_key(key, (int)(t % 6));
+  nbr[t] = nk == key ? -1 : (int)surf_find(bricks, n, nk);
+}
+
+// Nothing can change in a brick while neither it nor a face neighbour holds a defined corner: wave-uniform, before any value is read
+__device__ __forceinline__ bool surf_fill_active(const int* __restrict__ nbr, const unsigned char* __restrict__ holds, int lane) {
+  const int q = lane < 6 ? nbr[6 * (size_t)blockIdx.x + lane] : lane == 6 ? (int)blockIdx.x : -1;
+  return __any(q >= 0 && holds[q] != 0);
+}
+
+// the value of the face neighbour d of this lane's corner: `own` of the neighbouring lane, or a[] of the neighbour brick's corner
+template <class T>
+__device__ __forceinline__ T surf_fill_gather(const T* __restrict__ a, int nb, int lane, T own, int d, bool wanted = true) {
+  const int shift = 2 * (d >> 1), stride = 1 << shift, c = (lane >> shift) & 3;
+  const bool up = d & 1;
+  const bool edge = up ? c == 3 : c == 0;
+  T v = __shfl(own, (up ? lane + stride : lane - stride) & 63, 64);
+  if (edge) v = (nb >= 0 && wanted) ? a[(size_t)nb * 64 + (up ? lane - 3 * stride : lane + 3 * stride)] : T(0);
+  return v;
+}
+
+// X(y): y is defined and has a defined neighbour of the other sign
+__global__ __launch_bounds__(64) void k_surf_fill_x(const int* __restrict__ nbr, const unsigned char* __restrict__ holds, const unsigned char* __restrict__ state,
+                                                    unsigned char* __restrict__ x) {
+  const int lane = threadIdx.x;
+  if (!surf_fill_active(nbr, holds, lane)) return;
+  const size_t o = (size_t)blockIdx.x * 64 + lane;
+  const unsigned own = state[o];
+  bool hit = false;
+#pragma unroll
+  for (int d = 0; d < 6; ++d) {
+    const unsigned s = surf_fill_gather<unsigned char>(state, nbr[6 * (size_t)blockIdx.x + d], lane, (unsigned char)own, d);
+    hit = hit || ((s & kFillDefined) && ((s ^ own) & kFillNegative));
+  }
+  x[o] = (own & kFillDefined) && hit ? 1 : 0;
+}
+
+// X1(y): y is defined and X holds for y or for one of its neighbours
+__global__ __launch_bounds__(64) void k_surf_fill_x1(const int* __restrict__ nbr, const unsigned char* __restrict__ holds, const unsigned char* __restrict__ state,
+                                                     const unsigned char* __restrict__ x, unsigned char* __restrict__ x1) {
+  const int lane = threadIdx.x;
+  if (!surf_fill_active(nbr, holds, lane)) return;
+  const size_t o = (size_t)blockIdx.x * 64 + lane;
+  const unsigned char own = x[o];
+  unsigned hit = own;
+#pragma unroll
+  for (int d = 0; d < 6; ++d) hit |= surf_fill_gather<unsigned char>(x, nbr[6 * (size_t)blockIdx.x + d], lane, own, d);
+  x1[o] = (state[o] & kFillDefined) && hit ? 1 : 0;
+}
+
+// growth and smoothing: state and f of iteration t from those of t - 1
+__global__ __launch_bounds__(64) void k_surf_fill_update(const int* __restrict__ nbr, const unsigned char* __restrict__ holds, const unsigned char* __restrict__ state,
+                                                         const unsigned char* __restrict__ x1, const double* __restrict__ f, unsigned char* __restrict__ state_out,
+                                                         double* __restrict__ f_out, unsigned char* __restrict__ holds_out) {
+  const int lane = threadIdx.x;
+  if (!surf_fill_active(nbr, holds, lane)) return;
+  const size_t o = (size_t)blockIdx.x * 64 + lane;
+  const unsigned char own = state[o], own_x1 = x1[o];
+  const double own_f = f[o];
+  bool near = false;
+  double s = 0.0;
+  int c = 0;
+#pragma unroll
+  for (int d = 0; d < 6; ++d) {
+    const int nb = nbr[6 * (size_t)blockIdx.x + d];
+    const unsigned ns = surf_fill_gather<unsigned char>(state, nb, lane, own, d);
+    const unsigned nx1 = surf_fill_gather<unsigned char>(x1, nb, lane, own_x1, d);   // (every lane takes part in the gather's __shfl)
+    near = near || nx1 != 0;
+    const double nf = surf_fill_gather<double>(f, nb, lane, own_f, d, (ns & kFillDefined) != 0);
+    if (ns & kFillDefined) { s += nf; ++c; }
+  }
+  unsigned st = own;
+  double v = own_f;
+  if (!(own & kFillDefined)) {
+    if (near) { v = s / (double)c; st = kFillDefined | (v < 0.0 ? kFillNegative : 0u); }
+  } else if (!(own & kFillSource)) {
+    s += own_f; ++c;
+    v = s / (double)c;
+    st = kFillDefined | (v < 0.0 ? kFillNegative : 0u);
+  }
+  state_out[o] = (unsigned char)st;
+  f_out[o] = v;
+  const bool any = __any((st & kFillDefined) != 0);
+  if (lane == 0) holds_out[blockIdx.x] = any ? 1 : 0;
+}
+
+// After the last iteration: the defined flag the extraction reads, and the number the solids' kernel takes for "a point counts"
+// (k_surf_apply_solids starts from count > 0): a filled corner enters it as an ordinary defined corner.  Its public count stays 0.
+__global__ __launch_bounds__(kSurfBlock) void k_surf_fill_finish(const unsigned char* __restrict__ state, const int* __restrict__ count, size_t n_slots,
+                                                                 unsigned char* __restrict__ defined, int* __restrict__ defined_count) {
+  const size_t j = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= n_slots) return;
+  const bool def = (state[j] & kFillDefined) != 0;
+  defined[j] = def ? 1 : 0;
+  defined_count[j] = def ? max(count[j], 1) : 0;
+}
+
+__device__ __forceinline__ bool surf_fill_filled(const unsigned char* __restrict__ state, long long slot) {
+  return (state[slot] & (kFillDefined | kFillSource)) == kFillDefined;
+}
+// the flag `filled` of the sorted corners
+__global__ __launch_bounds__(kSurfBlock) void k_surf_fill_corner_flags(const unsigned* __restrict__ slots, size_t n_corners, const unsigned char* __restrict__ state,
+                                                                       unsigned char* __restrict__ out) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c < n_corners) out[c] = surf_fill_filled(state, slots[c]) ? 1 : 0;
+}
+// a vertex is filled iff a crossing edge of its cell has a filled endpoint (the 12 edges as k_surf_vertices visits them)
+__global__ __launch_bounds__(kSurfBlock) void k_surf_fill_vertex_flags(const unsigned long long* __restrict__ cells, size_t n_cells, SurfField F,
+                                                                       const unsigned char* __restrict__ state, unsigned char* __restrict__ out) {
+  const size_t c = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= n_cells) return;
+  const unsigned long long key = cells[c];
+  const int o[3] = {(int)(key & 0x1FFFFF), (int)((key >> 21) & 0x1FFFFF), (int)((key >> 42) & 0x1FFFFF)};
+  bool filled = false;
+  for (int d = 0; d < 3; ++d) {
+    const int u = (d + 1) % 3, v = (d + 2) % 3;
+    for (int dv = 0; dv < 2; ++dv)
+      for (int du = 0; du < 2; ++du) {
+        int a[3] = {o[0], o[1], o[2]};
+        a[u] += du; a[v] += dv;
+        double t; bool neg;
+        if (!surf_edge(F, a[0], a[1], a[2], d, t, neg)) continue;
+        filled = filled || surf_fill_filled(state, surf_corner_slot(F.bricks, F.n_bricks, a[0], a[1], a[2])) ||
+                 surf_fill_filled(state, surf_corner_slot(F.bricks, F.n_bricks, a[0] + (d == 0), a[1] + (d == 1), a[2] + (d == 2)));
+      }
+  }
+  out[c] = filled ? 1 : 0;
+}
+
 static int bits_for(unsigned v) { int b = 0; while (b < 32 && (v >> b)) ++b; return b; }
 
 }  // namespace e3d
@@ -446,7 +633,9 @@ struct e3d_surface {
   std::vector<double> corner_f, corner_w;
   std::vector<float> vertices;
   std::vector<uint32_t> triangles;
-  float ms[kSurfMaxGroups] = {0, 0, 0, 0, 0, 0};
+  std::vector<uint8_t> corner_filled, vertex_filled;  // all zero unless the call filled holes
+  float ms[kSurfMaxGroups] = {0, 0, 0, 0, 0, 0, 0};
+  const char* names[kSurfMaxGroups] = {kSurfGroupNames[0], kSurfGroupNames[1], kSurfGroupNames[2], kSurfGroupNames[3], kSurfGroupNames[4], nullptr, nullptr};
   int groups = kSurfGroups;
 };
 
@@ -502,16 +691,20 @@ void check_solids(SurfSolids& S, const e3d_surface_solid_t* ops, size_t n_ops, d
 }
 
 void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius,
-                 const e3d_surface_solid_t* ops, size_t n_ops) {
+                 int fill_iterations, const e3d_surface_solid_t* ops, size_t n_ops) {
   const double h = (double)voxel_size, R = (double)support_radius;
+  const int N = fill_iterations;
   if (!std::isfinite(h) || !(h > 0.0)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the voxel size must be positive and finite");
   if (!std::isfinite(R) || !(R > 0.0)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: the support radius must be positive and finite");
   if (R / h > 8.0) throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct: support radius / voxel size = %g, at most 8", R / h));
   if (n && (!xyz || !normals)) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: null argument");
   if (n >= (size_t)1 << 31) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: more than 2^31-1 points");
+  if (N < 0 || N > kSurfMaxFill)
+    throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_filled: fill_iterations = %d, 0 to %d are possible", N, kSurfMaxFill));
   SurfSolids solids;
   check_solids(solids, ops, n_ops, h);
-  if (n_ops) out.groups = kSurfMaxGroups;
+  if (n_ops) out.names[out.groups++] = "solids";
+  if (N) out.names[out.groups++] = "fill";
   require_device();
   // without a union nothing can be defined where no point counts: subtracting from nothing gives nothing
   if (n == 0 && !solids.any_union) return;
@@ -546,6 +739,13 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   }
   const size_t m = (size_t)hb[7];
   if (m == 0 && !solids.any_union) return;
+  // the fill can define corners up to N steps beyond the scan field's: the limits hold for the voxels' box grown by N + 4
+  if (N && m)
+    for (int a = 0; a < 3; ++a) {
+      hb[a] -= N + kSurfFillMargin; hb[3 + a] += N + kSurfFillMargin;
+      if (hb[a] < -(1 << 20) || hb[3 + a] >= (1 << 20))
+        throw Error(E3D_ERR_INVALID, fmt("e3d_surface_reconstruct_filled: a point lies within fill_iterations + %d voxels of |coordinate| / voxel size = 2^20", kSurfFillMargin));
+    }
 
   SurfParams P{};
   P.h = h; P.R = R; P.R2 = R * R;
@@ -563,8 +763,9 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
     P.org[a] = (int)(std::floor((double)(lo[a] - kSurfOrgMargin) / 4.0) * 4.0);
     ext[a] = (unsigned)(hi[a] - P.org[a] + kSurfOrgMargin);
     if (ext[a] >= (1u << 21))
-      throw Error(E3D_ERR_INVALID, n_ops ? "e3d_surface_reconstruct: the cloud and the solids span more than 2^21 - 36 voxels along an axis"
-                                         : "e3d_surface_reconstruct: the cloud spans more than 2^21 - 36 voxels along an axis");
+      throw Error(E3D_ERR_INVALID, N ? "e3d_surface_reconstruct_filled: the cloud grown by fill_iterations + 4 voxels on every side (and the solids) spans more than 2^21 - 36 voxels along an axis"
+                                   : n_ops ? "e3d_surface_reconstruct: the cloud and the solids span more than 2^21 - 36 voxels along an axis"
+                                           : "e3d_surface_reconstruct: the cloud spans more than 2^21 - 36 voxels along an axis");
   }
   const int key_bits = 42 + bits_for(ext[2]);
 
@@ -641,9 +842,9 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   kb.reserve(n_brick_keys + n_solid_keys);
   if (n_brick_keys) hipLaunchKernelGGL(k_surf_brick_keys, blocks(n_brick_keys), dim3(kSurfBlock), 0, s, voxels.p, n_voxels, P.D, M, kb.p);
   if (n_solid_keys) E3D_HIP(hipMemcpyAsync(kb.p + n_brick_keys, solid_keys.p, sizeof(unsigned long long) * n_solid_keys, hipMemcpyDeviceToDevice, s));
-  const size_t n_bricks = run.sort_unique(kb, ka, bricks, n_brick_keys + n_solid_keys, key_bits, scatter_keys);
+  size_t n_bricks = run.sort_unique(kb, ka, bricks, n_brick_keys + n_solid_keys, key_bits, scatter_keys);
   timer[1].stop(s);
-  const size_t n_slots = n_bricks * 64;
+  size_t n_slots = n_bricks * 64;
   if (n_slots > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many candidate corners for one call");
   if (n_bricks == 0) { E3D_HIP(hipStreamSynchronize(s)); return; }
 
@@ -656,20 +857,81 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   timer[2].stop(s);
   E3D_HIP(hipGetLastError());
 
+  // ---- fill: N iterations that extend the scan field next to where the surface ends ------------------------------------------------
+  GroupTimer fill_timer;
+  DevBuf<unsigned char> defined, fill_state;
+  DevBuf<int> defined_count;                                           // what the solids' kernel reads as "a point counts" after a fill
+  bool filled = false;
+  if (N) {
+    fill_timer.start(s);
+    // the seeds: the bricks that hold a defined corner
+    run.flags.reserve(n_bricks);
+    hipLaunchKernelGGL(k_surf_fill_seed_flags, dim3((unsigned)n_bricks), dim3(64), 0, s, count.p, run.flags.p);
+    size_t n_grown = run.scan(n_bricks);
+    filled = n_grown > 0;
+    if (filled) {
+      // Candidates: every brick within floor((N + 9) / 4) face steps of a seed.  A corner defined in iteration t has a defined
+      // neighbour in t - 1, so it lies within N lattice steps of a source; n steps along an axis cross at most ceil(n / 4) brick
+      // faces, over three axes at most (N + 9) / 4.  Bricks beyond them stay empty, so which bricks are candidates shows nowhere.
+      DevBuf<unsigned long long> grown, next;
+      grown.reserve(n_grown);
+      scatter_keys(bricks.p, n_bricks, grown.p);
+      for (int step = 0; step < (N + 9) / 4; ++step) {
+        if (7 * n_grown > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct_filled: too many candidate bricks of the fill for one call");
+        kb.reserve(7 * n_grown);
+        hipLaunchKernelGGL(k_surf_fill_dilate, blocks(7 * n_grown), dim3(kSurfBlock), 0, s, grown.p, n_grown, kb.p);
+        n_grown = run.sort_unique(kb, ka, next, 7 * n_grown, key_bits, scatter_keys);
+        std::swap(grown, next);
+      }
+      // ... together with the candidates so far (those of the solids among them): f, W and count move to the enlarged list
+      if (n_grown + n_bricks > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct_filled: too many candidate bricks of the fill for one call");
+      kb.reserve(n_grown + n_bricks);
+      E3D_HIP(hipMemcpyAsync(kb.p, grown.p, sizeof(unsigned long long) * n_grown, hipMemcpyDeviceToDevice, s));
+      E3D_HIP(hipMemcpyAsync(kb.p + n_grown, bricks.p, sizeof(unsigned long long) * n_bricks, hipMemcpyDeviceToDevice, s));
+      const size_t n_all = run.sort_unique(kb, ka, next, n_grown + n_bricks, key_bits, scatter_keys);
+      if (n_all * 64 > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct_filled: too many candidate corners of the fill for one call");
+      const size_t all_slots = n_all * 64;
+      DevBuf<double> f2, w2, f_next;
+      DevBuf<int> count2, nbr;
+      DevBuf<unsigned char> state_next, holds, holds_next, x, x1;
+      f2.reserve(all_slots); w2.reserve(all_slots); count2.reserve(all_slots); f_next.reserve(all_slots); nbr.reserve(6 * n_all);
+      fill_state.reserve(all_slots); state_next.reserve(all_slots); x.reserve(all_slots); x1.reserve(all_slots); holds.reserve(n_all); holds_next.reserve(n_all);
+      hipLaunchKernelGGL(k_surf_fill_relay, dim3((unsigned)n_all), dim3(64), 0, s, next.p, bricks.p, n_bricks, f.p, w.p, count.p, f2.p, w2.p, count2.p, fill_state.p, holds.p);
+      hipLaunchKernelGGL(k_surf_fill_neighbours, blocks(6 * n_all), dim3(kSurfBlock), 0, s, next.p, n_all, nbr.p);
+      // a brick that is not active in an iteration writes nothing: it holds no defined corner, in either copy
+      E3D_HIP(hipMemsetAsync(state_next.p, 0, all_slots, s));
+      E3D_HIP(hipMemsetAsync(x.p, 0, all_slots, s));
+      E3D_HIP(hipMemsetAsync(x1.p, 0, all_slots, s));
+      E3D_HIP(hipMemsetAsync(holds_next.p, 0, n_all, s));               // (f of an undefined corner is never read)
+      std::swap(bricks, next); std::swap(f, f2); std::swap(w, w2); std::swap(count, count2);
+      n_bricks = n_all; n_slots = all_slots;
+      for (int t = 0; t < N; ++t) {
+        hipLaunchKernelGGL(k_surf_fill_x, dim3((unsigned)n_bricks), dim3(64), 0, s, nbr.p, holds.p, fill_state.p, x.p);
+        hipLaunchKernelGGL(k_surf_fill_x1, dim3((unsigned)n_bricks), dim3(64), 0, s, nbr.p, holds.p, fill_state.p, x.p, x1.p);
+        hipLaunchKernelGGL(k_surf_fill_update, dim3((unsigned)n_bricks), dim3(64), 0, s, nbr.p, holds.p, fill_state.p, x1.p, f.p, state_next.p, f_next.p, holds_next.p);
+        std::swap(fill_state, state_next); std::swap(f, f_next); std::swap(holds, holds_next);
+      }
+      defined.reserve(n_slots); defined_count.reserve(n_slots);
+      hipLaunchKernelGGL(k_surf_fill_finish, blocks(n_slots), dim3(kSurfBlock), 0, s, fill_state.p, count.p, n_slots, defined.p, defined_count.p);
+      E3D_HIP(hipStreamSynchronize(s));                                  // the buffers of this block are freed
+    }
+    fill_timer.stop(s);
+    E3D_HIP(hipGetLastError());
+  }
+
   // ---- solids: the operation list at every candidate corner ---------------------------------------------------------------------------
-  DevBuf<unsigned char> defined;
   defined.reserve(n_slots);
   if (n_ops) {
     solid_timer.start(s);
-    hipLaunchKernelGGL(k_surf_apply_solids, blocks(n_slots), dim3(kSurfBlock), sizeof(double) * 16 * n_ops, s, bricks.p, n_slots, d_ops.p, (int)n_ops, P, count.p,
-                       f.p, defined.p);
+    hipLaunchKernelGGL(k_surf_apply_solids, blocks(n_slots), dim3(kSurfBlock), sizeof(double) * 16 * n_ops, s, bricks.p, n_slots, d_ops.p, (int)n_ops, P,
+                       filled ? defined_count.p : count.p, f.p, defined.p);
     solid_timer.stop(s);
     E3D_HIP(hipGetLastError());
   }
 
   // ---- corners: the defined ones in (k, j, i) ------------------------------------------------------------------------------------------
   timer[3].start(s);
-  if (!n_ops) hipLaunchKernelGGL(k_surf_corner_flags, blocks(n_slots), dim3(kSurfBlock), 0, s, count.p, n_slots, defined.p);
+  if (!n_ops && !filled) hipLaunchKernelGGL(k_surf_corner_flags, blocks(n_slots), dim3(kSurfBlock), 0, s, count.p, n_slots, defined.p);
   const size_t n_corners = run.scan(defined.p, n_slots);
   if (3 * n_corners > kMaxItems) throw Error(E3D_ERR_INVALID, "e3d_surface_reconstruct: too many corners for one call");
   DevBuf<unsigned long long> ck;
@@ -718,10 +980,24 @@ void reconstruct(e3d_surface& out, const float* xyz, const float* normals, size_
   copy_out(out.vertices.data(), vertices.p, sizeof(float) * 3 * n_cells, s);
   copy_out(out.cell_ijk.data(), cell_ijk.p, sizeof(int32_t) * 3 * n_cells, s);
   copy_out(out.triangles.data(), tri.p, sizeof(uint32_t) * 6 * n_edges, s);
+  // ---- fill: which corners and vertices it made ---------------------------------------------------------------------------------------
+  out.corner_filled.assign(n_corners, 0); out.vertex_filled.assign(n_cells, 0);
+  DevBuf<unsigned char> corner_filled, vertex_filled;
+  if (filled) {
+    fill_timer.start(s);
+    corner_filled.reserve(n_corners); vertex_filled.reserve(n_cells);
+    if (n_corners) hipLaunchKernelGGL(k_surf_fill_corner_flags, blocks(n_corners), dim3(kSurfBlock), 0, s, cs.p, n_corners, fill_state.p, corner_filled.p);
+    if (n_cells) hipLaunchKernelGGL(k_surf_fill_vertex_flags, blocks(n_cells), dim3(kSurfBlock), 0, s, cells.p, n_cells, F, fill_state.p, vertex_filled.p);
+    fill_timer.stop(s);
+    copy_out(out.corner_filled.data(), corner_filled.p, n_corners, s);
+    copy_out(out.vertex_filled.data(), vertex_filled.p, n_cells, s);
+  }
   E3D_HIP(hipStreamSynchronize(s));
   E3D_HIP(hipGetLastError());
   for (int g = 0; g < kSurfGroups; ++g) out.ms[g] = timer[g].ms();
-  if (n_ops) out.ms[kSurfGroups] = solid_timer.ms();
+  int group = kSurfGroups;
+  if (n_ops) out.ms[group++] = solid_timer.ms();
+  if (N) out.ms[group++] = fill_timer.ms();
   static const bool trace = env_default_off("E3D_SURFACE_TRACE");
   if (trace)
     fprintf(stderr, "[surface] %zu points, %zu contribute, %zu voxels, %zu bricks (%zu candidate corners), %zu grid cells, %zu corners, %zu crossing edges, %zu vertices, %zu operations, %zu bricks of solids\n",
@@ -736,7 +1012,7 @@ e3d_surface_t* e3d_surface_reconstruct(const float* xyz, const float* normals, s
   e3d_surface* h = nullptr;
   E3D_TRY
   h = new e3d_surface;
-  reconstruct(*h, xyz, normals, n, voxel_size, support_radius, nullptr, 0);
+  reconstruct(*h, xyz, normals, n, voxel_size, support_radius, 0, nullptr, 0);
   return h;
   E3D_CATCH_NEW(h)
 }
@@ -746,7 +1022,17 @@ e3d_surface_t* e3d_surface_reconstruct_csg(const float* xyz, const float* normal
   e3d_surface* h = nullptr;
   E3D_TRY
   h = new e3d_surface;
-  reconstruct(*h, xyz, normals, n, voxel_size, support_radius, ops, n_ops);
+  reconstruct(*h, xyz, normals, n, voxel_size, support_radius, 0, ops, n_ops);
+  return h;
+  E3D_CATCH_NEW(h)
+}
+
+e3d_surface_t* e3d_surface_reconstruct_filled(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius, int fill_iterations,
+                                              const e3d_surface_solid_t* ops, size_t n_ops) {
+  e3d_surface* h = nullptr;
+  E3D_TRY
+  h = new e3d_surface;
+  reconstruct(*h, xyz, normals, n, voxel_size, support_radius, fill_iterations, ops, n_ops);
   return h;
   E3D_CATCH_NEW(h)
 }
@@ -786,12 +1072,21 @@ int e3d_surface_get_mesh(e3d_surface_t* h, float* vertices, int32_t* cell_ijk, u
   E3D_CATCH()
 }
 
+int e3d_surface_get_fill(e3d_surface_t* h, uint8_t* corner_filled, uint8_t* vertex_filled) {
+  E3D_TRY
+  if (!h) throw Error(E3D_ERR_INVALID, "e3d_surface_get_fill: null handle");
+  if (corner_filled && !h->corner_filled.empty()) memcpy(corner_filled, h->corner_filled.data(), h->corner_filled.size());
+  if (vertex_filled && !h->vertex_filled.empty()) memcpy(vertex_filled, h->vertex_filled.data(), h->vertex_filled.size());
+  return 0;
+  E3D_CATCH()
+}
+
 int e3d_surface_kernel_ms(e3d_surface_t* h, float* ms, const char** names, int capacity) {
   E3D_TRY
   if (!h) throw Error(E3D_ERR_INVALID, "e3d_surface_kernel_ms: null handle");
   for (int g = 0; g < h->groups && g < capacity; ++g) {
     if (ms) ms[g] = h->ms[g];
-    if (names) names[g] = kSurfGroupNames[g];
+    if (names) names[g] = h->names[g];
   }
   return h->groups;
   E3D_CATCH()

@@ -46,6 +46,7 @@ namespace e3d_host {
   X(e3d_edit_delete_selected) X(e3d_edit_extract_selected) X(e3d_edit_kernel_ms)                                       \
   X(e3d_surface_reconstruct) X(e3d_surface_destroy) X(e3d_surface_counts) X(e3d_surface_get_corners)                   \
   X(e3d_surface_get_mesh) X(e3d_surface_kernel_ms) X(e3d_surface_reconstruct_csg)                                      \
+  X(e3d_surface_reconstruct_filled) X(e3d_surface_get_fill)                                                            \
   X(e3d_evaluate_reconstruction) X(e3d_eval_destroy) X(e3d_eval_counts) X(e3d_eval_get_scores)                         \
   X(e3d_eval_get_classes) X(e3d_eval_get_voxels) X(e3d_eval_kernel_ms)                                                 \
   X(e3d_evaluate_disparity) X(e3d_disp_eval_destroy) X(e3d_disp_eval_get_counts) X(e3d_disp_eval_get_sums)             \

@@ -2,11 +2,16 @@
 // the merged point + normal cloud becomes the strongly subdivided triangle mesh that SplatCreator (--mesh_path), ImageRegistrator,
 // GroundTruthCreator, MaskTransfer and ImageLocalizer (--occlusion_mesh_path) read.  A signed field of the oriented points is
 // evaluated on a lattice of --voxel_size anchored at the world origin and one vertex per cell with a sign change is written
-// (e3d_surface_reconstruct; the rules: include/e3d_hip.h).  The mesh ends where the data ends: unobserved regions are not filled.
+// (e3d_surface_reconstruct; the rules: include/e3d_hip.h).  Without --fill_holes the mesh ends where the data ends.
 //
 //   SurfaceReconstructor --point_normal_cloud_path cloud.ply --output_path surface.ply [--voxel_size 0.02] [--support_radius 2 x voxel_size]
-//                        [--csg_script boxes.txt] [--print_csg_script] [--timings]
+//                        [--fill_holes N] [--filled_mesh_path filled.ply] [--csg_script boxes.txt] [--print_csg_script] [--timings]
 //
+// --fill_holes N (0 to 32, default 0): N iterations that extend the signed field next to where the surface ends, before the boxes of
+// --csg_script (e3d_surface_reconstruct_filled): holes up to about 2 (N + support_radius / voxel_size) cells wide close, and at an
+// outer boundary of the data the sheet grows by up to N cells.  The value is checked with the other arguments, before anything is
+// loaded.  --filled_mesh_path writes the triangles the fill made (those with a filled vertex) in the same PLY layout, all vertices
+// kept, for inspection.  One line reports the numbers of filled corners, vertices and triangles.
 // --csg_script: what the reference's editor does by hand with its CSG tool (src/point_cloud_editor/tool_csg.cc: a box united with or
 // subtracted from the surface mesh where the scanner missed glass or dark objects), as a text file that is applied again whenever the
 // surface is rebuilt (e3d_surface_reconstruct_csg).  `#` starts a comment; otherwise one operation per line, applied in order:
@@ -77,6 +82,21 @@ bool parse_csg_line(const std::vector<std::string>& tok, e3d_surface_solid_t* op
   return true;
 }
 
+// --fill_holes: an integer in [0, 32], nothing behind it
+bool parse_fill_holes(int argc, char** argv, int* n) {
+  const int at = find_argument(argc, argv, "--fill_holes");
+  if (at < 0) return true;
+  const char* text = at + 1 < argc ? argv[at + 1] : nullptr;
+  char* end = nullptr;
+  const long v = text ? strtol(text, &end, 10) : 0;
+  if (!text || end == text || *end != 0 || v < 0 || v > 32) {
+    std::cerr << "--fill_holes: an integer from 0 to 32 is expected, " << (text ? std::string("'") + text + "' given" : std::string("no value given")) << std::endl;
+    return false;
+  }
+  *n = (int)v;
+  return true;
+}
+
 bool read_csg_script(const std::string& path, std::vector<e3d_surface_solid_t>* ops) {
   std::ifstream f(path);
   if (!f) { std::cerr << "Cannot read the script " << path << std::endl; return false; }
@@ -114,6 +134,10 @@ int main(int argc, char** argv) {
   const bool timings = find_argument(argc, argv, "--timings") > 0;
   std::string csg_script;
   parse_argument(argc, argv, "--csg_script", csg_script);
+  int fill_holes = 0;
+  if (!parse_fill_holes(argc, argv, &fill_holes)) return EXIT_FAILURE;
+  std::string filled_mesh_path;
+  parse_argument(argc, argv, "--filled_mesh_path", filled_mesh_path);
 
   if (point_normal_cloud_path.empty() || output_path.empty()) {
     std::cout << "Please provide input / output paths." << std::endl;
@@ -142,7 +166,10 @@ int main(int argc, char** argv) {
   }
 
   std::cerr << "Reconstructing the surface ..." << std::endl;
-  e3d_surface_t* surface = csg_script.empty()
+  e3d_surface_t* surface = fill_holes > 0
+                               ? api().e3d_surface_reconstruct_filled(cloud.xyz.data(), cloud.normals.data(), cloud.size(), voxel_size, support_radius,
+                                                                      fill_holes, ops.data(), ops.size())
+                           : csg_script.empty()
                                ? api().e3d_surface_reconstruct(cloud.xyz.data(), cloud.normals.data(), cloud.size(), voxel_size, support_radius)
                                : api().e3d_surface_reconstruct_csg(cloud.xyz.data(), cloud.normals.data(), cloud.size(), voxel_size, support_radius,
                                                                    ops.data(), ops.size());
@@ -154,7 +181,9 @@ int main(int argc, char** argv) {
   api().e3d_surface_counts(surface, &n_corners, &n_vertices, &n_triangles);
   std::vector<float> vertices(3 * (size_t)n_vertices);
   std::vector<uint32_t> triangles(3 * (size_t)n_triangles);
-  const int r = api().e3d_surface_get_mesh(surface, vertices.data(), nullptr, triangles.data());
+  int r = api().e3d_surface_get_mesh(surface, vertices.data(), nullptr, triangles.data());
+  std::vector<uint8_t> corner_filled((size_t)n_corners), vertex_filled((size_t)n_vertices);
+  if (r >= 0 && fill_holes > 0) r = api().e3d_surface_get_fill(surface, corner_filled.data(), vertex_filled.data());
   if (timings) {
     float ms[16];
     const char* names[16];
@@ -174,6 +203,19 @@ int main(int argc, char** argv) {
   }
   std::vector<int32_t> faces(triangles.begin(), triangles.end());
   if (savePLYMeshBinary(output_path, vertices.data(), (size_t)n_vertices, faces.data(), (size_t)n_triangles) < 0) return EXIT_FAILURE;
+  if (fill_holes > 0) {
+    std::vector<int32_t> filled_faces;
+    for (size_t t = 0; t < (size_t)n_triangles; ++t)
+      if (vertex_filled[faces[3 * t]] || vertex_filled[faces[3 * t + 1]] || vertex_filled[faces[3 * t + 2]])
+        filled_faces.insert(filled_faces.end(), faces.begin() + 3 * t, faces.begin() + 3 * t + 3);
+    size_t fc = 0, fv = 0;
+    for (uint8_t b : corner_filled) fc += b;
+    for (uint8_t b : vertex_filled) fv += b;
+    std::cerr << "Filled: " << fc << " lattice corners, " << fv << " vertices, " << filled_faces.size() / 3 << " triangles." << std::endl;
+    if (!filled_mesh_path.empty() &&
+        savePLYMeshBinary(filled_mesh_path, vertices.data(), (size_t)n_vertices, filled_faces.data(), filled_faces.size() / 3) < 0)
+      return EXIT_FAILURE;
+  }
   std::cout << "Finished!" << std::endl;
   return EXIT_SUCCESS;
 }

@@ -900,7 +900,7 @@ int e3d_surface_get_corners(e3d_surface_t* surface, int32_t* ijk, double* f, dou
 int e3d_surface_get_mesh(e3d_surface_t* surface, float* vertices, int32_t* cell_ijk, uint32_t* triangles);
 /* HIP-event times of the call's kernel groups in ms and their names (static strings), at most capacity of each (either
  * array may be NULL); returns the number of groups: grid, candidates, field, corners, extract, and for a handle made with
- * n_ops > 0 a sixth, solids, last. */
+ * n_ops > 0 a sixth, solids; for one made with fill_iterations > 0 one more, fill, last. */
 int e3d_surface_kernel_ms(e3d_surface_t* surface, float* ms, const char** names, int capacity);
 
 /* ---- SurfaceReconstructor: box union and subtraction (the reference's CSG tool, src/point_cloud_editor/tool_csg.cc) --------
@@ -940,6 +940,48 @@ typedef struct e3d_surface_solid {
 } e3d_surface_solid_t;
 e3d_surface_t* e3d_surface_reconstruct_csg(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius,
                                            const e3d_surface_solid_t* ops, size_t n_ops);
+
+/* ---- SurfaceReconstructor: filling holes on the lattice ----------------------------------------------------------------------
+ * The scan field ends where the data ends, and every hole of the mesh lets scan points behind it shine through in the tools that
+ * use it as occlusion geometry.  The reference's README asks for a method that "is able to fill in unobserved surfaces such that
+ * occlusions by those surfaces are also accounted for"; this is volumetric diffusion of the signed field (Davis et al., "Filling
+ * holes in complex surfaces using volumetric diffusion", 2002), restricted to where the surface ends.  N = fill_iterations Jacobi
+ * iterations run between the scan field and the operation list above; the scan field, the solids and the extraction are unchanged.
+ * All arithmetic is f64, IEEE, with no contraction, in the stated order.
+ *
+ * State per lattice corner: defined, f, source.  A source is a corner the scan field defines; sources never change.  "Neighbour"
+ * means the six face neighbours, always visited in the order -x, +x, -y, +y, -z, +z.  neg(c) means f(c) < 0.
+ * Iteration t = 1 .. N reads state t - 1 only:
+ *   1. At a crossing.  X(y) holds iff y is defined and has a defined neighbour z with neg(z) != neg(y).
+ *   2. Near a crossing.  X1(y) holds iff y is defined and X(y) or X of one of its neighbours holds.
+ *   3. Growth.  An undefined corner becomes defined, with source = 0, iff one of its neighbours has X1.  Its value is
+ *      s / (double)c, where s starts at +0.0 and adds f of each defined neighbour in neighbour order and c is their number.
+ *   4. Smoothing.  A defined non-source corner is replaced by s / (double)c with s and c built as in step 3 and its own f then
+ *      added last and counted.
+ *   5. Everything else keeps its state.
+ * After iteration N the operation list is applied as above, to a field in which filled corners are ordinary defined corners (so
+ * an edit script keeps the last word: a subtract box re-opens what the fill closed wrongly).  Then "negative iff f < 0" and the
+ * unchanged extraction.  A filled corner reports count = 0 and W = 0, like a corner defined by a solid.  filled: the corners the
+ * fill defined.  A vertex is filled iff a crossing edge of its cell has a filled endpoint; a triangle iff one of its vertices is.
+ * Why growth is restricted to corners near a crossing.  Plain diffusion thickens every one-sided sheet by N cells and puts a
+ * false sheet wherever the back of one surface faces the front of another.  With rule 3 the band follows the zero set, the
+ * surface extends tangentially by one cell per iteration, and growth stops by itself once a hole has closed: a closed surface
+ * has no rim.  (Growth next to X alone leaves pinholes.)
+ * Known behaviour.  At a true outer boundary of the data the sheet is extended by up to N cells.  The extension runs along
+ * lattice directions: a wall tilted by a drifts N h tan a off its plane.  Two surfaces that face the same way 6 cells or fewer
+ * apart get a false sheet at N = 16 (at 8 cells they do not).  Holes wider than about 2 (N + R / h) cells stay open; once a hole
+ * has closed, the smoothing that goes on pulls the patch flat.
+ * Refused (NULL; E3D_ERR_INVALID, the library stays usable): fill_iterations < 0 or > 32; with N > 0 the range and span limits
+ * of e3d_surface_reconstruct applied to the voxels of the contributing points grown by N + 4 lattice steps on every side (a
+ * point within N + 4 voxels of |coordinate| / h = 2^20; a grown box, with the solids, of more than 2^21 - 36 steps along an
+ * axis); the per-call item limits applied to the enlarged brick set.  A cloud with no contributing point and N > 0 is no error.
+ * fill_iterations == 0 is e3d_surface_reconstruct_csg: the same launches, the same bytes, the same kernel groups.  With N > 0
+ * e3d_surface_kernel_ms reports one more group, fill, last (after solids when n_ops > 0, otherwise sixth). */
+e3d_surface_t* e3d_surface_reconstruct_filled(const float* xyz, const float* normals, size_t n, float voxel_size, float support_radius,
+                                              int fill_iterations, const e3d_surface_solid_t* ops, size_t n_ops);
+/* Which corners (in the order of e3d_surface_get_corners) and which vertices (in the order of e3d_surface_get_mesh) the fill made:
+ * one byte each, 0 or 1; all 0 for a handle made with fill_iterations == 0.  Each pointer may be NULL. */
+int e3d_surface_get_fill(e3d_surface_t* surface, uint8_t* corner_filled, uint8_t* vertex_filled);
 
 /* ---- ReconstructionEvaluator: accuracy and completeness of a reconstruction against the scans ----------------------------
  * The ETH3D evaluation scheme the reference's README describes and neither tree computes: a reconstruction point within a
